@@ -206,6 +206,34 @@ def waveform_check(np, voc, kept_all):
             "input": "utterances 0..2: the ORACLE's mel -> GPU vocoder (one ragged batch) vs the oracle vocoder, worst of the three"}
 
 
+DUMP_BUDGET_BYTES = 60 << 20            # --dump-outputs: the float arrays of the last timed step, at most this many bytes in all
+
+
+def dump_outputs(np, out_dir, outs, voc):
+    """--dump-outputs DIR: what the timed path handed its caller in the LAST timed step, one .npy per array: per batch of that step the
+    mel [B, T_mel, 80], the valid frame counts, the fp32 waveform [B, T_mel * hop] and its int16 conversion (the samples that crossed to
+    the host in the 'table' / 'tensors' modes, here as float32).  An array larger than its share of DUMP_BUDGET_BYTES is written as a
+    fixed, seeded sample of its flattened elements (`<name>_sample`, the same positions for the same shape on every run and build).
+    Several batches per step (--workload testset) get a `_b<j>` suffix."""
+    os.makedirs(out_dir, exist_ok=True)
+    multi = len(outs) > 1
+    cap = DUMP_BUDGET_BYTES // 4 // (3 * max(len(outs), 1))   # float32 elements per large array (mel, wav, pcm of each batch)
+    written = {}
+    for j, (mel, lens, wav) in enumerate(outs):
+        arrays = {"mel": mel.cpu().numpy().astype(np.float32), "mel_lens": lens.cpu().numpy().astype(np.float64),
+                  "wav": wav.cpu().numpy().astype(np.float32)}
+        if voc is not None:   # (None: --input resident, whose caller keeps the fp32 waveform in HBM)
+            arrays["pcm"] = voc.to_int16(wav, lens).cpu().numpy().astype(np.float32)   # the conversion of the step, recomputed bit for bit
+        for name, a in arrays.items():
+            if a.size > cap:
+                pos = np.sort(np.random.default_rng(20240611).choice(a.size, cap, replace=False))
+                a, name = a.reshape(-1)[pos], name + "_sample"
+            fname = name + (f"_b{j}" if multi else "")
+            np.save(os.path.join(out_dir, fname + ".npy"), a)
+            written[fname] = list(a.shape)
+    return written
+
+
 def voc_mode_name(voc):
     from dict_tts_amd import abi
     return {v: k for k, v in abi.VOC_PRECISIONS.items()}[voc.precision]
@@ -236,6 +264,9 @@ def main():
     ap.add_argument("--no-pipeline", action="store_true",
                     help="run the vocoder on the text->mel stream (default: vocoder of batch i on a second HIP stream, "
                          "overlapping text->mel of batch i+1; every batch is still fully processed inside the timed region)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays of the last timed step (mel, frame counts, waveform, int16 samples) as "
+                         "DIR/<name>.npy (rank 0; float32 / float64, seeded samples of arrays over the size budget)")
     ap.add_argument("--lib", default=None, help="path of a library build to load instead of the in-tree release library (same-box A/B runs "
                                                 "with the ablation build; the headline is always measured on the release library)")
     args = ap.parse_args()
@@ -286,6 +317,7 @@ def main():
     sd_np["dur_predictor.linear.0.bias"] = np.array([DUR_BIAS], np.float32)
     m = model.PortaSpeech_dict(hparams={})
     m.load_state_dict({k: T(v) for k, v in sd_np.items()})
+    m.ctx.set_noise_seed(1234 + rank)        # the device prior sample: the same noise on every run with the same arguments
     voc_sd = {k: T(v) for k, v in synth.hifigan_state_dict(1234).items()}
     voc = vocoder.HifiGAN(state_dict=voc_sd, config={**synth.hifigan_config(), "dtts_tune_flags": args.voc_tune},
                           precision=abi.VOC_PRECISIONS[args.precision])
@@ -440,15 +472,19 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        last_step = []
         for i in range(n_steps_ * steps_per_pass):
             lens, _, _ = run_step(n_warm * steps_per_pass + i, mode)
             if lens is not None:
                 kept_lens.append(lens)
+                if i >= (n_steps_ - 1) * steps_per_pass:   # (the batches of the last timed step, for --dump-outputs)
+                    last_step.append(state["last"][:3])
         torch.cuda.synchronize()                 # includes the D2H copies into pinned memory
         if dist is not None and sync_dist:
             dist.barrier()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        state["last_step"] = last_step
         return dt, int(sum(int(l.sum().item()) for l in kept_lens))
 
     # ---- fp16 range guard over the BENCHED batches: one guarded forward of each distinct batch before anything is timed.
@@ -483,6 +519,12 @@ def main():
         frames_total = int(f.item())
     else:
         frames_total = frames_rank
+
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if not state["last_step"]:
+            raise RuntimeError("--dump-outputs: rank 0 processed no batch in the last timed step")
+        dumped = dump_outputs(np, args.dump_outputs, state["last_step"], voc if args.input != "resident" else None)
 
     # ---- after the timed region, rank 0 only, nothing else on the GPU
     side = stages = iso = modes = voc2 = other = None
@@ -761,6 +803,8 @@ def main():
                                            "kernel_ms_per_forward": iso[0], "launches": iso[1], "mel_frames": iso[2],
                                            "what": "three forwards of the LAST timed batch alone on the GPU; achieved / frac are priced on THAT batch's own valid "
                                                    "frame count (mel_frames), not on the run's average batch"}
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if side:
             out["side"] = side
         if modes:

@@ -12,6 +12,21 @@ from oracle import dict_tts_ref as ref
 from oracle import hifigan_ref as href
 
 T = lambda a: torch.from_numpy(np.ascontiguousarray(a))
+GOLDEN_THREADS = 8   # torch's CPU reductions split their sums by the intra-op thread count: at 8 threads the oracle reproduces the fixtures
+# the S2PA context and the end-to-end log-durations on a CPU whose BLAS picks other kernels than the fixtures' host (measured on an AMD
+# EPYC 9575F at 8 threads: 4.3e-6 / 6.0e-6, the same under every MKL_CBWR branch; the oracle evaluated in float64: 6.4e-6 / 6.0e-6, i.e.
+# the fixtures' own fp32 rounding): fp32 re-association of these sums, not a difference of semantics
+FP32_ORDER_BOUND = 1e-5
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _pinned_threads():
+    """most bounds below are fp32 rounding of ONE summation order; a many-core host's default thread count reorders the sums (measured:
+    g5 log-durations 5.5e-6 from the fixture at 64 threads, 0 at 4 and 8), so the module runs at a fixed count and restores the default"""
+    before = torch.get_num_threads()
+    torch.set_num_threads(GOLDEN_THREADS)
+    yield
+    torch.set_num_threads(before)
 
 
 @pytest.fixture(scope="module")
@@ -40,7 +55,7 @@ def test_g2_s2pa(sd, golden_dir):
     x, keys, values, key_map, pinyin, pinyin_map, pron_modified = gc.g2_inputs()
     c, a, p, w = ref.s2pa_attention(sd, "dict_encoder.S2PA_module.s2pa_attention", T(x), T(keys), T(values),
                                     T(key_map), T(pinyin), T(pinyin_map), T(pron_modified))
-    _close(c, g["context"], 2e-6)
+    _close(c, g["context"], FP32_ORDER_BOUND)
     _close(a, g["dict_attn"], 1e-6)
     _close(p, g["pron"], 2e-6)
     _close(w, g["pron_attn"], 1e-6)
@@ -77,7 +92,7 @@ def test_g5_end2end(sd, golden_dir, which):
     r = ref.forward_infer(sd, b["word_tokens"], (b["keys"], b["values"], b["key_map"], b["pinyin"], b["pinyin_map"]),
                           b["pron_modified"], z_p=lambda B, T4: T(gc.g5_noise(B, T4, which)))
     tag = f"b{which}"
-    _close(r["dur"], g[tag + ".dur"], 5e-6)
+    _close(r["dur"], g[tag + ".dur"], FP32_ORDER_BOUND)
     _close(r["x_mask"], g[tag + ".x_mask"], 0)           # identical integer durations / T_mel
     _close(r["word_encoder_out"], g[tag + ".word_encoder_out"], 2e-5)
     _close(r["pron_attn"], g[tag + ".pron_attn"], 2e-6)

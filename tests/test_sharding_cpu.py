@@ -120,3 +120,61 @@ def test_group_device_follows_backend():
         assert group_device(FakeDist("nccl")) == torch.device("cuda", 3)
         assert group_device(FakeDist("cpu:gloo,cuda:nccl")) == torch.device("cuda", 3)
     assert group_device(FakeDist("gloo")) == torch.device("cpu")
+
+
+def _testset_worker8(rank, world, port, q):
+    """one rank of BASELINE configs[2] at its stated width: the 200-sentence test set over eight ranks, with the collectives bench.py runs
+    under the one-device hook (gloo on the host): the early shape exchange, the padded mel gather, ranks_seen, the max-over-ranks time and
+    the frame all-reduce.  Mels and lengths are synthetic, a function of (rank, utterance): every rank can check every other rank's rows."""
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    ok = n_steps(200, world, 60) == 1
+
+    def mk(r):
+        idx = shard_indices(200, r, world, 60)[0]
+        T = 100 + 7 * r                                                 # ragged T_mel per rank
+        mel = torch.stack([torch.full((T, 80), float(i)) + torch.arange(T, dtype=torch.float32)[:, None] for i in idx])
+        lens = torch.tensor([T - (i % 5) for i in idx], dtype=torch.int32)
+        return idx, mel, lens
+
+    idx, mel, lens = mk(rank)
+    ok = ok and idx == list(range(rank, 200, world)) and len(idx) == 25
+    early = exchange_shapes(mel.shape[0], mel.shape[1], dist, comm_device="cpu")   # started right behind "encode", as bench.py does
+    mel_all, lens_all, meta = gather_mels(mel, lens, dist, comm_device="cpu", shapes=early)
+    ok = ok and meta.tolist() == [[25, 100 + 7 * r] for r in range(world)]
+    Tm = 100 + 7 * (world - 1)
+    ok = ok and tuple(mel_all.shape) == (world, 25, Tm, 80) and tuple(lens_all.shape) == (world, 25)
+    for r in range(world):
+        _, wm, wl = mk(r)
+        T = wm.shape[1]
+        ok = ok and torch.equal(mel_all[r, :, :T], wm) and float(mel_all[r, :, T:].abs().sum()) == 0 and torch.equal(lens_all[r], wl)
+    seen = ranks_seen(dist, device_index=0, device_uuid="")
+    ok = ok and sorted(s["rank"] for s in seen) == list(range(world))
+    t = torch.tensor([0.5 + rank], dtype=torch.float64)
+    dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    f = torch.tensor([int(lens.sum())], dtype=torch.int64)
+    dist.all_reduce(f)
+    ok = ok and float(t.item()) == 0.5 + world - 1 and int(f.item()) == sum(int(mk(r)[2].sum()) for r in range(world))
+    dist.barrier()
+    q.put((rank, bool(ok)))
+    dist.destroy_process_group()
+
+
+def test_testset_sharding_and_gather_gloo_world8():
+    """the eight-rank width of BASELINE configs[2] (utterance i -> rank i mod 8: 25 per rank, one chunk) through the same collectives the
+    one-device bench run uses, on the CPU: the GPU suite runs bench.py itself at four ranks
+    (tests/test_gpu_parity.py::test_bench_four_ranks_on_one_device_testset_sharding)"""
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_testset_worker8, args=(r, 8, port, q)) for r in range(8)]
+    for p in procs:
+        p.start()
+    res = [q.get(timeout=300) for _ in procs]
+    for p in procs:
+        p.join(60)
+    assert sorted(res) == [(r, True) for r in range(8)]
