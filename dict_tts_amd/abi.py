@@ -16,11 +16,12 @@ VOC_BF16, VOC_BF16X3, VOC_F16 = 0, 1, 2
 VOC_PRECISIONS = {"f16": VOC_F16, "bf16": VOC_BF16, "bf16x3": VOC_BF16X3}
 PART_ACOUSTIC, PART_VOCODER, PART_FFT = 1, 2, 4
 OUT_PRON_ATTN, OUT_DUR, OUT_MEL2WORD, OUT_DICT_ATTN, OUT_WORD_ENCODER_OUT, OUT_X_MASK, OUT_CONTEXT, OUT_MEL_LENS = range(1, 9)
+SPK_EMBED, SPK_ID = 1, 2   # dtts_text2mel_speakers kinds: fp32 [B,256] (use_spk_embed) / int64 [B] (use_spk_id)
 TIMER_VOC_CONV, TIMER_S2PA = 1, 2
 TIMER_STAGE_ENCODER, TIMER_STAGE_DICT_ENCODER, TIMER_STAGE_FVAE, TIMER_STAGE_HIFIGAN = 3, 4, 5, 6   # the reference's profile_infer names
 
 EXPORTS = ["dtts_default_config", "dtts_config_sizeof", "dtts_create", "dtts_destroy", "dtts_last_error", "dtts_load_weight",
-           "dtts_finalize_weights", "dtts_dict_table_upload", "dtts_text2mel_encode", "dtts_text2mel_encode_ids", "dtts_text2mel_decode", "dtts_text2mel_fetch",
+           "dtts_finalize_weights", "dtts_dict_table_upload", "dtts_text2mel_encode", "dtts_text2mel_encode_ids", "dtts_text2mel_speakers", "dtts_text2mel_decode", "dtts_text2mel_fetch",
            "dtts_load_weights", "dtts_text2mel_plan", "dtts_text2mel_forward", "dtts_text2mel_forward_ids",
            "dtts_length_regulate", "dtts_hifigan_forward", "dtts_hifigan_hop", "dtts_wav_to_int16", "dtts_fft_blocks_forward",
            "dtts_timer_enable", "dtts_timer_read", "dtts_timer_reset", "dtts_set_noise_seed", "dtts_vocoder_range_guard", "dtts_vocoder_clamped", "dtts_vocoder_nonfinite", "dtts_vocoder_fp16_bound",
@@ -78,6 +79,7 @@ def load_library(path=None):
     lib.dtts_text2mel_encode.argtypes = [vp] + [vp] * 8 + [i32] * 5 + [C.POINTER(C.c_int32), vp]
     lib.dtts_text2mel_decode.argtypes = [vp, vp, vp, vp]
     lib.dtts_text2mel_encode_ids.argtypes = [vp, vp, vp, vp, vp] + [i32] * 5 + [C.POINTER(C.c_int32), vp]
+    lib.dtts_text2mel_speakers.argtypes = [vp, i32, vp, i32, vp]
     lib.dtts_dict_table_upload.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.dtts_text2mel_fetch.argtypes = [vp, i32, vp, vp]
     lib.dtts_hifigan_forward.argtypes = [vp, vp, vp, i32, i32, vp, vp]
@@ -186,6 +188,10 @@ class Context:
         self._chk(self.lib.dtts_text2mel_encode_ids(self.h, word_tokens, entry_ids, pron_modified or None, m2w_ptr, T_m2w, B,
                                                     T_w, L_k, P, C.byref(t_mel), stream), "dtts_text2mel_encode_ids")
         return t_mel.value
+
+    def text2mel_speakers(self, kind, spk, B, stream):
+        """project B speaker inputs (device pointer: fp32 [B,256] for SPK_EMBED, int64 [B] for SPK_ID) and arm the next encode"""
+        self._chk(self.lib.dtts_text2mel_speakers(self.h, int(kind), spk, int(B), stream), "dtts_text2mel_speakers")
 
     def text2mel_decode(self, z_p, mel_out, stream):
         self._chk(self.lib.dtts_text2mel_decode(self.h, z_p, mel_out, stream), "dtts_text2mel_decode")

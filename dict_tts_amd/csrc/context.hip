@@ -191,6 +191,16 @@ struct dtts_ctx {
     float *t_keys = nullptr, *t_values = nullptr, *t_key_map = nullptr;
     bool t_projected = false;   // t_keys / t_values hold K = key Wk^T and V = value Wv^T (hidden_size wide) instead of the raw gloss rows
     int64_t *t_pinyin = nullptr, *t_pinyin_map = nullptr;
+    // ---- speaker conditioning (dtts_text2mel_speakers; modules/portaspeech/model.py:159-163, modules/dict_tts/model.py:44-45,94-96)
+    int spk_kind = 0;                        // 0 = no spk_embed_proj loaded, DTTS_SPK_EMBED (Linear 256 -> hidden), DTTS_SPK_ID (Embedding)
+    int spk_n = 0;                           // DTTS_SPK_ID: rows of the table (num_spk)
+    float *spk_w = nullptr, *spk_bias = nullptr;   // Linear: W^T [256][hidden] + bias [hidden]; Embedding: table [num_spk][hidden]
+    Arena a_spk;                             // the projected rows [B][hidden] + the id-check flag words, written by dtts_text2mel_speakers
+    float* spk_rows = nullptr;
+    unsigned long long* spk_flag = nullptr;
+    int spk_armed_B = 0;                     // > 0: the next encode adds spk_rows (and disarms)
+    unsigned spk_gen = 0, enc_spk_gen = 0;   // arming count; the one the last encode consumed
+    bool enc_spk = false;                    // the last encode was conditioned on spk_rows
 };
 
 static std::string g_create_err;
@@ -534,6 +544,43 @@ bool build_wn(dtts_ctx* h, Need& need, WNet& W, const std::string& p, int hidden
     return pack_plain(h, need, W.cond, ENG_F32, p + ".cond_layer", 1, 1, 0);
 }
 
+// spk_embed_proj (modules/portaspeech/model.py:159-163), optional: the form follows from the shapes — weight [hidden][256] + bias [hidden]
+// = nn.Linear(256, hidden) (use_spk_embed), weight [num_spk][hidden] without bias = Embedding(num_spk, hidden) (use_spk_id)
+int build_speaker(dtts_ctx* h) {
+    h->spk_kind = 0;
+    h->spk_n = 0;
+    h->spk_armed_B = 0;
+    const auto iw = h->w.find("model.spk_embed_proj.weight"), ib = h->w.find("model.spk_embed_proj.bias");
+    const bool has_w = iw != h->w.end(), has_b = ib != h->w.end();
+    if (!has_w && !has_b) return DTTS_OK;
+    const int H = h->cfg.hidden_size;
+    if (!has_w) return fail(h, DTTS_E_INVAL, "spk_embed_proj.bias without spk_embed_proj.weight");
+    const HostTensor& w = iw->second;
+    if (has_b) {
+        if (w.shape.size() != 2 || w.shape[0] != H || w.shape[1] != SPK_IN || ib->second.shape.size() != 1 || ib->second.shape[0] != H)
+            return fail(h, DTTS_E_INVAL, "spk_embed_proj with a bias must be nn.Linear(%d, %d): weight [%d, %d] + bias [%d] expected, got weight "
+                        "of %d dims [%lld, %lld]", SPK_IN, H, H, SPK_IN, H, (int)w.shape.size(), w.shape.empty() ? -1LL : (long long)w.shape[0],
+                        w.shape.size() > 1 ? (long long)w.shape[1] : -1LL);
+        std::vector<float> wt((size_t)SPK_IN * H);
+        for (int o = 0; o < H; ++o)
+            for (int k = 0; k < SPK_IN; ++k) wt[(size_t)k * H + o] = w.f[(size_t)o * SPK_IN + k];
+        h->spk_w = upload(h, wt);
+        h->spk_bias = upload(h, ib->second.f);
+        if (!h->spk_w || !h->spk_bias) return fail(h, DTTS_E_NOMEM, "uploading spk_embed_proj");
+        h->spk_kind = DTTS_SPK_EMBED;
+        return DTTS_OK;
+    }
+    if (w.shape.size() != 2 || w.shape[1] != H || w.shape[0] < 1 || w.shape[0] > INT_MAX / H)
+        return fail(h, DTTS_E_INVAL, "spk_embed_proj.weight without a bias must be Embedding(num_spk, %d) = [num_spk, %d], got %d dims [%lld, %lld]",
+                    H, H, (int)w.shape.size(), w.shape.empty() ? -1LL : (long long)w.shape[0], w.shape.size() > 1 ? (long long)w.shape[1] : -1LL);
+    h->spk_w = upload(h, w.f);
+    h->spk_bias = nullptr;
+    if (!h->spk_w) return fail(h, DTTS_E_NOMEM, "uploading spk_embed_proj");
+    h->spk_n = (int)w.shape[0];
+    h->spk_kind = DTTS_SPK_ID;
+    return DTTS_OK;
+}
+
 int build_acoustic(dtts_ctx* h) {
     Need need{h, ""};
     const dtts_config& c = h->cfg;
@@ -677,6 +724,10 @@ int build_acoustic(dtts_ctx* h) {
     const int dec_eng = (c.fvae_enc_dec_hidden % 64 == 0 && !c.decoder_fp32) ? ENG_BF16X3 : ENG_F32;
     ok = ok && build_wn(h, need, h->dec_wn, m + "fvae.decoder.wn", c.fvae_enc_dec_hidden, c.fvae_kernel_size, c.fvae_dec_n_layers, dec_eng);
     ok = ok && pack_plain(h, need, h->dec_out, ENG_F32, m + "fvae.decoder.out_proj", 1, 1, 0);
+    if (ok) {
+        const int rc = build_speaker(h);
+        if (rc) return rc;
+    }
     if (!ok) {
         if (!need.missing.empty()) return fail(h, DTTS_E_NOENT, "missing weight tensor '%s'", need.missing.c_str());
         if (h->err.empty()) return fail(h, DTTS_E_NOMEM, "packing / uploading acoustic weights failed");
@@ -1024,7 +1075,7 @@ void set_res(ConvParams& p, int s, const float* res, int ld) {
     } while (0)
 
 int run_encoder(dtts_ctx* h, const Encoder& E, float* x, float* hbuf, float* qkv, float* att, float* ff, float* out,
-                const int* lens, int B, int T, hipStream_t s) {
+                const int* lens, int B, int T, hipStream_t s, const float* spk = nullptr) {
     const int C = h->cfg.hidden_size, F = 4 * C;
     for (size_t i = 0; i < E.l.size(); ++i) {
         const EncLayer& l = E.l[i];
@@ -1047,7 +1098,7 @@ int run_encoder(dtts_ctx* h, const Encoder& E, float* x, float* hbuf, float* qkv
         set_res(p, 0, x, C);
         LAUNCH(conv1d_launch(l.ffn2, p, s));
     }
-    LAUNCH(layernorm_launch(x, out, E.lg, E.lb, 1e-4f, lens, 0, 1, B, T, C, s));
+    LAUNCH(layernorm_launch(x, out, E.lg, E.lb, 1e-4f, lens, 0, 1, B, T, C, s, spk));   // spk: (LN + spk[b]) * nonpadding
     return DTTS_OK;
 }
 
@@ -1605,7 +1656,7 @@ int dtts_create(const dtts_config* cfg, dtts_handle* out) {
     (void)hipGetDevice(&h->device);
     if (hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || h->n_cu <= 0) h->n_cu = 256;
     h->debug_rz = cfg->debug_redzone != 0;
-    h->a_fft.debug = h->a_enc.debug = h->a_dec.debug = h->a_voc.debug = h->debug_rz;
+    h->a_fft.debug = h->a_enc.debug = h->a_dec.debug = h->a_voc.debug = h->a_spk.debug = h->debug_rz;
     *out = h;
     return DTTS_OK;
 }
@@ -1624,6 +1675,7 @@ void dtts_destroy(dtts_handle h) {
     h->a_enc.release();
     h->a_dec.release();
     h->a_voc.release();
+    h->a_spk.release();
     for (auto& t : h->timers)
         for (auto e : t.pool) (void)hipEventDestroy(e);
     delete h;
@@ -1928,12 +1980,20 @@ static int encode_impl(dtts_handle h, const int64_t* word_tokens, const float* k
                        const int64_t* pron_modified, const int64_t* mel2word, int T_m2w, int B, int T_w, int L_k, int P,
                        int32_t* T_mel_host, dtts_stream stream) {
     if (!h) return DTTS_E_INVAL;
+    // an armed speaker batch belongs to THIS encode whatever its outcome: a later batch never reuses it
+    const int spk_B = h->spk_armed_B;
+    h->spk_armed_B = 0;
+    h->enc_spk = false;
     if (!h->acoustic_ready) return fail(h, DTTS_E_STATE, "acoustic weights not finalized");
     const bool tensors_ok = keys && values && key_map && pinyin && pinyin_map;
     if (!word_tokens || (!entry_ids && !tensors_ok) || !T_mel_host || B <= 0 || T_w <= 0 || L_k <= 0 || P <= 0 || L_k > 1024 ||
         P > 64)
         return fail(h, DTTS_E_INVAL, "dtts_text2mel_encode: bad argument (B=%d T_w=%d L_k=%d P=%d)", B, T_w, L_k, P);
     if (entry_ids && !h->t_entries) return fail(h, DTTS_E_STATE, "dtts_text2mel_encode_ids before dtts_dict_table_upload");
+    if (spk_B && spk_B != B)
+        return fail(h, DTTS_E_INVAL, "dtts_text2mel_speakers armed %d utterances but this encode has B=%d (the speakers are dropped; arm again)",
+                    spk_B, B);
+    const float* spk = spk_B ? h->spk_rows : nullptr;
     hipStream_t s = (hipStream_t)stream;
     const dtts_config& c = h->cfg;
     const int C = c.hidden_size, D = c.gloss_dim, F = 4 * C;
@@ -2041,7 +2101,7 @@ static int encode_impl(dtts_handle h, const int64_t* word_tokens, const float* k
         LAUNCH(add_launch(h->context, pron, x, (long long)rows * C, s));
     }
     // A4: linguistic encoder; * (word_tokens > 0) is the same prefix mask
-    rc = run_encoder(h, h->lin, x, hb, qkv, att, ff, h->weo, h->lens, B, T_w, s);
+    rc = run_encoder(h, h->lin, x, hb, qkv, att, ff, h->weo, h->lens, B, T_w, s, spk);   // + spk_embed, * nonpadding (model.py:94-96)
     if (rc) return rc;
     t_dict.stop();
     // A5: duration predictor
@@ -2065,11 +2125,16 @@ static int encode_impl(dtts_handle h, const int64_t* word_tokens, const float* k
         LAUNCH(durations_launch(h->dur, ilens, starts, h->mel_lens, B, T_w, s));
         std::vector<int> tot(B);
         int pm_host = 0;
+        unsigned long long spk_bad[2] = {0ull, 0ull};
         HIPCHK(hipMemcpyAsync(tot.data(), h->mel_lens, sizeof(int) * B, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(&pm_host, pm_max, sizeof(int), hipMemcpyDeviceToHost, s));
+        if (spk) HIPCHK(hipMemcpyAsync(spk_bad, h->spk_flag, sizeof spk_bad, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));  // the one host sync of the path: T_mel sizes every later buffer
         if (pm_host > DTTS_MAX_SENSES)   // the S2PA kernel keeps DTTS_MAX_SENSES sense slots; larger indices would silently get weight 0
             return fail(h, DTTS_E_INVAL, "pinyin_map holds sense index %d; at most %d senses per word are supported", pm_host, DTTS_MAX_SENSES);
+        if (spk_bad[0])   // nn.Embedding raises on such an id; the gather wrote a zero row instead of reading out of range
+            return fail(h, DTTS_E_INVAL, "speaker id %lld of utterance %llu is out of range: spk_embed_proj has %d rows (num_spk)",
+                        (long long)spk_bad[1], spk_bad[0] - 1, h->spk_n);
         for (int b = 0; b < B; ++b) T_raw = std::max(T_raw, tot[b]);
     } else {
         if (T_m2w <= 0) return fail(h, DTTS_E_INVAL, "mel2word given with T_m2w=%d", T_m2w);
@@ -2091,6 +2156,33 @@ static int encode_impl(dtts_handle h, const int64_t* word_tokens, const float* k
     h->T_mel = T_mel;
     *T_mel_host = T_mel;
     h->encoded = true;
+    h->enc_spk = spk != nullptr;
+    h->enc_spk_gen = h->spk_gen;
+    return DTTS_OK;
+}
+
+int dtts_text2mel_speakers(dtts_handle h, int kind, const void* spk, int B, dtts_stream stream) {
+    if (!h) return DTTS_E_INVAL;
+    h->spk_armed_B = 0;
+    if (!h->acoustic_ready) return fail(h, DTTS_E_STATE, "dtts_text2mel_speakers: acoustic weights not finalized");
+    if (!h->spk_kind)
+        return fail(h, DTTS_E_INVAL, "dtts_text2mel_speakers: no speaker weights loaded (spk_embed_proj.* exists only in checkpoints trained with "
+                    "use_spk_embed / use_spk_id and num_spk > 1)");
+    if (kind != h->spk_kind)
+        return fail(h, DTTS_E_INVAL, "dtts_text2mel_speakers: kind %d does not match the loaded spk_embed_proj (%s: kind %d)", kind,
+                    h->spk_kind == DTTS_SPK_EMBED ? "nn.Linear(256, hidden), use_spk_embed" : "Embedding(num_spk, hidden), use_spk_id", h->spk_kind);
+    if (!spk || B <= 0 || B > DTTS_MAX_SPEAKER_BATCH)
+        return fail(h, DTTS_E_INVAL, "dtts_text2mel_speakers: bad argument (B=%d, at most %d)", B, DTTS_MAX_SPEAKER_BATCH);
+    hipStream_t s = (hipStream_t)stream;
+    const int C = h->cfg.hidden_size;
+    HIPCHK(h->a_spk.reserve((size_t)DTTS_MAX_SPEAKER_BATCH * C * sizeof(float) + (64 << 10), s));   // fixed capacity: allocated once
+    h->spk_rows = h->a_spk.alloc<float>((size_t)B * C);
+    h->spk_flag = h->a_spk.alloc<unsigned long long>(2);
+    if (!h->spk_rows || !h->spk_flag) return fail(h, DTTS_E_NOMEM, "speaker workspace");
+    h->spk_gen += 1;
+    if (kind == DTTS_SPK_EMBED) LAUNCH(spk_linear_launch(h->spk_w, h->spk_bias, (const float*)spk, h->spk_rows, B, C, h->spk_flag, s));
+    else LAUNCH(spk_gather_launch(h->spk_w, h->spk_n, (const int64_t*)spk, h->spk_rows, B, C, h->spk_flag, s));
+    h->spk_armed_B = B;
     return DTTS_OK;
 }
 
@@ -2422,7 +2514,17 @@ int dtts_text2mel_fetch(dtts_handle h, int what, void* dst, dtts_stream stream) 
             // transposed view weights.permute(0, 1, 3, 2) = [B, 1, L_k, T_w] (dict_encoder.py:66): produced here, when somebody asks for it
             LAUNCH(transpose_cf_to_cl_launch(h->dict_attn, (float*)dst, h->B, h->T_w, h->L_k, s));
             return DTTS_OK;
-        case DTTS_OUT_WORD_ENCODER_OUT: src = h->weo; bytes = rows * h->cfg.hidden_size * 4; break;
+        case DTTS_OUT_WORD_ENCODER_OUT:
+            if (h->enc_spk) {   // padded rows hold the speaker row (model.py:94,102), added here, off the hot path
+                if (h->enc_spk_gen != h->spk_gen)
+                    return fail(h, DTTS_E_STATE, "dtts_text2mel_fetch(DTTS_OUT_WORD_ENCODER_OUT): the speakers were re-armed since the encode; "
+                                "fetch before arming the next batch");
+                LAUNCH(weo_spk_fetch_launch(h->weo, h->spk_rows, h->lens, (float*)dst, h->B, h->T_w, h->cfg.hidden_size, s));
+                return DTTS_OK;
+            }
+            src = h->weo;
+            bytes = rows * h->cfg.hidden_size * 4;
+            break;
         case DTTS_OUT_X_MASK: src = h->x_mask; bytes = mrows * 4; break;
         case DTTS_OUT_CONTEXT: src = h->context; bytes = rows * h->cfg.hidden_size * 4; break;
         case DTTS_OUT_MEL_LENS: src = h->mel_lens; bytes = (size_t)h->B * 4; break;
@@ -2556,7 +2658,7 @@ int dtts_debug_poke(dtts_handle h, dtts_stream stream) {
     if (!h) return DTTS_E_INVAL;
     if (!h->debug_rz) return fail(h, DTTS_E_STATE, "dtts_debug_poke: the context was not created with dtts_config.debug_redzone = 1");
     char* target = nullptr;
-    for (Arena* a : {&h->a_voc, &h->a_enc, &h->a_dec, &h->a_fft})
+    for (Arena* a : {&h->a_voc, &h->a_enc, &h->a_dec, &h->a_fft, &h->a_spk})
         if (!target && a->base && !a->bufs.empty()) target = a->base + a->bufs[0].start + a->bufs[0].bytes;
     if (!target && !h->rz_static.empty()) target = h->rz_static[0].p + h->rz_static[0].bytes;
     if (!target) return fail(h, DTTS_E_STATE, "dtts_debug_poke: nothing allocated yet");
@@ -2577,7 +2679,7 @@ int dtts_debug_check(dtts_handle h, int64_t* damaged_bytes, dtts_stream stream) 
         zones.push_back({(const unsigned char*)p0, (unsigned)n, (unsigned)names.size()});
         names.push_back(name);
     };
-    const std::pair<const char*, Arena*> arenas[] = {{"encode workspace", &h->a_enc}, {"decode workspace", &h->a_dec}, {"vocoder workspace", &h->a_voc}, {"fft workspace", &h->a_fft}};
+    const std::pair<const char*, Arena*> arenas[] = {{"encode workspace", &h->a_enc}, {"decode workspace", &h->a_dec}, {"vocoder workspace", &h->a_voc}, {"fft workspace", &h->a_fft}, {"speaker workspace", &h->a_spk}};
     for (const auto& a : arenas) {
         const auto& bufs = a.second->bufs;
         const char* base = a.second->base;

@@ -13,9 +13,22 @@ hipError_t embed_launch(const int64_t* tok, const float* table, float scale, flo
 
 // y = LayerNorm_C(x) with biased variance over the channel dim.  Options: mask_in -> rows >= lens[b] of x are
 // first zeroed IN PLACE (Encoder.forward's x = x * x_mask, rel_transformer_encoder.py:58); mask_out -> rows
-// >= lens[b] of y are zero (dur predictor / last_ln * x_mask).
+// >= lens[b] of y are zero (dur predictor / last_ln * x_mask).  spk [B][C] (needs mask_out): y = (LN(x) + spk[b]) * nonpadding,
+// the speaker add of modules/dict_tts/model.py:94-96; null = the plain kernel.
 hipError_t layernorm_launch(float* x, float* y, const float* gamma, const float* beta, float eps, const int* lens,
-                            int mask_in, int mask_out, int B, int T, int C, hipStream_t s);
+                            int mask_in, int mask_out, int B, int T, int C, hipStream_t s, const float* spk = nullptr);
+
+// Speaker projection (modules/portaspeech/model.py:159-163, modules/dict_tts/model.py:44-45) into out [B][C]:
+//   linear: out[b] = W e[b] + bias, wt = W^T [SPK_IN][C], e [B][SPK_IN] (use_spk_embed; fixed-order fp32 FMA sum over SPK_IN);
+//   gather: out[b] = table[ids[b]], table [n_spk][C] (use_spk_id); out-of-range ids give a zero row.
+// flag[0..1] (written by both): 0 / 0, or first offending utterance + 1 / its id.
+constexpr int SPK_IN = 256;
+hipError_t spk_linear_launch(const float* wt, const float* bias, const float* e, float* out, int B, int C, unsigned long long* flag,
+                             hipStream_t s);
+hipError_t spk_gather_launch(const float* table, int n_spk, const int64_t* ids, float* out, int B, int C, unsigned long long* flag,
+                             hipStream_t s);
+// dst[b,t] = t < lens[b] ? weo[b,t] : spk[b]   (ret['word_encoder_out'] of a conditioned forward, model.py:94,102)
+hipError_t weo_spk_fetch_launch(const float* weo, const float* spk, const int* lens, float* dst, int B, int T, int C, hipStream_t s);
 
 // Multi-head self-attention on a fused qkv buffer [B][T][3C] (q | k | v), window_size=None
 // (rel_transformer_encoder.py:132-158): scores/sqrt(dk), masked_fill(mask==0, -1e4), softmax, PV.

@@ -3,6 +3,7 @@
 #include "tune_env.h"
 
 #include <algorithm>
+#include <climits>
 #include <cstdlib>
 
 namespace dtts {
@@ -49,8 +50,11 @@ hipError_t embed_launch(const int64_t* tok, const float* table, float scale, flo
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// SPK: the speaker epilogue of the linguistic encoder's last_ln (dtts_text2mel_speakers) — y = (LN(x) + spk[b]) * nonpadding.  The
+// instantiation without it is the one every other LayerNorm (and every unconditioned encode) runs.
+template <bool SPK>
 __global__ void layernorm_kernel(float* x, float* y, const float* gamma, const float* beta, float eps, const int* lens,
-                                 int mask_in, int mask_out, int T, int C, int rows) {
+                                 int mask_in, int mask_out, int T, int C, int rows, const float* spk) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
     const int b = row / T, t = row % T;
@@ -79,12 +83,86 @@ __global__ void layernorm_kernel(float* x, float* y, const float* gamma, const f
     }
     const float var = wave_sum(sq) / (float)C;
     const float inv = 1.0f / sqrtf(var + eps);
-    for (int c = lane; c < C; c += 64) yr[c] = (xr[c] - mean) * inv * gamma[c] + beta[c];
+    if (SPK) {   // word_encoder_out + spk_embed (modules/dict_tts/model.py:94), padded rows zeroed above (* nonpadding, :96)
+        const float* sr = spk + (long long)b * C;
+        for (int c = lane; c < C; c += 64) {
+            const float v = (xr[c] - mean) * inv * gamma[c] + beta[c];
+            yr[c] = v + sr[c];
+        }
+    } else {
+        for (int c = lane; c < C; c += 64) yr[c] = (xr[c] - mean) * inv * gamma[c] + beta[c];
+    }
 }
 hipError_t layernorm_launch(float* x, float* y, const float* gamma, const float* beta, float eps, const int* lens,
-                            int mask_in, int mask_out, int B, int T, int C, hipStream_t s) {
-    hipLaunchKernelGGL(layernorm_kernel, dim3((B * T + 3) / 4), dim3(256), 0, s, x, y, gamma, beta, eps, lens, mask_in,
-                       mask_out, T, C, B * T);
+                            int mask_in, int mask_out, int B, int T, int C, hipStream_t s, const float* spk) {
+    if (spk) {
+        if (!mask_out || !lens) return hipErrorInvalidValue;   // the speaker epilogue is defined with the nonpadding mask only
+        hipLaunchKernelGGL(layernorm_kernel<true>, dim3((B * T + 3) / 4), dim3(256), 0, s, x, y, gamma, beta, eps, lens, mask_in,
+                           mask_out, T, C, B * T, spk);
+    } else {
+        hipLaunchKernelGGL(layernorm_kernel<false>, dim3((B * T + 3) / 4), dim3(256), 0, s, x, y, gamma, beta, eps, lens, mask_in,
+                           mask_out, T, C, B * T, (const float*)nullptr);
+    }
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Speaker conditioning (dtts_text2mel_speakers).  Linear form: one workgroup per utterance, e[b] staged in LDS, one output channel per
+// thread summed over k = 0..SPK_IN-1 in that fixed order with fp32 FMAs, bias added last (60 x 256 x 192 MACs per batch: no MFMA).
+__global__ __launch_bounds__(256) void spk_linear_kernel(const float* wt, const float* bias, const float* e, float* out, int C,
+                                                         unsigned long long* flag) {
+    __shared__ float es[SPK_IN];
+    const int b = blockIdx.x;
+    for (int k = threadIdx.x; k < SPK_IN; k += blockDim.x) es[k] = e[(long long)b * SPK_IN + k];
+    __syncthreads();
+    for (int o = threadIdx.x; o < C; o += blockDim.x) {
+        float acc = 0.f;
+        for (int k = 0; k < SPK_IN; ++k) acc = fmaf(wt[(long long)k * C + o], es[k], acc);   // wt = W^T [SPK_IN][C]: coalesced over o
+        out[(long long)b * C + o] = acc + bias[o];
+    }
+    if (b == 0 && threadIdx.x == 0) flag[0] = flag[1] = 0ull;
+}
+// Embedding form: row gather.  Every id is bounds-checked; an out-of-range id gets a zero row (never an out-of-range read) and workgroup 0
+// records the FIRST offending utterance: flag[0] = b + 1, flag[1] = the id (0 / 0 = all ids valid).
+__global__ __launch_bounds__(256) void spk_gather_kernel(const float* table, int n_spk, const int64_t* ids, float* out, int B, int C,
+                                                         unsigned long long* flag) {
+    const int b = blockIdx.x;
+    const long long id = ids[b];
+    const bool ok = id >= 0 && id < n_spk;
+    for (int o = threadIdx.x; o < C; o += blockDim.x) out[(long long)b * C + o] = ok ? table[id * C + o] : 0.f;
+    if (b != 0) return;
+    __shared__ int first;
+    if (threadIdx.x == 0) first = INT_MAX;
+    __syncthreads();
+    for (int u = threadIdx.x; u < B; u += blockDim.x)
+        if (ids[u] < 0 || ids[u] >= n_spk) atomicMin(&first, u);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        flag[0] = first == INT_MAX ? 0ull : (unsigned long long)first + 1ull;
+        flag[1] = first == INT_MAX ? 0ull : (unsigned long long)ids[first];
+    }
+}
+hipError_t spk_linear_launch(const float* wt, const float* bias, const float* e, float* out, int B, int C, unsigned long long* flag,
+                             hipStream_t s) {
+    hipLaunchKernelGGL(spk_linear_kernel, dim3(B), dim3(256), 0, s, wt, bias, e, out, C, flag);
+    return hipGetLastError();
+}
+hipError_t spk_gather_launch(const float* table, int n_spk, const int64_t* ids, float* out, int B, int C, unsigned long long* flag,
+                             hipStream_t s) {
+    hipLaunchKernelGGL(spk_gather_kernel, dim3(B), dim3(256), 0, s, table, n_spk, ids, out, B, C, flag);
+    return hipGetLastError();
+}
+// DTTS_OUT_WORD_ENCODER_OUT of a conditioned encode: the reference returns word_encoder_out + spk_embed BEFORE the nonpadding mask
+// (model.py:94,102), so its padded rows hold the speaker row; the workspace keeps the masked sum the duration predictor consumed
+__global__ void weo_spk_fetch_kernel(const float* weo, const float* spk, const int* lens, float* dst, int T, int C, int rows) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const int b = row / T;
+    const bool keep = (row % T) < lens[b];
+    for (int c = lane; c < C; c += 64) dst[(long long)row * C + c] = keep ? weo[(long long)row * C + c] : spk[(long long)b * C + c];
+}
+hipError_t weo_spk_fetch_launch(const float* weo, const float* spk, const int* lens, float* dst, int B, int T, int C, hipStream_t s) {
+    hipLaunchKernelGGL(weo_spk_fetch_kernel, dim3((B * T + 3) / 4), dim3(256), 0, s, weo, spk, lens, dst, T, C, B * T);
     return hipGetLastError();
 }
 

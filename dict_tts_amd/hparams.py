@@ -101,13 +101,27 @@ HIFIGAN_DEFAULTS = {
 }
 
 
+def speaker_kind(hp):
+    """None (single speaker), "id" (use_spk_id: Embedding(num_spk, hidden)) or "embed" (use_spk_embed: Linear(256, hidden)).
+    The reference builds spk_embed_proj only when num_spk > 1 (modules/portaspeech/model.py:159-163) and then crashes in forward
+    (modules/dict_tts/model.py:45) when use_spk_* is set with num_spk = 1, the value egs/egs_bases/tts/base.yaml:58 ships: refused here."""
+    hp = {**BIAOBEI_DEFAULTS, **(hp or {})}
+    if not (hp.get("use_spk_embed") or hp.get("use_spk_id")):
+        return None
+    num_spk = int(hp.get("num_spk", 1) or 1)
+    if num_spk <= 1:
+        which = "use_spk_id" if hp.get("use_spk_id") else "use_spk_embed"
+        raise ValueError(f"{which}=True needs num_spk > 1, but num_spk={num_spk}: the reference builds no spk_embed_proj then and fails in "
+                         f"forward.  Override it with the checkpoint's speaker count, e.g. --hparams num_spk=N")
+    return "id" if hp.get("use_spk_id") else "embed"   # use_spk_id wins (modules/portaspeech/model.py:160-163, tasks/tts/dict_tts.py:182)
+
+
 def fill_abi_config(cfg, hp=None, voc=None, n_phone=None, vocoder_precision=None):
     """copy reference hparams into a DttsConfig (abi.DttsConfig); unsupported settings fail loudly"""
     hp = {**BIAOBEI_DEFAULTS, **(hp or {})}
     if hp.get("use_post_glow"):
         raise NotImplementedError("use_post_glow=True is outside the Dict-TTS path (egs/egs_bases/tts/dict_tts.yaml:4)")
-    if hp.get("use_spk_embed") or hp.get("use_spk_id"):
-        raise NotImplementedError("speaker embeddings are not part of the Biaobei Dict-TTS path (num_spk=1)")
+    speaker_kind(hp)   # use_spk_embed / use_spk_id need num_spk > 1; nothing of it goes into the config struct (the weights carry the form)
     if not hp.get("use_prior_glow", True) or hp.get("dur_scale", "log") != "log":
         raise NotImplementedError("only use_prior_glow=True / dur_scale=log are implemented")
     for k in ("hidden_size", "num_heads", "enc_ffn_kernel_size", "word_size", "value_embedding_size",

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 from scipy.io import wavfile
 
+from . import hparams as hparams_mod
 from .model import decode_pinyin_ids
 
 META_COLUMNS = ["item_name", "text", "pinyin_tokens", "wav_fn_pred", "wav_fn_gt"]
@@ -48,9 +49,13 @@ def infer_batch(model, vocoder, batch, z_p=None):
 
 
 def _model_forward(model, batch, z_p):
+    kw = {}
+    if "spk_embed" in batch or "spk_ids" in batch:   # multi-speaker batches: tasks/tts/dict_tts.py:182
+        hp = getattr(model, "hparams", None) or hparams_mod.hparams
+        kw["spk_embed"] = batch.get("spk_ids") if hp.get("use_spk_id") else batch.get("spk_embed")
     return model((batch["word_tokens"], batch.get("txt_tokens")), batch.get("pron_modified"), (None, None, None),
                  batch.get("ph2word"), None,
-                 (batch["keys"], batch["values"], batch["key_map"], batch["pinyin"], batch["pinyin_map"]), infer=True, z_p=z_p)
+                 (batch["keys"], batch["values"], batch["key_map"], batch["pinyin"], batch["pinyin_map"]), infer=True, z_p=z_p, **kw)
 
 
 def _iter_results(model, vocoder, batches, pipeline, out_wav_norm=False):

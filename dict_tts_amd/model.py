@@ -3,7 +3,13 @@
 reference's key names, every tensor op executed by libdicttts_hip.so.
 
 What the reference ignores at inference is accepted and ignored here too: ``ph_tokens`` (txt_tokens[1]),
-``key_value_map``, ``ph2word``, ``word_len``, ``mel2ph``, ``tgt_mels``, ``spk_embed`` (num_spk = 1).
+``key_value_map``, ``ph2word``, ``word_len``, ``mel2ph``, ``tgt_mels``.
+
+Speakers (modules/dict_tts/model.py:44-45,94-96): with ``use_spk_embed`` (``spk_embed`` = fp32 [B, 256] utterance embeddings) or
+``use_spk_id`` (``spk_embed`` = int64 [B] speaker ids; use_spk_id wins if both are set) and ``num_spk > 1``, ``load_state_dict``
+uploads ``spk_embed_proj.*`` and every forward projects the batch's speakers on the GPU and adds them to the word encoder output
+(dtts_text2mel_speakers).  Without those hparams ``spk_embed`` is ignored and ``spk_embed_proj.*`` is accepted and not uploaded,
+as before; with them, a forward without ``spk_embed`` raises (the reference crashes there).
 One extra keyword, ``z_p`` ([B, latent, T_mel/4]): the prior sample, which the reference draws from the CPU
 global RNG (modules/dict_tts/fvae_semantics.py:110-111); when omitted it is drawn the same way here.
 """
@@ -18,6 +24,7 @@ from .hparams import fill_abi_config
 # (SURVEY.md §8a "Parameter inventory"): accepted by load_state_dict, not uploaded
 UNUSED_PREFIXES = ("fvae.encoder.", "attn.", "enc_pos_proj.", "dec_query_proj.", "dec_res_proj.",
                    "dict_encoder.S2PA_module.emb.", "spk_embed_proj.", "post_flow.", "sin_pos.")
+SPEAKER_PREFIX = "spk_embed_proj."   # used (uploaded) when the hparams ask for speakers, unused otherwise
 
 
 def load_checkpoint_state(work_dir, child="model"):
@@ -47,6 +54,7 @@ class PortaSpeech_dict(torch.nn.Module):
             hparams = hparams_mod.hparams
         hp = dict(hparams)
         self.hparams = hp
+        self.spk_kind = hparams_mod.speaker_kind(hp)   # None | "embed" | "id"; raises for use_spk_* with num_spk <= 1
         n_phone = len(dictionary) if dictionary is not None else None
         if ctx is None:
             ctx = abi.Context(fill_abi_config(abi.default_config(), hp, None, n_phone=n_phone))
@@ -65,7 +73,14 @@ class PortaSpeech_dict(torch.nn.Module):
             unexpected.append(k)
         if strict and unexpected:
             raise RuntimeError(f"Unexpected key(s) in state_dict: {unexpected[:5]}")
-        used = {k: v for k, v in state_dict.items() if not k.startswith(UNUSED_PREFIXES)}
+        unused = UNUSED_PREFIXES if self.spk_kind is None else tuple(p for p in UNUSED_PREFIXES if p != SPEAKER_PREFIX)
+        used = {k: v for k, v in state_dict.items() if not k.startswith(unused)}
+        if self.spk_kind is not None:
+            want = ["spk_embed_proj.weight"] + (["spk_embed_proj.bias"] if self.spk_kind == "embed" else [])
+            missing = [k for k in want if k not in state_dict]
+            if missing and strict:
+                raise RuntimeError(f"Error(s) in loading state_dict for PortaSpeech_dict: missing key(s) {missing} "
+                                   f"(use_spk_{'id' if self.spk_kind == 'id' else 'embed'}=True, num_spk={self.hparams.get('num_spk')})")
         self._state = dict(state_dict)
         self.ctx.load_state_dict("model", used)
         try:
@@ -99,6 +114,7 @@ class PortaSpeech_dict(torch.nn.Module):
         assert key_map.shape == (B, T_w, L_k) and pinyin.shape == pinyin_map.shape == (B, T_w, P)
         stream = torch.cuda.current_stream().cuda_stream
         ptr = lambda t: None if t is None else t.data_ptr()
+        spk = self._arm_speakers(spk_embed, B, stream)   # noqa: F841  (kept alive until the projection has read it)
         return self._finish(self.ctx.text2mel_encode(ptr(word_tokens), ptr(keys), ptr(values), ptr(key_map), ptr(pinyin),
                                          ptr(pinyin_map), ptr(pron_modified),
                                          (ptr(mel2word), mel2word.shape[1]) if mel2word is not None else None, B, T_w,
@@ -109,7 +125,28 @@ class PortaSpeech_dict(torch.nn.Module):
         self.ctx.dict_table_upload(table["tok_off"], table["keys"], table.get("values"), table["key_map"], table["pin_off"],
                                    table["pinyin"], table["pinyin_map"])
 
-    def forward_ids(self, word_tokens, entry_ids, pron_modified, L_k, P, mel2word=None, z_p=None):
+    def _arm_speakers(self, spk_embed, B, stream):
+        """project the batch's speakers and arm the next encode (modules/dict_tts/model.py:44-45; tasks/tts/dict_tts.py:182 passes
+        sample['spk_ids'] with use_spk_id, sample['spk_embed'] otherwise); returns the device tensor the projection reads"""
+        if self.spk_kind is None:
+            return None
+        if spk_embed is None:
+            raise abi.DttsError(f"use_spk_{self.spk_kind}=True: forward needs spk_embed (" +
+                             ("int64 speaker ids [B]" if self.spk_kind == "id" else "fp32 speaker embeddings [B, 256]") +
+                             "); the reference crashes in spk_embed_proj(None) here")
+        if self.spk_kind == "id":
+            t = torch.as_tensor(spk_embed).to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
+            if t.shape[0] != B:
+                raise ValueError(f"spk_ids has {t.shape[0]} entries for a batch of {B}")
+            self.ctx.text2mel_speakers(abi.SPK_ID, t.data_ptr(), B, stream)
+        else:
+            t = torch.as_tensor(spk_embed).to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(t.shape) != (B, 256):
+                raise ValueError(f"spk_embed must be [B, 256] = [{B}, 256], got {tuple(t.shape)}")
+            self.ctx.text2mel_speakers(abi.SPK_EMBED, t.data_ptr(), B, stream)
+        return t
+
+    def forward_ids(self, word_tokens, entry_ids, pron_modified, L_k, P, mel2word=None, z_p=None, spk_embed=None):
         """forward(infer=True) with the dictionary tensors replaced by ids into the resident table"""
         dev = self.device
         word_tokens = word_tokens.to(device=dev, dtype=torch.int64).contiguous()
@@ -119,6 +156,7 @@ class PortaSpeech_dict(torch.nn.Module):
         B, T_w = word_tokens.shape
         stream = torch.cuda.current_stream().cuda_stream
         ptr = lambda t: None if t is None else t.data_ptr()
+        spk = self._arm_speakers(spk_embed, B, stream)   # noqa: F841
         T_mel = self.ctx.text2mel_encode_ids(ptr(word_tokens), ptr(entry_ids), ptr(pron_modified),
                                              (ptr(mel2word), mel2word.shape[1]) if mel2word is not None else None, B, T_w,
                                              int(L_k), int(P), stream)

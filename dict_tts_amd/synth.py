@@ -82,8 +82,37 @@ def _wn(sd, seed, p, hidden, k, layers, gin):
     _conv(sd, seed, f"{p}.cond_layer", 2 * hidden * layers, gin, 1, gain=0.7, wn=True)
 
 
-def dict_tts_state_dict(seed=1234, n_phone=6, word_size=WORD_SIZE):
-    """numpy state dict with the key names / shapes of ``state_dict['model']``."""
+SPK_EMBED_DIM = 256   # utterance speaker embeddings of use_spk_embed (modules/portaspeech/model.py:163)
+
+
+def speaker_state_dict(seed=1234, speaker="embed", num_spk=4):
+    """seeded spk_embed_proj weights (modules/portaspeech/model.py:159-163): "embed" = nn.Linear(256, hidden) (weight + bias),
+    "id" = Embedding(num_spk, hidden) (weight only).  Rows of about the size of the word encoder output's, so that speakers move
+    the durations."""
+    sd = {}
+    if speaker == "embed":
+        _linear(sd, seed, "spk_embed_proj", HIDDEN, SPK_EMBED_DIM, gain=0.5, bias=0.1)
+    elif speaker == "id":
+        sd["spk_embed_proj.weight"] = randn(seed, "spk_embed_proj.table", (num_spk, HIDDEN), 0.5)
+    else:
+        raise ValueError(f"speaker must be 'embed' or 'id', got {speaker!r}")
+    return sd
+
+
+def speaker_inputs(seed, speaker, B, num_spk=4, name="spk"):
+    """seeded per-utterance speaker inputs: "embed" -> fp32 [B, 256] unit-norm embeddings (one per utterance, as the binarizer's
+    resemblyzer vectors are), "id" -> int64 [B] speaker ids in [0, num_spk)"""
+    if speaker == "embed":
+        e = randn(seed, name + ".embed", (B, SPK_EMBED_DIM))
+        return (e / np.linalg.norm(e, axis=1, keepdims=True)).astype(np.float32)
+    if speaker == "id":
+        return _rng(seed, name + ".ids").integers(0, num_spk, size=B).astype(np.int64)
+    raise ValueError(f"speaker must be 'embed' or 'id', got {speaker!r}")
+
+
+def dict_tts_state_dict(seed=1234, n_phone=6, word_size=WORD_SIZE, speaker=None, num_spk=4):
+    """numpy state dict with the key names / shapes of ``state_dict['model']``.  speaker = "embed" / "id" (opt-in)
+    adds the spk_embed_proj of a multi-speaker checkpoint (speaker_state_dict); every other tensor is the same as without it."""
     sd = {}
     h = HIDDEN
     # PortaSpeech leftovers: loaded, never used by PortaSpeech_dict (modules/portaspeech/model.py:153-158)
@@ -127,6 +156,8 @@ def dict_tts_state_dict(seed=1234, n_phone=6, word_size=WORD_SIZE):
     sd[a + ".pinyin_embedding.weight"] = randn(seed, a + ".pinyin", (N_PINYIN, h), 1.0)
     sd[a + ".pinyin_embedding.weight"][0] = 0
     _rel_encoder(sd, seed, p + ".linguistic_encoder")
+    if speaker is not None:
+        sd.update(speaker_state_dict(seed, speaker, num_spk))
     return sd
 
 

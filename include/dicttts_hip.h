@@ -192,6 +192,29 @@ DTTS_API int dtts_text2mel_encode_ids(dtts_handle h, const int64_t* word_tokens_
                              int P, int32_t* T_mel_host, dtts_stream stream);
 
 /*
+ * Speaker conditioning — replaces spk_embed_proj and the add of modules/dict_tts/model.py:44-45,94-96 (multi-speaker checkpoints such as
+ * the WenetSpeech configuration: use_spk_embed / use_spk_id with num_spk > 1).  The projection is an optional part of the acoustic weights:
+ * "model.spk_embed_proj.weight" [hidden][256] + "model.spk_embed_proj.bias" [hidden] = nn.Linear(256, hidden) (use_spk_embed), or
+ * "model.spk_embed_proj.weight" [num_spk][hidden] alone = Embedding(num_spk, hidden) (use_spk_id); dtts_finalize_weights(DTTS_PART_ACOUSTIC)
+ * packs it when present and rejects any other shape (DTTS_E_INVAL).
+ *
+ * dtts_text2mel_speakers enqueues the projection of B speaker inputs (device: fp32 [B][256] for DTTS_SPK_EMBED, int64 [B] ids for
+ * DTTS_SPK_ID) on `stream` at once and ARMS the next dtts_text2mel_encode / _encode_ids / _forward / _forward_ids on this handle, which
+ * must be enqueued on the same stream with the same B: that encode computes word_encoder_out + spk_embed and feeds
+ * (word_encoder_out + spk_embed) * nonpadding to the duration predictor and the decoder condition, as the reference does.  Every encode
+ * consumes (disarms) the speakers, whether it succeeds or not; a later batch is never conditioned on them.  DTTS_E_INVAL: no speaker
+ * weights, `kind` not the loaded form, B > DTTS_MAX_SPEAKER_BATCH, or (at the encode) a B that differs from the armed one.  Speaker ids
+ * are bounds-checked on the device and reported at the T_mel synchronisation of the encode (DTTS_E_INVAL naming the utterance and the
+ * id; the reference's nn.Embedding raises there); with teacher-forced mel2word (no synchronisation) they are not checked and an
+ * out-of-range id gets a zero row.  DTTS_OUT_WORD_ENCODER_OUT of a conditioned encode is the reference's ret['word_encoder_out'] (padded
+ * rows hold the speaker row); fetch it before arming the next batch (DTTS_E_STATE otherwise).
+ */
+#define DTTS_SPK_EMBED 1   /* fp32 [B][256] (use_spk_embed) */
+#define DTTS_SPK_ID 2      /* int64 [B]      (use_spk_id)    */
+#define DTTS_MAX_SPEAKER_BATCH 4096
+DTTS_API int dtts_text2mel_speakers(dtts_handle h, int kind, const void* spk_dev, int B, dtts_stream stream);
+
+/*
  * Acoustic model, phase 2 — replaces the gather-expand and run_decoder (model.py:105-121,
  * fvae_semantics.py:109-115): z_p [B,latent,T_mel/4] f32 is the prior sample (the reference draws it from the
  * CPU RNG; here it is an explicit input for parity runs) or NULL: N(0,1) drawn on the device (counter-based, a new stream
