@@ -16,6 +16,7 @@ VOC_BF16, VOC_BF16X3, VOC_F16 = 0, 1, 2
 VOC_PRECISIONS = {"f16": VOC_F16, "bf16": VOC_BF16, "bf16x3": VOC_BF16X3}
 PART_ACOUSTIC, PART_VOCODER, PART_FFT = 1, 2, 4
 OUT_PRON_ATTN, OUT_DUR, OUT_MEL2WORD, OUT_DICT_ATTN, OUT_WORD_ENCODER_OUT, OUT_X_MASK, OUT_CONTEXT, OUT_MEL_LENS = range(1, 9)
+OUT_POSTERIOR = 9   # not a copy: the posterior pass, dst = a PosteriorArgs block (include/dicttts_hip.h)
 SPK_EMBED, SPK_ID = 1, 2   # dtts_text2mel_speakers kinds: fp32 [B,256] (use_spk_embed) / int64 [B] (use_spk_id)
 TIMER_VOC_CONV, TIMER_S2PA = 1, 2
 TIMER_STAGE_ENCODER, TIMER_STAGE_DICT_ENCODER, TIMER_STAGE_FVAE, TIMER_STAGE_HIFIGAN = 3, 4, 5, 6   # the reference's profile_infer names
@@ -26,6 +27,13 @@ EXPORTS = ["dtts_default_config", "dtts_config_sizeof", "dtts_create", "dtts_des
            "dtts_length_regulate", "dtts_hifigan_forward", "dtts_hifigan_hop", "dtts_wav_to_int16", "dtts_fft_blocks_forward",
            "dtts_timer_enable", "dtts_timer_read", "dtts_timer_reset", "dtts_set_noise_seed", "dtts_vocoder_range_guard", "dtts_vocoder_clamped", "dtts_vocoder_nonfinite", "dtts_vocoder_fp16_bound",
            "dtts_debug_check", "dtts_debug_poke"]
+
+
+class PosteriorArgs(C.Structure):
+    """dtts_posterior_args (include/dicttts_hip.h): the argument block of dtts_text2mel_fetch(DTTS_OUT_POSTERIOR)"""
+    _fields_ = [("size", C.c_int32), ("mel_ld", C.c_int32), ("eps_ld", C.c_int32), ("mel_cap", C.c_int32),
+                ("tgt_mels_dev", C.c_void_p), ("eps_dev", C.c_void_p), ("mel_out_dev", C.c_void_p), ("m_q_dev", C.c_void_p),
+                ("logs_q_dev", C.c_void_p), ("z_p_dev", C.c_void_p), ("kl_dev", C.c_void_p)]
 
 
 class DttsConfig(C.Structure):
@@ -195,6 +203,12 @@ class Context:
 
     def text2mel_decode(self, z_p, mel_out, stream):
         self._chk(self.lib.dtts_text2mel_decode(self.h, z_p, mel_out, stream), "dtts_text2mel_decode")
+
+    def text2mel_posterior(self, tgt_mels, mel_ld, eps, eps_ld, mel_out, mel_cap, m_q, logs_q, z_p, kl, stream):
+        """the teacher-forced FVAE posterior pass after an encode: dtts_text2mel_fetch(DTTS_OUT_POSTERIOR) with its host argument block
+        (device pointers; eps / m_q / logs_q / z_p / kl may be None)"""
+        a = PosteriorArgs(C.sizeof(PosteriorArgs), int(mel_ld), int(eps_ld), int(mel_cap), tgt_mels, eps, mel_out, m_q, logs_q, z_p, kl)
+        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_POSTERIOR, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_POSTERIOR)")
 
     def fetch(self, what, dst, stream):
         self._chk(self.lib.dtts_text2mel_fetch(self.h, what, dst, stream), "dtts_text2mel_fetch")

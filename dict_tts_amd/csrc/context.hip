@@ -201,6 +201,17 @@ struct dtts_ctx {
     int spk_armed_B = 0;                     // > 0: the next encode adds spk_rows (and disarms)
     unsigned spk_gen = 0, enc_spk_gen = 0;   // arming count; the one the last encode consumed
     bool enc_spk = false;                    // the last encode was conditioned on spk_rows
+    // ---- FVAE posterior pass (dtts_text2mel_fetch(DTTS_OUT_POSTERIOR); modules/dict_tts/fvae_semantics.py:84-108), packed when the checkpoint carries
+    // fvae.encoder.*; otherwise post_missing names the first absent tensor and the call is refused
+    bool post_ready = false;
+    std::string post_missing;
+    PackedConv post_pre;                     // encoder.pre_net.0: Conv1d(n_mel -> hidden, k = 8, s = 4, p = 2)
+    WNet post_wn;                            // encoder.wn (fvae_enc_n_layers layers, conditioned on g_sqz)
+    float *post_wt = nullptr, *post_bias = nullptr;   // encoder.out_proj as W^T [hidden][2 latent] + bias [2 latent]
+    std::vector<Flow> flows_fwd;             // the prior flow's couplings in EXECUTION order of the forward direction (+m, not -m)
+    float* fs_w_fwd = nullptr;               // the same blocks packed for the fused kernel's masked forward form (flowstack.hip: MASK), or null
+    PackedConv fs_cond_fwd;                  //   with their cond_layers as one 1x1 convolution in forward execution order
+    Arena a_post;
 };
 
 static std::string g_create_err;
@@ -531,7 +542,8 @@ bool build_encoder(dtts_ctx* h, Need& need, Encoder& E, const std::string& p) {
 }
 
 // eng: ENG_F32 (exact fp32 MFMA, generic kernel) or ENG_BF16X3 (split operands: the vconv kernel's WaveNet form)
-bool build_wn(dtts_ctx* h, Need& need, WNet& W, const std::string& p, int hidden, int k, int layers, int eng = ENG_F32) {
+// cond_eng: the conditioning layer's engine (ENG_BF16X3: computed by the caller on the vconv kernel, as the posterior encoder does)
+bool build_wn(dtts_ctx* h, Need& need, WNet& W, const std::string& p, int hidden, int k, int layers, int eng = ENG_F32, int cond_eng = ENG_F32) {
     W.hidden = hidden;
     W.layers = layers;
     W.in.resize(layers);
@@ -541,7 +553,7 @@ bool build_wn(dtts_ctx* h, Need& need, WNet& W, const std::string& p, int hidden
             return false;
         if (!pack_plain(h, need, W.rs[i], eng, p + ".res_skip_layers." + std::to_string(i), 1, 1, 0)) return false;
     }
-    return pack_plain(h, need, W.cond, ENG_F32, p + ".cond_layer", 1, 1, 0);
+    return pack_plain(h, need, W.cond, cond_eng, p + ".cond_layer", 1, 1, 0);
 }
 
 // spk_embed_proj (modules/portaspeech/model.py:159-163), optional: the form follows from the shapes — weight [hidden][256] + bias [hidden]
@@ -578,6 +590,111 @@ int build_speaker(dtts_ctx* h) {
     if (!h->spk_w) return fail(h, DTTS_E_NOMEM, "uploading spk_embed_proj");
     h->spk_n = (int)w.shape[0];
     h->spk_kind = DTTS_SPK_ID;
+    return DTTS_OK;
+}
+
+// The FVAE posterior encoder + the prior flow's forward-direction packs.  A checkpoint without fvae.encoder.* loads as before; the
+// posterior call then reports the missing tensor.  The forward flow shares pre / WN packs with the reverse one (same flip parity per block:
+// block f sees f flips going forward and n - f going back, n even) and gets its own post pack with the reference's signs.
+int build_posterior(dtts_ctx* h) {
+    h->post_ready = false;
+    h->post_missing.clear();
+    h->flows_fwd.clear();
+    const dtts_config& c = h->cfg;
+    const std::string p = "model.fvae.encoder";
+    if (!h->w.count(p + ".pre_net.0.weight") && !h->w.count(p + ".pre_net.0.weight_v")) {
+        h->post_missing = p + ".pre_net.0.weight";
+        return DTTS_OK;
+    }
+    Need need{h, ""};
+    const int Hd = c.fvae_enc_dec_hidden, Z = c.latent_size, half = Z / 2, Hf = c.prior_glow_hidden;
+    bool ok = pack_plain(h, need, h->post_pre, ENG_F32, p + ".pre_net.0", 1, 4, 2);
+    // the encoder WaveNet (8 layers at T_mel / 4) on the decoder's engine: split-bf16 operands unless the width does not tile or fp32 was asked for
+    const int eng = (Hd % 64 == 0 && !c.decoder_fp32) ? ENG_BF16X3 : ENG_F32;
+    // (its 192 -> 3,072 conditioning on the vconv kernel too when the width allows: 1.2 MFLOP per T/4 row, like fs_cond)
+    const int cond_eng = (eng == ENG_BF16X3 && (2 * Hd * c.fvae_enc_n_layers) % 256 == 0 && c.hidden_size == 192) ? ENG_BF16X3 : ENG_F32;
+    ok = ok && build_wn(h, need, h->post_wn, p + ".wn", Hd, c.fvae_kernel_size, c.fvae_enc_n_layers, eng, cond_eng);
+    const HostTensor* wo = ok ? folded_weight(h, need, p + ".out_proj") : nullptr;
+    std::vector<float> bo = ok ? bias_of(need, p + ".out_proj") : std::vector<float>();
+    if (ok && wo && !bo.empty()) {
+        if (wo->numel() != (int64_t)2 * Z * Hd || (int)bo.size() != 2 * Z)
+            return fail(h, DTTS_E_INVAL, "fvae.encoder.out_proj must be Conv1d(%d, %d, 1)", Hd, 2 * Z);
+        std::vector<float> wt((size_t)Hd * 2 * Z);
+        for (int o = 0; o < 2 * Z; ++o)
+            for (int k = 0; k < Hd; ++k) wt[(size_t)k * 2 * Z + o] = wo->f[(size_t)o * Hd + k];
+        h->post_wt = upload(h, wt);
+        h->post_bias = upload(h, bo);
+        if (!h->post_wt || !h->post_bias) return fail(h, DTTS_E_NOMEM, "uploading fvae.encoder.out_proj");
+    } else
+        ok = false;
+    const int n = (int)h->flows.size();
+    std::vector<float> fs_host, fs_cond_w, fs_cond_b;
+    const bool fuse = h->fs_w != nullptr;   // the reverse flow is fused: the forward one is too (same shapes, same DTTS_TUNE bit 8)
+    for (int f = 0; ok && f < n; ++f) {
+        Flow fl = h->flows[n - 1 - f];   // h->flows is in reverse execution order: the same block, the same pre / WN packs and channel offsets
+        const bool rev = f & 1;
+        const std::string q = "model.fvae.prior_flow.flows." + std::to_string(2 * f);
+        const HostTensor* wpost = need.get(q + ".post.weight");
+        std::vector<float> bpost = bias_of(need, q + ".post");
+        if (!wpost || bpost.empty()) { ok = false; break; }
+        const float* pp = wpost->f.data();
+        std::vector<float> b(half);
+        for (int o = 0; o < half; ++o) b[o] = bpost[rev ? half - 1 - o : o];
+        fl.post = PackedConv();
+        // x1 = post(h) + x1, masked (glow_modules.py:112,120): the epilogue's residual add, then the row mask
+        ok = pack_conv(h, fl.post, ENG_F32, half, Hf, 1, [=](int co, int ci, int) { return pp[(size_t)(rev ? half - 1 - co : co) * Hf + ci]; }, b, 1, 1, 0);
+        h->flows_fwd.push_back(fl);
+        if (ok && fuse) {   // logical weights with the flip folded in, as build_acoustic packs the reverse blocks; post with the reference's sign
+            const HostTensor* wpre = need.get(q + ".pre.weight");
+            std::vector<float> bpre = bias_of(need, q + ".pre");
+            if (!wpre || bpre.empty()) { ok = false; break; }
+            FlowStackHostWeights fw;
+            fw.pre.resize((size_t)Hf * half);
+            for (int co = 0; co < Hf; ++co)
+                for (int ci = 0; ci < half; ++ci) fw.pre[(size_t)co * half + ci] = wpre->f[(size_t)co * half + (rev ? half - 1 - ci : ci)];
+            fw.bpre = bpre;
+            fw.post.resize((size_t)half * Hf);
+            for (int o = 0; o < half; ++o)
+                for (int ci = 0; ci < Hf; ++ci) fw.post[(size_t)o * Hf + ci] = pp[(size_t)(rev ? half - 1 - o : o) * Hf + ci];
+            fw.bpost = b;
+            for (int l = 0; ok && l < c.prior_glow_n_layers; ++l) {
+                const std::string bi = q + ".enc.in_layers." + std::to_string(l), br = q + ".enc.res_skip_layers." + std::to_string(l);
+                const HostTensor *wi = folded_weight(h, need, bi), *wr = folded_weight(h, need, br);
+                std::vector<float> b1 = bias_of(need, bi), b2 = bias_of(need, br);
+                if (!wi || !wr || b1.empty() || b2.empty()) { ok = false; break; }
+                fw.in.push_back(wi->f);
+                fw.bin.push_back(b1);
+                fw.rs.push_back(wr->f);
+                fw.brs.push_back(b2);
+            }
+            const HostTensor* wc = ok ? folded_weight(h, need, q + ".enc.cond_layer") : nullptr;
+            std::vector<float> bc = ok ? bias_of(need, q + ".enc.cond_layer") : std::vector<float>();
+            if (!wc || bc.empty()) { ok = false; break; }
+            flowstack_pack(fw, c.prior_glow_n_layers, !c.decoder_fp32, fs_host);
+            fs_cond_w.insert(fs_cond_w.end(), wc->f.begin(), wc->f.end());
+            fs_cond_b.insert(fs_cond_b.end(), bc.begin(), bc.end());
+        }
+    }
+    h->fs_w_fwd = nullptr;
+    if (ok && fuse && n > 0) {   // (the shapes were checked when the reverse blocks were packed)
+        h->fs_w_fwd = upload(h, fs_host);
+        const int n_c = (int)fs_cond_b.size(), Cg = c.hidden_size;
+        const float* pc = fs_cond_w.data();
+        ok = h->fs_w_fwd && pack_conv(h, h->fs_cond_fwd, h->fs_cond.engine, n_c, Cg, 1, [=](int co, int ci, int) { return pc[(size_t)co * Cg + ci]; },
+                                      fs_cond_b, 1, 1, 0);
+    }
+    if (!ok) {
+        if (!need.missing.empty()) {
+            h->post_missing = need.missing;
+            h->flows_fwd.clear();
+            return DTTS_OK;
+        }
+        if (h->err.empty()) return fail(h, DTTS_E_NOMEM, "packing / uploading the FVAE posterior encoder failed");
+        return DTTS_E_INVAL;
+    }
+    if (Z != 16 || Hd > 512 || c.frames_multiple % 4)
+        return fail(h, DTTS_E_INVAL, "the posterior pass supports latent_size 16, fvae_enc_dec_hidden <= 512 and frames_multiple % 4 == 0");
+    h->post_ready = true;
     return DTTS_OK;
 }
 
@@ -726,6 +843,10 @@ int build_acoustic(dtts_ctx* h) {
     ok = ok && pack_plain(h, need, h->dec_out, ENG_F32, m + "fvae.decoder.out_proj", 1, 1, 0);
     if (ok) {
         const int rc = build_speaker(h);
+        if (rc) return rc;
+    }
+    if (ok) {
+        const int rc = build_posterior(h);
         if (rc) return rc;
     }
     if (!ok) {
@@ -1102,10 +1223,12 @@ int run_encoder(dtts_ctx* h, const Encoder& E, float* x, float* hbuf, float* qkv
     return DTTS_OK;
 }
 
-// WN.forward with x_mask = 1 (modules/commons/wavenet.py:54-78): x is updated in place, `out` receives the skip sum
+// WN.forward (modules/commons/wavenet.py:54-78): x is updated in place, `out` receives the skip sum
 // g == null: `cond` already holds the conditioning (the caller computed it)
+// mask == null: x_mask = 1 (inference).  Otherwise [B][T]: x = (x + res) * mask in every non-last layer and out = skip_sum * mask, both in the
+// res / skip epilogue (x must arrive masked)
 int run_wn(dtts_ctx* h, const WNet& W, float* x, const float* g, int g_ld, float* cond, float* acts, float* out, int B,
-           int T, hipStream_t s, const int64_t* cond_m2w = nullptr, int cond_Tw = 0) {
+           int T, hipStream_t s, const int64_t* cond_m2w = nullptr, int cond_Tw = 0, const float* mask = nullptr) {
     const int H = W.hidden;
     ConvParams p;
     if (g) {
@@ -1132,6 +1255,7 @@ int run_wn(dtts_ctx* h, const WNet& W, float* x, const float* g, int g_ld, float
                 VConvParams v = vparams_x3(W.rs[i], acts, H, 1.f, nullptr, B, T);
                 v.bias = nullptr;
                 v.gbias = W.rs[i].bias;
+                v.row_mask = mask;   // the first segment: the res half, or the last layer's skip sum
                 if (i < W.layers - 1) {
                     v.split = H;
                     v.yf = x;
@@ -1163,6 +1287,7 @@ int run_wn(dtts_ctx* h, const WNet& W, float* x, const float* g, int g_ld, float
         p.cond_coff = i * 2 * H;
         LAUNCH(conv1d_launch(W.in[i], p, s));
         p = base_params(acts, H, B, T, T, x, H);
+        p.row_mask = mask;   // seg[0]: the res half, or the last layer's skip sum
         if (i < W.layers - 1) {
             p.split = H;
             set_res(p, 0, x, H);
@@ -1656,7 +1781,7 @@ int dtts_create(const dtts_config* cfg, dtts_handle* out) {
     (void)hipGetDevice(&h->device);
     if (hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || h->n_cu <= 0) h->n_cu = 256;
     h->debug_rz = cfg->debug_redzone != 0;
-    h->a_fft.debug = h->a_enc.debug = h->a_dec.debug = h->a_voc.debug = h->a_spk.debug = h->debug_rz;
+    h->a_fft.debug = h->a_enc.debug = h->a_dec.debug = h->a_voc.debug = h->a_spk.debug = h->a_post.debug = h->debug_rz;
     *out = h;
     return DTTS_OK;
 }
@@ -1676,6 +1801,7 @@ void dtts_destroy(dtts_handle h) {
     h->a_dec.release();
     h->a_voc.release();
     h->a_spk.release();
+    h->a_post.release();
     for (auto& t : h->timers)
         for (auto e : t.pool) (void)hipEventDestroy(e);
     delete h;
@@ -2456,6 +2582,169 @@ int dtts_text2mel_decode(dtts_handle h, const float* z_p, float* mel_out, dtts_s
     return decode_impl(h, z_p, 0, mel_out, 0, stream);   // z_p == NULL: the prior sample is drawn on the device
 }
 
+// The FVAE posterior pass, teacher-forced (FVAE_semantics.forward(infer=False), modules/dict_tts/fvae_semantics.py:84-108), on the batch the
+// last encode laid out; reached through dtts_text2mel_fetch(DTTS_OUT_POSTERIOR).  Its own workspace (a_post): the infer path's buffers and results are untouched.
+// (dtts_text2mel_fetch(DTTS_OUT_POSTERIOR): the argument block has been checked by the caller)
+static int posterior_impl(dtts_handle h, const float* tgt_mels, int mel_ld, const float* eps, int eps_ld, float* mel_out, int mel_cap,
+                          float* m_q, float* logs_q, float* z_p, float* kl, dtts_stream stream) {
+    if (!h->post_ready)
+        return fail(h, DTTS_E_STATE, "dtts_text2mel_fetch(DTTS_OUT_POSTERIOR): the checkpoint lacks the posterior encoder (missing weight "
+                    "tensor '%s')", h->post_missing.empty() ? "model.fvae.encoder.pre_net.0.weight" : h->post_missing.c_str());
+    if (!tgt_mels || !mel_out) return fail(h, DTTS_E_INVAL, "dtts_text2mel_fetch(DTTS_OUT_POSTERIOR): null tgt_mels / mel_out");
+    hipStream_t s = (hipStream_t)stream;
+    const dtts_config& c = h->cfg;
+    const int B = h->B, T = h->T_mel, T4 = T / 4, C = c.hidden_size, Z = c.latent_size, n_mel = c.audio_num_mel_bins;
+    const int Hd = c.fvae_enc_dec_hidden, Hf = c.prior_glow_hidden, Le = c.fvae_enc_n_layers;
+    if (mel_ld && mel_ld < T) return fail(h, DTTS_E_INVAL, "tgt_mels holds %d frames per utterance, T_mel = %d", mel_ld, T);
+    if (mel_cap && mel_cap < T) return fail(h, DTTS_E_INVAL, "mel_out holds %d frames per utterance, T_mel = %d", mel_cap, T);
+    if (eps && eps_ld && eps_ld < T4) return fail(h, DTTS_E_INVAL, "eps holds %d steps per row, T_mel/4 = %d", eps_ld, T4);
+    const size_t mrows = (size_t)B * T, qrows = (size_t)B * T4;
+    const int CW = 2 * Hd * c.fvae_dec_n_layers;
+    const bool dec_x3 = !h->dec_wn.in.empty() && h->dec_wn.in[0].engine == ENG_BF16X3;
+    HIPCHK(h->a_post.reserve(sizeof(float) * (mrows * (size_t)(C + 3 * Hd + (dec_x3 ? 0 : CW)) + ((size_t)B * h->T_w + 1) * CW +
+                                              qrows * (size_t)(C + 2 + 3 * Hd + 2 * Hd * Le + 3 * Z + 2 * Hf * c.prior_glow_n_layers + 3 * Hf +
+                                                               (h->fs_w_fwd ? h->fs_cond_fwd.C_out : 0))) +
+                             sizeof(double) * 2 * KL_BLOCKS + (64 << 10), s));
+    Arena& A = h->a_post;
+    float* g = A.alloc<float>(mrows * C);
+    float* gs = A.alloc<float>(qrows * C);
+    float* msq = A.alloc<float>(qrows);
+    float* hq = A.alloc<float>(qrows * Hd);
+    float* ecnd = A.alloc<float>(qrows * 2 * Hd * Le);
+    float* eacts = A.alloc<float>(qrows * Hd);
+    float* eout = A.alloc<float>(qrows * Hd);
+    float* epsb = A.alloc<float>(qrows * Z);
+    float* zq = A.alloc<float>(qrows * Z);
+    float* zp = A.alloc<float>(qrows * Z);
+    float* logq = A.alloc<float>(qrows);
+    float* fcond = A.alloc<float>(qrows * 2 * Hf * c.prior_glow_n_layers);
+    float* fh = A.alloc<float>(qrows * Hf);
+    float* facts = A.alloc<float>(qrows * Hf);
+    float* fout = A.alloc<float>(qrows * Hf);
+    float* dx = A.alloc<float>(mrows * Hd);
+    float* dacts = A.alloc<float>(mrows * Hd);
+    float* dout = A.alloc<float>(mrows * Hd);
+    float* cond_w = A.alloc<float>(((size_t)B * h->T_w + 1) * CW);
+    double* partial = A.alloc<double>(2 * KL_BLOCKS);
+    if (!g || !gs || !msq || !hq || !ecnd || !eacts || !eout || !epsb || !zq || !zp || !logq || !fcond || !fh || !facts || !fout || !dx || !dacts ||
+        !dout || !cond_w || !partial)
+        return fail(h, DTTS_E_NOMEM, "posterior workspace");
+    // g = expand(word_encoder_out) (* tgt_nonpadding), x_mask = (mel2word > 0); g_sqz = g_pre_net(g) exactly as the infer path computes them
+    LAUNCH(expand_launch(h->weo, h->m2w, g, h->x_mask, B, h->T_w, T, C, s));
+    if (h->g_pre_poly.w_hi) {
+        VConvParams v = vparams_x3(h->g_pre_poly, g, 4 * C, 1.f, nullptr, B, T4);
+        v.in_half = 1;
+        v.yf = gs;
+        v.ldyf = C;
+        LAUNCH(vconv_launch(v, s));
+    } else {
+        ConvParams p = base_params(g, C, B, T, T4, gs, C);
+        LAUNCH(conv1d_launch(h->g_pre, p, s));
+    }
+    LAUNCH(mask_sqz_launch(h->x_mask, msq, B, T, T4, s));   // x_mask[:, :, ::4] (fvae_semantics.py:31)
+    // posterior encoder (fvae_semantics.py:29-35): pre_net(x) * x_mask_sqz, the masked WN conditioned on g_sqz, out_proj + sample + log q
+    {
+        ConvParams p = base_params(tgt_mels, n_mel, B, T, T4, hq, Hd);
+        p.x_bstride = (long long)(mel_ld ? mel_ld : T) * n_mel;
+        p.row_mask = msq;
+        LAUNCH(conv1d_launch(h->post_pre, p, s));
+    }
+    int rc;
+    if (h->post_wn.cond.engine == ENG_BF16X3) {   // the conditioning of all 8 layers by one split-operand convolution, then the masked layers
+        VConvParams v = vparams_x3(h->post_wn.cond, gs, C, 1.f, nullptr, B, T4);
+        v.yf = ecnd;
+        v.ldyf = 2 * Hd * Le;
+        LAUNCH(vconv_launch(v, s));
+        rc = run_wn(h, h->post_wn, hq, nullptr, C, ecnd, eacts, eout, B, T4, s, nullptr, 0, msq);
+    } else {
+        rc = run_wn(h, h->post_wn, hq, gs, C, ecnd, eacts, eout, B, T4, s, nullptr, 0, msq);
+    }
+    if (rc) return rc;
+    if (eps) {
+        LAUNCH(transpose_cf_to_cl_launch(eps, epsb, B, Z, T4, s, eps_ld));
+    } else {
+        LAUNCH(normal_fill_launch(epsb, (long long)qrows * Z, h->noise_seed + ++h->noise_counter, s));   // torch.randn_like(m) (:34)
+    }
+    LAUNCH(post_proj_sample_launch(eout, h->post_wt, h->post_bias, epsb, zq, logq, m_q, logs_q, B, T4, Hd, Z, s));
+    // prior flow, forward, masked (glow_modules.py:108-123,157-161) on a copy of z_q, then log p and the KL (fvae_semantics.py:95-99)
+    if ((z_p || kl) && h->fs_w_fwd) {   // every block in one kernel, its masked forward form; the conditioning of all blocks by one convolution
+        const int n_c = h->fs_cond_fwd.C_out;
+        float* cond_all = A.alloc<float>(qrows * n_c);
+        if (!cond_all) return fail(h, DTTS_E_NOMEM, "posterior workspace");
+        if (h->fs_cond_fwd.engine == ENG_BF16X3) {
+            VConvParams v = vparams_x3(h->fs_cond_fwd, gs, C, 1.f, nullptr, B, T4);
+            v.yf = cond_all;
+            v.ldyf = n_c;
+            LAUNCH(vconv_launch(v, s));
+        } else {
+            ConvParams p = base_params(gs, C, B, T4, T4, cond_all, n_c);
+            LAUNCH(conv1d_launch(h->fs_cond_fwd, p, s));
+        }
+        FlowStackParams fp;
+        memset(&fp, 0, sizeof fp);
+        fp.z_in = zq;
+        fp.z_out = zp;
+        fp.cond = cond_all;
+        fp.ld_cond = n_c;
+        fp.w = h->fs_w_fwd;
+        fp.B = B;
+        fp.T4 = T4;
+        fp.Z = Z;
+        fp.n_flows = (int)h->flows_fwd.size();
+        fp.layers = c.prior_glow_n_layers;
+        fp.x3 = c.decoder_fp32 ? 0 : 1;
+        for (size_t i = 0; i < h->flows_fwd.size(); ++i) {
+            fp.in_coff[i] = h->flows_fwd[i].in_coff;
+            fp.out_coff[i] = h->flows_fwd[i].out_coff;
+        }
+        fp.mask = msq;
+        LAUNCH(flowstack_launch(fp, s));
+        LAUNCH(kl_launch(zp, logq, msq, z_p, partial, kl, B, T4, Z, s));
+    } else if (z_p || kl) {   // launch by launch (DTTS_TUNE bit 8, or a flow shape the fused kernel does not take)
+        HIPCHK(hipMemcpyAsync(zp, zq, qrows * Z * sizeof(float), hipMemcpyDeviceToDevice, s));
+        for (const Flow& fl : h->flows_fwd) {
+            ConvParams p = base_params(zp, Z, B, T4, T4, fh, Hf);
+            p.x_coff = fl.in_coff;
+            p.row_mask = msq;   // h = pre(x0) * x_mask
+            LAUNCH(conv1d_launch(fl.pre, p, s));
+            rc = run_wn(h, fl.wn, fh, gs, C, fcond, facts, fout, B, T4, s, nullptr, 0, msq);
+            if (rc) return rc;
+            p = base_params(fout, Hf, B, T4, T4, zp, Z);
+            p.seg[0].coff = fl.out_coff;
+            set_res(p, 0, zp, Z);
+            p.seg[0].coff_res = fl.out_coff;
+            p.row_mask = msq;   // x1 = post(h) * mask + x1 * mask
+            LAUNCH(conv1d_launch(fl.post, p, s));
+        }
+        LAUNCH(kl_launch(zp, logq, msq, z_p, partial, kl, B, T4, Z, s));
+    }
+    // decoder with the frame mask (fvae_semantics.py:52-57): pre_net(z_q) * x_mask, the masked WN, out_proj
+    {
+        ConvParams p = base_params(zq, Z, B, T4, T4, dx, 4 * Hd);
+        LAUNCH(conv1d_launch(h->dec_pre, p, s));
+    }
+    LAUNCH(rows_scale_launch(dx, h->x_mask, (long long)mrows, Hd, s));
+    if (hipMemcpyAsync(cond_w, h->dec_wn.cond.bias, (size_t)CW * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return fail(h, DTTS_E_HIP, "decoder conditioning bias row");
+    {
+        ConvParams p = base_params(h->weo, C, B, h->T_w, h->T_w, cond_w + CW, CW);
+        LAUNCH(conv1d_launch(h->dec_wn.cond, p, s));
+    }
+    if (dec_x3) {
+        rc = run_wn(h, h->dec_wn, dx, nullptr, C, cond_w, dacts, dout, B, T, s, h->m2w, h->T_w, h->x_mask);
+    } else {
+        float* dcond = A.alloc<float>(mrows * CW);
+        if (!dcond) return fail(h, DTTS_E_NOMEM, "posterior workspace");
+        LAUNCH(expand_launch(cond_w + CW, h->m2w, dcond, nullptr, B, h->T_w, T, CW, s, h->dec_wn.cond.bias));
+        rc = run_wn(h, h->dec_wn, dx, nullptr, C, dcond, dacts, dout, B, T, s, nullptr, 0, h->x_mask);
+    }
+    if (rc) return rc;
+    ConvParams p = base_params(dout, Hd, B, T, T, mel_out, n_mel);
+    if (mel_cap) p.y_bstride_rows = mel_cap;
+    LAUNCH(conv1d_launch(h->dec_out, p, s));
+    return DTTS_OK;
+}
+
 // ---- the single-call forms and names of SURVEY.md 8(b)
 int dtts_load_weights(dtts_handle h, const char* name, const void* host_ptr, const int64_t* shape, int ndim, int dtype) {
     return dtts_load_weight(h, name, host_ptr, shape, ndim, dtype);
@@ -2501,6 +2790,14 @@ int dtts_text2mel_forward_ids(dtts_handle h, const int64_t* word_tokens, const i
 int dtts_text2mel_fetch(dtts_handle h, int what, void* dst, dtts_stream stream) {
     if (!h || !dst) return DTTS_E_INVAL;
     if (!h->encoded) return fail(h, DTTS_E_STATE, "dtts_text2mel_fetch before encode");
+    if (what == DTTS_OUT_POSTERIOR) {   // the posterior pass; dst is the host argument block
+        const dtts_posterior_args* a = (const dtts_posterior_args*)dst;
+        if (a->size != (int32_t)sizeof(dtts_posterior_args))
+            return fail(h, DTTS_E_INVAL, "dtts_text2mel_fetch(DTTS_OUT_POSTERIOR): argument block of %d bytes, this library's is %d", a->size,
+                        (int)sizeof(dtts_posterior_args));
+        return posterior_impl(h, a->tgt_mels_dev, a->mel_ld, a->eps_dev, a->eps_ld, a->mel_out_dev, a->mel_cap, a->m_q_dev, a->logs_q_dev,
+                              a->z_p_dev, a->kl_dev, stream);
+    }
     hipStream_t s = (hipStream_t)stream;
     const size_t rows = (size_t)h->B * h->T_w, mrows = (size_t)h->B * h->T_mel;
     const void* src = nullptr;
@@ -2658,7 +2955,7 @@ int dtts_debug_poke(dtts_handle h, dtts_stream stream) {
     if (!h) return DTTS_E_INVAL;
     if (!h->debug_rz) return fail(h, DTTS_E_STATE, "dtts_debug_poke: the context was not created with dtts_config.debug_redzone = 1");
     char* target = nullptr;
-    for (Arena* a : {&h->a_voc, &h->a_enc, &h->a_dec, &h->a_fft, &h->a_spk})
+    for (Arena* a : {&h->a_voc, &h->a_enc, &h->a_dec, &h->a_fft, &h->a_spk, &h->a_post})
         if (!target && a->base && !a->bufs.empty()) target = a->base + a->bufs[0].start + a->bufs[0].bytes;
     if (!target && !h->rz_static.empty()) target = h->rz_static[0].p + h->rz_static[0].bytes;
     if (!target) return fail(h, DTTS_E_STATE, "dtts_debug_poke: nothing allocated yet");
@@ -2679,7 +2976,7 @@ int dtts_debug_check(dtts_handle h, int64_t* damaged_bytes, dtts_stream stream) 
         zones.push_back({(const unsigned char*)p0, (unsigned)n, (unsigned)names.size()});
         names.push_back(name);
     };
-    const std::pair<const char*, Arena*> arenas[] = {{"encode workspace", &h->a_enc}, {"decode workspace", &h->a_dec}, {"vocoder workspace", &h->a_voc}, {"fft workspace", &h->a_fft}, {"speaker workspace", &h->a_spk}};
+    const std::pair<const char*, Arena*> arenas[] = {{"encode workspace", &h->a_enc}, {"decode workspace", &h->a_dec}, {"vocoder workspace", &h->a_voc}, {"fft workspace", &h->a_fft}, {"speaker workspace", &h->a_spk}, {"posterior workspace", &h->a_post}};
     for (const auto& a : arenas) {
         const auto& bufs = a.second->bufs;
         const char* base = a.second->base;

@@ -53,6 +53,8 @@ struct ConvParams {
     long long y_bstride_rows; // rows per batch item in every output/residual tensor (T_out)
     int split;           // channels < split go to seg[0], the rest (minus split) to seg[1]
     ConvSeg seg[2];
+    const float* row_mask; // optional [B][T_out] per-row factor applied last to seg[0] only (the FVAE posterior's x_mask: a WaveNet layer's
+                           // (x + res) * mask, the last layer's skip sum * mask, a plain conv * mask); null = no multiply (unchanged arithmetic)
 };
 
 // Host-side description of a packed layer

@@ -232,6 +232,7 @@ __global__ __launch_bounds__(256) void conv1d_cl_kernel(const ConvParams p) {
                     if (p.post_act == 1) v = fmaxf(v, 0.f);
                     else if (p.post_act == 2) v = tanhf(v);
                     else if (p.post_act == 3) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752f));  // F.gelu (erf form)
+                    if (p.row_mask && s == 0) v *= p.row_mask[(long long)b * p.T_out + t];
                 }
                 sg.y[row * sg.ld + sg.coff + cs] = v;
             }
@@ -635,6 +636,14 @@ __global__ __launch_bounds__(256, U > 8 ? 1 : NT > 1 ? (ENGINE == ENG_BF16X6 ? 1
             } else if (p.post_act == 3) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) v[r] = 0.5f * v[r] * (1.f + erff(v[r] * 0.70710678118654752f));  // F.gelu (erf form)
+            }
+            if (p.row_mask && s == 0) {
+                const float* mk = p.row_mask + (long long)b * p.T_out + tb;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int dt = (r & 3) + 8 * (r >> 2);
+                    if (tb + dt < t_end) v[r] *= mk[dt];
+                }
             }
             float* yp = sg.y + row0 * sg.ld + sg.coff + cs;
             const int t_store = p.zero_masked ? p.T_out : t_end;

@@ -1,5 +1,6 @@
 // The FVAE prior flow, reverse direction (modules/dict_tts/fvae_semantics.py:112-113 -> glow_modules.py ResidualCouplingBlock
-// reverse: [Flip, ResidualCouplingLayer(mean_only)] x n_blocks), as ONE kernel: see flowstack.hip.
+// reverse: [Flip, ResidualCouplingLayer(mean_only)] x n_blocks), as ONE kernel: see flowstack.hip.  With FlowStackParams::mask the same
+// kernel runs the posterior pass's forward direction with the frame mask (flowstack.hip: MASK).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -32,6 +33,8 @@ struct FlowStackParams {
     int n_flows, layers;
     int x3;               // 1: weights packed as bf16 hi / lo fragments, contractions on three bf16 MFMAs per product; 0: exact fp32 MFMA
     int in_coff[FS_MAX_FLOWS], out_coff[FS_MAX_FLOWS];   // physical channel offsets of the logical x0 / x1 halves (flip parity)
+    const float* mask;    // null: the reverse flow of inference (x_mask = 1).  [B][T4]: the posterior pass's forward flow with x_mask_sqz
+                          // (blocks in forward execution order, packed with the reference's post signs; flowstack.hip: MASK)
 };
 
 // host packer: getters return the LOGICAL weights of flow block `f` in execution order

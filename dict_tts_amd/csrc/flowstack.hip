@@ -38,7 +38,11 @@ constexpr int ZP = 16;                 // z row (floats)
 // 8 waves: wave (rt, ch) owns row tile rt = rows 32 rt .. 32 rt + 31 and the channel half ch: in_layer co-tiles {ch (tanh), ch + 2 (its
 // sigmoid partner)}, res_skip co-tiles {ch (res), ch + 2 (skip)}, i.e. channels 32 ch .. 32 ch + 31 of h, of the activations and of the
 // skip sum.  Two waves per SIMD: one wave's LDS / L2 / transcendental latencies run under the other's MFMAs.
-template <bool X3>
+// MASK: the FORWARD direction of the posterior pass (glow_modules.py:108-123,157-161 with x_mask = x_mask_sqz): the blocks arrive in forward
+// execution order with the reference's post signs (x1 = post(out) + x1: the pack differs, not this code), and the row mask m (p.mask) is
+// applied where the reference applies it: h = pre(x0) * m, h = (h + res) * m, x1 = (post(skip * m) + x1) * m — for a 0 / 1 mask the same
+// value as post(out) * m + x1 * m.  MASK = false is the reverse kernel of inference, unchanged.
+template <bool X3, bool MASK>
 __global__ __launch_bounds__(512, 1) void flowstack_kernel(const FlowStackParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* zt = (float*)smem_raw;                       // [W][ZP]
@@ -59,6 +63,7 @@ __global__ __launch_bounds__(512, 1) void flowstack_kernel(const FlowStackParams
     const int t = t_base + row_l;
     const bool inb = t >= 0 && t < p.T4;
     const long long grow = (long long)b * p.T4 + t;    // global row (valid when inb)
+    const float mk = MASK ? (inb ? p.mask[grow] : 0.f) : 1.f;   // this lane's row mask (MASK only)
 
     // ---- z tile (zeros outside the sequence), guard rows
     for (int i = tid; i < W * ZP / 4; i += 512) {
@@ -128,7 +133,8 @@ __global__ __launch_bounds__(512, 1) void flowstack_kernel(const FlowStackParams
                     float a = wp[FS_H * FS_HALF + c];
                     a += wa[0] * xa[0]; a += wa[1] * xa[1]; a += wa[2] * xa[2]; a += wa[3] * xa[3];
                     a += wb[0] * xb[0]; a += wb[1] * xb[1]; a += wb[2] * xb[2]; a += wb[3] * xb[3];
-                    hv[e] = inb ? a : 0.f;
+                    if constexpr (MASK) hv[e] = inb ? a * mk : 0.f;
+                    else hv[e] = inb ? a : 0.f;
                 }
                 *(fs4*)(hrow + c0 + 8 * q) = hv;
             }
@@ -298,7 +304,10 @@ __global__ __launch_bounds__(512, 1) void flowstack_kernel(const FlowStackParams
                     float* hp = hrow + c0 + 8 * q;
                     fs4 v = *(const fs4*)hp;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = inb ? v[e] + acc[0][4 * q + e] : 0.f;
+                    for (int e = 0; e < 4; ++e) {
+                        if constexpr (MASK) v[e] = inb ? (v[e] + acc[0][4 * q + e]) * mk : 0.f;
+                        else v[e] = inb ? v[e] + acc[0][4 * q + e] : 0.f;
+                    }
                     *(fs4*)hp = v;
                 }
                 skip += acc[1];
@@ -331,7 +340,10 @@ __global__ __launch_bounds__(512, 1) void flowstack_kernel(const FlowStackParams
             if (ch == 0 && half == 0) {
                 float* zp = zt + row_l * ZP + p.out_coff[f];
 #pragma unroll
-                for (int o = 0; o < FS_HALF; ++o) zp[o] += (m[o] + pm[row_l * FS_HALF + o]) + wq[FS_HALF * FS_H + o];
+                for (int o = 0; o < FS_HALF; ++o) {
+                    if constexpr (MASK) zp[o] = (zp[o] + ((m[o] + pm[row_l * FS_HALF + o]) + wq[FS_HALF * FS_H + o])) * mk;
+                    else zp[o] += (m[o] + pm[row_l * FS_HALF + o]) + wq[FS_HALF * FS_H + o];
+                }
             }
         }
     }
@@ -441,14 +453,21 @@ hipError_t flowstack_launch(const FlowStackParams& p, hipStream_t stream) {
     (void)hipGetDevice(&cur_dev);
     bool& configured = configured_dev[cur_dev & 63];
     if (!configured) {
-        hipError_t e = hipFuncSetAttribute((const void*)flowstack_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)flowstack_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipError_t e = hipFuncSetAttribute((const void*)flowstack_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)flowstack_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)flowstack_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)flowstack_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
         configured = true;
     }
     dim3 grid((p.T4 + RC - 1) / RC, p.B);
-    if (p.x3) hipLaunchKernelGGL(flowstack_kernel<true>, grid, dim3(512), lds, stream, p);
-    else hipLaunchKernelGGL(flowstack_kernel<false>, grid, dim3(512), lds, stream, p);
+    if (p.mask) {
+        if (p.x3) hipLaunchKernelGGL((flowstack_kernel<true, true>), grid, dim3(512), lds, stream, p);
+        else hipLaunchKernelGGL((flowstack_kernel<false, true>), grid, dim3(512), lds, stream, p);
+    } else {
+        if (p.x3) hipLaunchKernelGGL((flowstack_kernel<true, false>), grid, dim3(512), lds, stream, p);
+        else hipLaunchKernelGGL((flowstack_kernel<false, false>), grid, dim3(512), lds, stream, p);
+    }
     return hipGetLastError();
 }
 

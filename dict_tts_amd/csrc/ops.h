@@ -122,4 +122,24 @@ hipError_t transpose_cf_to_cl_launch(const float* x, float* y, int B, int C, int
 // y[i] ~ N(0,1), counter-based on (seed, i)
 hipError_t normal_fill_launch(float* y, long long n, unsigned long long seed, hipStream_t s);
 
+// ---- the FVAE posterior pass (modules/dict_tts/fvae_semantics.py:84-108; dtts_text2mel_fetch(DTTS_OUT_POSTERIOR))
+// msq[b, j] = x_mask[b, 4j]   (x_mask[:, :, ::4][:, :, :T/4], fvae_semantics.py:31)
+hipError_t mask_sqz_launch(const float* x_mask, float* msq, int B, int T, int T4, hipStream_t s);
+// x[r, :] *= mask[r] for r < rows (C % 4 == 0): the decoder's pre_net(z) * x_mask (fvae_semantics.py:53-54)
+hipError_t rows_scale_launch(float* x, const float* mask, long long rows, int C, hipStream_t s);
+// FVAEEncoder's out_proj + sample (fvae_semantics.py:32-35) and log q (:95,98) per row r = b * T4 + j of h [B*T4][H]:
+//   stats = W h + bias (wt = W^T [H][2Z], fixed-order fp32 FMAs); m = stats[:Z], logs = stats[Z:];
+//   zq[r, c] = m + eps[r, c] * exp(logs)   (eps channels-last [B*T4][Z]);
+//   logq[r] = sum_c Normal(m, exp(logs)).log_prob(zq[r, c])   (torch's form: -(z - m)^2 / (2 s^2) - log(s) - log(sqrt(2 pi)));
+//   m_q / logs_q (or null): the caller's channel-first [B][Z][T4].  Z = 16, H <= 512.
+hipError_t post_proj_sample_launch(const float* h, const float* wt, const float* bias, const float* eps, float* zq, float* logq, float* m_q,
+                                   float* logs_q, int B, int T4, int H, int Z, hipStream_t s);
+// KL of the posterior pass (fvae_semantics.py:95-99), deterministic: stage 1 (KL_BLOCKS workgroups, each a fixed contiguous chunk of rows
+// summed in a fixed order, fp64) writes partial[blk] = {sum_r msq[r] * (logq[r] - sum_c logp(zp[r, c])), sum_r msq[r]}; stage 2 (one
+// workgroup) sums the slabs in a fixed order: kl = S / M / Z.  No atomics: the same inputs give the same bits on every run.
+// z_p_out (or null): zp [B*T4][Z] written channel-first [B][Z][T4].  partial: 2 * KL_BLOCKS doubles.
+constexpr int KL_BLOCKS = 64;
+hipError_t kl_launch(const float* zp, const float* logq, const float* msq, float* z_p_out, double* partial, float* kl, int B, int T4, int Z,
+                     hipStream_t s);
+
 } // namespace dtts

@@ -1511,4 +1511,137 @@ hipError_t normal_fill_launch(float* y, long long n, unsigned long long seed, hi
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// FVAE posterior pass (fvae_semantics.py:84-108)
+__global__ void mask_sqz_kernel(const float* x_mask, float* msq, int T, int T4, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int b = i / T4, j = i % T4;
+    msq[i] = x_mask[(long long)b * T + 4 * j];
+}
+hipError_t mask_sqz_launch(const float* x_mask, float* msq, int B, int T, int T4, hipStream_t s) {
+    const int n = B * T4;
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(mask_sqz_kernel, dim3((n + 255) / 256), dim3(256), 0, s, x_mask, msq, T, T4, n);
+    return hipGetLastError();
+}
+
+__global__ void rows_scale_kernel(f32x4* x, const float* mask, long long n4, int C4) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x)
+        x[i] *= mask[i / C4];
+}
+hipError_t rows_scale_launch(float* x, const float* mask, long long rows, int C, hipStream_t s) {
+    if (C % 4) return hipErrorInvalidValue;
+    const long long n4 = rows * (C / 4);
+    if (n4 <= 0) return hipSuccess;
+    const int blocks = (int)std::min<long long>((n4 + 255) / 256, 8192);
+    hipLaunchKernelGGL(rows_scale_kernel, dim3(blocks), dim3(256), 0, s, (f32x4*)x, mask, n4, C / 4);
+    return hipGetLastError();
+}
+
+// 256 threads = 8 rows x 32 outputs; the rows' h staged in LDS, W^T read coalesced (thread o reads column o of row k)
+constexpr int PPS_ROWS = 8, PPS_Z = 16, PPS_HMAX = 512;
+__global__ __launch_bounds__(256) void post_proj_sample_kernel(const float* h, const float* wt, const float* bias, const float* eps, float* zq,
+                                                               float* logq, float* m_q, float* logs_q, int T4, int H, int rows) {
+    __shared__ float hs[PPS_ROWS][PPS_HMAX];
+    __shared__ float st[PPS_ROWS][2 * PPS_Z];
+    __shared__ float lq[PPS_ROWS][PPS_Z];
+    const int rl = threadIdx.x >> 5, o = threadIdx.x & 31;
+    const int r0 = blockIdx.x * PPS_ROWS;
+    for (int i = threadIdx.x; i < PPS_ROWS * H; i += 256) {
+        const int rr = i / H, k = i % H;
+        hs[rr][k] = r0 + rr < rows ? h[(long long)(r0 + rr) * H + k] : 0.f;
+    }
+    __syncthreads();
+    const int r = r0 + rl;
+    float acc = 0.f;
+    for (int k = 0; k < H; ++k) acc = fmaf(wt[k * 2 * PPS_Z + o], hs[rl][k], acc);
+    st[rl][o] = acc + bias[o];
+    __syncthreads();
+    if (r < rows && o < PPS_Z) {
+        const float m = st[rl][o], logs = st[rl][PPS_Z + o];
+        const float sc = expf(logs);
+        const float z = m + eps[(long long)r * PPS_Z + o] * sc;
+        zq[(long long)r * PPS_Z + o] = z;
+        // torch.distributions.Normal(m, exp(logs)).log_prob(z): var = scale ** 2, log_scale = scale.log()
+        const float d = z - m;
+        lq[rl][o] = -(d * d) / (2.f * (sc * sc)) - logf(sc) - 0.91893853320467274178f;   // log(sqrt(2 pi))
+        const int b = r / T4, j = r % T4;
+        const long long cf = ((long long)b * PPS_Z + o) * T4 + j;
+        if (m_q) m_q[cf] = m;
+        if (logs_q) logs_q[cf] = logs;
+    }
+    __syncthreads();
+    if (r < rows && o == 0) {
+        float sum = 0.f;
+        for (int c = 0; c < PPS_Z; ++c) sum += lq[rl][c];
+        logq[r] = sum;
+    }
+}
+hipError_t post_proj_sample_launch(const float* h, const float* wt, const float* bias, const float* eps, float* zq, float* logq, float* m_q,
+                                   float* logs_q, int B, int T4, int H, int Z, hipStream_t s) {
+    if (Z != PPS_Z || H > PPS_HMAX || H <= 0) return hipErrorInvalidValue;
+    const int rows = B * T4;
+    if (rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(post_proj_sample_kernel, dim3((rows + PPS_ROWS - 1) / PPS_ROWS), dim3(256), 0, s, h, wt, bias, eps, zq, logq, m_q, logs_q,
+                       T4, H, rows);
+    return hipGetLastError();
+}
+
+// stage 1: workgroup blk owns rows [blk * chunk, min((blk + 1) * chunk, rows)); thread t sums rows blk * chunk + t + 256 i in order, then a fixed
+// LDS tree.  The chunking depends on the row count only.
+__global__ __launch_bounds__(256) void kl_rows_kernel(const float* zp, const float* logq, const float* msq, float* z_p_out, double* partial, int T4,
+                                                      int Z, int rows, int chunk) {
+    __shared__ double ss[256], sm[256];
+    const int lo = blockIdx.x * chunk, hi = min(rows, lo + chunk);
+    double s = 0.0, m = 0.0;
+    for (int r = lo + (int)threadIdx.x; r < hi; r += 256) {
+        float lp = 0.f;
+        const int b = r / T4, j = r % T4;
+        for (int c = 0; c < Z; ++c) {
+            const float z = zp[(long long)r * Z + c];
+            lp += -(z * z) / 2.f - 0.91893853320467274178f;   // Normal(0, 1).log_prob(z)
+            if (z_p_out) z_p_out[((long long)b * Z + c) * T4 + j] = z;
+        }
+        const float mk = msq[r];
+        s += (double)((logq[r] - lp) * mk);
+        m += (double)mk;
+    }
+    ss[threadIdx.x] = s;
+    sm[threadIdx.x] = m;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            ss[threadIdx.x] += ss[threadIdx.x + w];
+            sm[threadIdx.x] += sm[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        partial[2 * blockIdx.x] = ss[0];
+        partial[2 * blockIdx.x + 1] = sm[0];
+    }
+}
+// stage 2: one workgroup, the KL_BLOCKS slabs in index order
+__global__ __launch_bounds__(64) void kl_final_kernel(const double* partial, float* kl, int Z) {
+    if (threadIdx.x != 0) return;
+    double s = 0.0, m = 0.0;
+    for (int i = 0; i < KL_BLOCKS; ++i) {
+        s += partial[2 * i];
+        m += partial[2 * i + 1];
+    }
+    *kl = (float)(s / m / (double)Z);   // loss_kl = ((logqx - logpx) * x_mask_sqz).sum() / x_mask_sqz.sum() / logqx.shape[1]
+}
+hipError_t kl_launch(const float* zp, const float* logq, const float* msq, float* z_p_out, double* partial, float* kl, int B, int T4, int Z,
+                     hipStream_t s) {
+    const int rows = B * T4;
+    if (rows <= 0 || Z <= 0) return hipErrorInvalidValue;
+    const int chunk = (rows + KL_BLOCKS - 1) / KL_BLOCKS;
+    hipLaunchKernelGGL(kl_rows_kernel, dim3(KL_BLOCKS), dim3(256), 0, s, zp, logq, msq, z_p_out, partial, T4, Z, rows, chunk);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !kl) return e;
+    hipLaunchKernelGGL(kl_final_kernel, dim3(1), dim3(64), 0, s, partial, kl, Z);
+    return hipGetLastError();
+}
+
 } // namespace dtts

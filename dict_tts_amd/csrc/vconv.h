@@ -47,6 +47,9 @@ struct VConvParams {
     int post_tanh;
     unsigned* bad;            // with post_tanh: device counter of non-finite pre-tanh values (the always-on overflow detector), or null
     int dbg;                  // -DDTTS_ABLATE builds only (DTTS_VCONV_DBG): 1 = skip the contraction, 2 = skip the epilogue, 4 = skip staging
+    const float* row_mask;    // optional [B][T] per-row factor (the FVAE posterior's x_mask), applied last to the first segment: the res half of a
+                              // WaveNet res / skip layer ((x + res) * mask), a single-segment layer's output (the last layer's skip sum), a plain
+                              // conv's output; never to the gated acts or the second (skip) segment.  Null: no multiply, the same arithmetic as before
 };
 
 hipError_t vconv_launch(const VConvParams& p, hipStream_t stream);

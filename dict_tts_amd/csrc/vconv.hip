@@ -337,6 +337,7 @@ __global__ __launch_bounds__(256, X3 ? (MT <= 2 ? (NT == 2 ? 3 : (CK == 64 && WC
                         *(f32x4*)(p.yf2 + row * p.ldyf2 + cs) = o;
                     } else {
                         if (p.res) o += *(const f32x4*)(p.res + row * p.ldres + co);
+                        if (p.row_mask) o *= p.row_mask[row];   // WN: x = (x + res) * x_mask; output * x_mask (wavenet.py:73-78)
                         *(f32x4*)(p.yf + row * p.ldyf + co) = o;
                     }
                 }
@@ -396,6 +397,7 @@ __global__ __launch_bounds__(256, X3 ? (MT <= 2 ? (NT == 2 ? 3 : (CK == 64 && WC
 #pragma unroll
                         for (int e = 0; e < 4; ++e) o[e] = tanhf(o[e]);
                     }
+                    if (p.row_mask) o *= p.row_mask[off[u]];
                     if (p.yf) {
 #if VC_NT_STORE
                         __builtin_nontemporal_store(o, (f32x4*)(p.yf + off[u] * p.ldyf + co));
@@ -433,6 +435,7 @@ __global__ __launch_bounds__(256, X3 ? (MT <= 2 ? (NT == 2 ? 3 : (CK == 64 && WC
                         if (nonfin && p.bad) atomicAdd(p.bad, 1u);
                         u = nonfin ? __builtin_nanf("") : tanhf(u);
                     }
+                    if (p.row_mask) u *= p.row_mask[row];
                     if (p.yf) p.yf[row * p.ldyf + co + e] = u;
                     if (p.ya) p.ya[row * p.ldya + co + e] = (unsigned short)vf2bf(u > 0.f ? u : u * p.slope);
                 }

@@ -5,6 +5,11 @@ reference's key names, every tensor op executed by libdicttts_hip.so.
 What the reference ignores at inference is accepted and ignored here too: ``ph_tokens`` (txt_tokens[1]),
 ``key_value_map``, ``ph2word``, ``word_len``, ``mel2ph``, ``tgt_mels``.
 
+``infer=False`` with ``tgt_mels`` and gradients disabled runs the teacher-forced posterior pass the reference's validation_step runs
+(modules/dict_tts/fvae_semantics.py:84-108; dtts_text2mel_fetch(DTTS_OUT_POSTERIOR)): it adds ``kl``, ``z_p``, ``m_q``, ``logs_q`` and returns the
+reconstruction through the posterior latent as ``mel_out``.  One extra keyword, ``eps`` ([B, latent, T_mel/4]): the posterior sample's
+noise (torch.randn_like in the reference); when omitted it is drawn on the device.  Training (gradients) is not implemented.
+
 Speakers (modules/dict_tts/model.py:44-45,94-96): with ``use_spk_embed`` (``spk_embed`` = fp32 [B, 256] utterance embeddings) or
 ``use_spk_id`` (``spk_embed`` = int64 [B] speaker ids; use_spk_id wins if both are set) and ``num_spk > 1``, ``load_state_dict``
 uploads ``spk_embed_proj.*`` and every forward projects the batch's speakers on the GPU and adds them to the word encoder output
@@ -22,7 +27,7 @@ from .hparams import fill_abi_config
 
 # state-dict groups that exist in a Dict-TTS checkpoint but are never used by PortaSpeech_dict at inference
 # (SURVEY.md §8a "Parameter inventory"): accepted by load_state_dict, not uploaded
-UNUSED_PREFIXES = ("fvae.encoder.", "attn.", "enc_pos_proj.", "dec_query_proj.", "dec_res_proj.",
+UNUSED_PREFIXES = ("attn.", "enc_pos_proj.", "dec_query_proj.", "dec_res_proj.",
                    "dict_encoder.S2PA_module.emb.", "spk_embed_proj.", "post_flow.", "sin_pos.")
 SPEAKER_PREFIX = "spk_embed_proj."   # used (uploaded) when the hparams ask for speakers, unused otherwise
 
@@ -95,9 +100,14 @@ class PortaSpeech_dict(torch.nn.Module):
 
     # -- inference -----------------------------------------------------------------------------------------
     def forward(self, txt_tokens, pron_modified, key_value_map, ph2word, word_len, dict_msg, mel2word=None, mel2ph=None,
-                spk_embed=None, infer=False, tgt_mels=None, forward_post_glow=True, two_stage=True, z_p=None):
+                spk_embed=None, infer=False, tgt_mels=None, forward_post_glow=True, two_stage=True, z_p=None, eps=None):
         if not infer:
-            raise NotImplementedError("the MI355X path implements inference only (infer=True)")
+            if tgt_mels is None:
+                raise NotImplementedError("the MI355X path implements inference (infer=True) and the teacher-forced posterior pass "
+                                          "(infer=False with tgt_mels, gradients disabled)")
+            if torch.is_grad_enabled():
+                raise NotImplementedError("infer=False with gradients enabled: gradients (training) are not implemented on the MI355X path; "
+                                          "run validation under torch.no_grad()")
         if not self._ready:
             raise RuntimeError("load_state_dict() must be called first")
         dev = self.device
@@ -114,11 +124,23 @@ class PortaSpeech_dict(torch.nn.Module):
         assert key_map.shape == (B, T_w, L_k) and pinyin.shape == pinyin_map.shape == (B, T_w, P)
         stream = torch.cuda.current_stream().cuda_stream
         ptr = lambda t: None if t is None else t.data_ptr()
+        if not infer:
+            tgt_mels = f32(torch.as_tensor(tgt_mels))
+            if tgt_mels.dim() != 3 or tgt_mels.shape[0] != B or tgt_mels.shape[2] != self.cfg.audio_num_mel_bins:
+                raise ValueError(f"tgt_mels must be [B, T, {self.cfg.audio_num_mel_bins}] with B = {B}, got {tuple(tgt_mels.shape)}")
+            if mel2word is not None:   # the length is known before the encode: refuse before any work is enqueued
+                fm = self.cfg.frames_multiple
+                T_mel = mel2word.shape[1] + (-mel2word.shape[1]) % fm
+                if tgt_mels.shape[1] != T_mel:
+                    raise ValueError(f"tgt_mels has {tgt_mels.shape[1]} frames, mel2word gives T_mel = {T_mel} (its length {mel2word.shape[1]} "
+                                     f"padded to a multiple of frames_multiple = {fm})")
         spk = self._arm_speakers(spk_embed, B, stream)   # noqa: F841  (kept alive until the projection has read it)
-        return self._finish(self.ctx.text2mel_encode(ptr(word_tokens), ptr(keys), ptr(values), ptr(key_map), ptr(pinyin),
-                                         ptr(pinyin_map), ptr(pron_modified),
-                                         (ptr(mel2word), mel2word.shape[1]) if mel2word is not None else None, B, T_w,
-                                         L_k, P, stream), z_p, B, T_w, L_k, P)
+        T_mel = self.ctx.text2mel_encode(ptr(word_tokens), ptr(keys), ptr(values), ptr(key_map), ptr(pinyin), ptr(pinyin_map),
+                                         ptr(pron_modified), (ptr(mel2word), mel2word.shape[1]) if mel2word is not None else None, B, T_w,
+                                         L_k, P, stream)
+        if not infer:
+            return self._posterior(T_mel, tgt_mels, eps, B, T_w, L_k, P)
+        return self._finish(T_mel, z_p, B, T_w, L_k, P)
 
     def upload_dict_table(self, table):
         """make the dictionary resident in HBM (dict_tts_amd/synth.py:dict_table layout = the reference's dict_embed items)"""
@@ -162,6 +184,28 @@ class PortaSpeech_dict(torch.nn.Module):
                                              int(L_k), int(P), stream)
         return self._finish(T_mel, z_p, B, T_w, int(L_k), int(P))
 
+    def _posterior(self, T_mel, tgt_mels, eps, B, T_w, L_k, P):
+        """the teacher-forced FVAE posterior pass (fvae_semantics.py:84-108) after the encode; returns forward(infer=False)'s keys"""
+        dev = self.device
+        stream = torch.cuda.current_stream().cuda_stream
+        if tgt_mels.shape[1] != T_mel:   # predicted durations: T_mel is known after the encode (the reference fails on the shapes here)
+            raise ValueError(f"tgt_mels has {tgt_mels.shape[1]} frames, the durations give T_mel = {T_mel}")
+        Z, T4 = self.cfg.latent_size, T_mel // 4
+        if eps is not None:
+            eps = eps.to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(eps.shape) != (B, Z, T4):
+                raise ValueError(f"eps must be [B, {Z}, T_mel/4] = {(B, Z, T4)}, got {tuple(eps.shape)}")
+        out = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        mel = out(B, T_mel, self.cfg.audio_num_mel_bins)
+        m_q, logs_q, z_p, kl = out(B, Z, T4), out(B, Z, T4), out(B, Z, T4), out(())
+        self.ctx.text2mel_posterior(tgt_mels.data_ptr(), T_mel, None if eps is None else eps.data_ptr(), T4, mel.data_ptr(), T_mel,
+                                    m_q.data_ptr(), logs_q.data_ptr(), z_p.data_ptr(), kl.data_ptr(), stream)
+        ret = self._fetch_encoder(B, T_w, L_k, P, T_mel)
+        ret["mel_out"] = ret["mel_out_fvae"] = mel
+        ret.update(kl=kl, z_p=z_p, m_q=m_q, logs_q=logs_q)
+        ret["rel"] = ret["dp_attn"] = None
+        return ret
+
     def _finish(self, T_mel, z_p, B, T_w, L_k, P):
         dev = self.device
         f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
@@ -171,9 +215,19 @@ class PortaSpeech_dict(torch.nn.Module):
             z_p = torch.distributions.Normal(0, 1).sample([B, Z, T_mel // 4])  # fvae_semantics.py:110
         z_p = f32(z_p)
         assert tuple(z_p.shape) == (B, Z, T_mel // 4), (tuple(z_p.shape), (B, Z, T_mel // 4))
-        n_mel, H = self.cfg.audio_num_mel_bins, self.cfg.hidden_size
+        n_mel = self.cfg.audio_num_mel_bins
         mel = torch.empty(B, T_mel, n_mel, dtype=torch.float32, device=dev)
         self.ctx.text2mel_decode(z_p.data_ptr(), mel.data_ptr(), stream)
+        ret = self._fetch_encoder(B, T_w, L_k, P, T_mel)
+        ret["mel_out"] = ret["mel_out_fvae"] = mel
+        ret["rel"] = ret["dp_attn"] = None
+        ret["z_p_in"] = z_p
+        return ret
+
+    def _fetch_encoder(self, B, T_w, L_k, P, T_mel):
+        dev = self.device
+        stream = torch.cuda.current_stream().cuda_stream
+        H = self.cfg.hidden_size
         ret = {}
         out = lambda shape, dt=torch.float32: torch.empty(*shape, dtype=dt, device=dev)
         ret["pron_attn"] = out((B, T_w, P))
@@ -187,9 +241,6 @@ class PortaSpeech_dict(torch.nn.Module):
                           ("word_encoder_out", abi.OUT_WORD_ENCODER_OUT), ("x_mask", abi.OUT_X_MASK),
                           ("mel2word", abi.OUT_MEL2WORD), ("mel_lens", abi.OUT_MEL_LENS)):
             self.ctx.fetch(what, ret[key].data_ptr(), stream)
-        ret["mel_out"] = ret["mel_out_fvae"] = mel
-        ret["rel"] = ret["dp_attn"] = None
-        ret["z_p_in"] = z_p
         return ret
 
 

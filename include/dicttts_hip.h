@@ -76,7 +76,7 @@ typedef struct dtts_config {
     int32_t fvae_enc_dec_hidden;  /* 192                                                                      */
     int32_t fvae_kernel_size;     /* 5                                                                        */
     int32_t fvae_dec_n_layers;    /* 4                                                                        */
-    int32_t fvae_enc_n_layers;    /* 8 (posterior encoder: loaded, unused at inference)                       */
+    int32_t fvae_enc_n_layers;    /* 8 (posterior encoder: the posterior pass, DTTS_OUT_POSTERIOR)             */
     int32_t prior_glow_hidden;    /* 64                                      ps_flow.yaml:32                   */
     int32_t glow_kernel_size;     /* 3                                                                        */
     int32_t prior_glow_n_blocks;  /* 4                                                                        */
@@ -256,6 +256,33 @@ DTTS_API int dtts_text2mel_forward_ids(dtts_handle h, const int64_t* word_tokens
 #define DTTS_OUT_CONTEXT 7          /* [B,T_w,hidden] f32 S2PA context              */
 #define DTTS_OUT_MEL_LENS 8         /* [B] i32 frames with mel2word > 0 AFTER the padding to frames_multiple (the frames the
                                       reference's B = 1 inference vocodes: an utterance that reaches T_mel keeps its pad frames) */
+/*
+ * DTTS_OUT_POSTERIOR: not a copy but the teacher-forced posterior pass — PortaSpeech_dict.forward(infer=False) without gradients, as the
+ * reference's validation_step runs it (modules/dict_tts/fvae_semantics.py:84-108) — on the batch of the last dtts_text2mel_encode /
+ * _encode_ids, with its inputs and outputs named by a HOST argument block: dst = (dtts_posterior_args*), args->size = sizeof(*args).
+ * It runs instead of dtts_text2mel_decode or in addition to it; the other items stay valid after it (X_MASK is rewritten with the same
+ * values).  No host synchronisation; everything is enqueued on `stream`.  Device pointers, f32:
+ *   tgt_mels [B][mel_ld][80] (mel_ld >= T_mel; 0 = exactly T_mel): the ground-truth mels; x_mask = (mel2word > 0) of the encode;
+ *   eps [B][latent][eps_ld] (eps_ld >= T_mel/4; 0 = exactly T_mel/4), the posterior sample's noise, or NULL: drawn on the device from the
+ *     context's noise stream (dtts_set_noise_seed makes it repeatable);
+ *   mel_out [B][mel_cap][80] (mel_cap >= T_mel; 0 = exactly T_mel): the reconstruction decoder(z_q, x_mask, g); rows >= T_mel untouched;
+ *   m_q, logs_q, z_p [B][latent][T_mel/4] (channel-first, as the reference returns them) and kl (a scalar): each optional (NULL = not
+ *     written).  kl = sum((log q - log p) * x_mask_sqz) / sum(x_mask_sqz) / latent, reduced in a fixed order (same inputs, same bits).
+ * DTTS_E_STATE before an encode, or when the checkpoint lacked fvae.encoder.* (the message names the missing tensor).  The pass has a
+ * workspace of its own, reserved on its first call: the infer path's buffers and results are not touched.
+ */
+#define DTTS_OUT_POSTERIOR 9
+typedef struct dtts_posterior_args {
+    int32_t size;                 /* sizeof(dtts_posterior_args) */
+    int32_t mel_ld, eps_ld, mel_cap;
+    const float* tgt_mels_dev;
+    const float* eps_dev;         /* or NULL */
+    float* mel_out_dev;
+    float* m_q_dev;               /* or NULL */
+    float* logs_q_dev;            /* or NULL */
+    float* z_p_dev;               /* or NULL */
+    float* kl_dev;                /* or NULL */
+} dtts_posterior_args;
 DTTS_API int dtts_text2mel_fetch(dtts_handle h, int what, void* dst_dev, dtts_stream stream);
 
 /*
