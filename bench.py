@@ -11,13 +11,21 @@ runs it (the dictionary is resident in HBM, uploaded once before the timed regio
     -> int16 conversion on the device -> D2H of the int16 waveforms into pinned host memory
 
 The timed loop rotates over 4 DIFFERENT batches of the 200-sentence test set (different lengths, T_w, L_k, T_mel), and the
-H2D / D2H copies are inside the timed region.  Two labelled side figures are measured after it in the same process:
-"inputs_resident" (ids already in HBM, fp32 waveform left in HBM: round 1's definition) and "tensor_api_incl_h2d" (the
-reference's own API: keys / values tensors [B,T_w,L_k,768] uploaded per batch, 1.47 GB at B=60).
+H2D / D2H copies are inside the timed region.
+
+A plain run does only what the headline needs: set-up, the range-guard pass (one forward of every distinct batch; it also
+places the timed steps on their device prior-sample stream; its clamp count is printed as `range_guard`), warm-up, the timed
+steps, --dump-outputs and the result line.
+--full adds everything else, measured after the timed region in the same process: the side figures "inputs_resident" (ids
+already in HBM, fp32 waveform left in HBM: round 1's definition) and "tensor_api_incl_h2d" (the reference's own API: keys /
+values tensors [B,T_w,L_k,768] uploaded per batch, 1.47 GB at B=60), `stages`, `vocoder_modes`, `roofline.isolated` and the
+CPU baseline (--no-side / --no-cpu-baseline leave parts of it out); it also fills `roofline.traffic`, which is not measured
+but read from the committed profiles/r*_pmc_traffic.json and scaled by the run's frame count.
 Data: synthetic (counter-based weights / gloss embeddings, real Biaobei sentence + dictionary structure); durations
 are PREDICTED by the duration predictor (its output bias is set so that the mean is ~22 frames per character).
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0.  --workload rotating (default): weak scaling, every rank rotates over its own 4 batches
@@ -253,12 +261,15 @@ def main():
                     help="what a timed step includes: table = ids H2D + int16 waveform D2H (default); resident = ids already in "
                          "HBM, fp32 waveform stays in HBM; tensors = the reference API, keys/values uploaded per batch")
     ap.add_argument("--no-gather", action="store_true", help="skip the RCCL all-gather of mels when --gpus > 1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure the side figures, per-stage figures and rooflines, the second vocoder mode "
+                         "and the CPU baseline (default: the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline", choices=["protocol", "bounded", "full"], default="protocol",
-                    help="protocol (default): all 60 rows, B=1, up to 5 repetitions inside a time budget, thread sweep; bounded: rows 0..2 (~35 s); "
-                         "full: no budget, B=60 batched variant")
+                    help="with --full: protocol (default): all 60 rows, B=1, up to 5 repetitions inside a time budget, thread sweep; "
+                         "bounded: rows 0..2 (~35 s); full: no budget, B=60 batched variant")
     ap.add_argument("--cpu-budget", type=float, default=420.0, help="seconds the 'protocol' CPU leg may spend on its repetitions")
-    ap.add_argument("--no-side", action="store_true", help="skip the side figures / per-stage / second-mode measurements")
+    ap.add_argument("--no-side", action="store_true", help="with --full: skip the side figures / per-stage / second-mode measurements")
     ap.add_argument("--voc-priority", type=int, default=0, help="HIP stream priority of the vocoder stream (two-stream pipeline): 0 normal, -1 high")
     ap.add_argument("--voc-tune", type=int, default=0, help="dtts_config.tune_flags of the vocoder context (A/B switches, include/dicttts_hip.h)")
     ap.add_argument("--no-pipeline", action="store_true",
@@ -490,6 +501,8 @@ def main():
     # ---- fp16 range guard over the BENCHED batches: one guarded forward of each distinct batch before anything is timed.
     # The guarded kernel instantiations count every pre-activation the fp16 operands cannot represent (dtts_vocoder_clamped); the timed
     # loop then runs the release instantiations.  A non-zero count means DTTS_VOC_F16 is not valid for this workload.
+    # It runs without --full too: every decode draws the next prior sample of the context's seeded noise stream, so this pass fixes
+    # the samples (and with --gpus N the gather calls) of the warm-up and timed steps.  Its count is printed as `range_guard`.
     guard_info = None
     if args.precision == "f16":
         voc.ctx.vocoder_range_guard(True)
@@ -526,9 +539,9 @@ def main():
             raise RuntimeError("--dump-outputs: rank 0 processed no batch in the last timed step")
         dumped = dump_outputs(np, args.dump_outputs, state["last_step"], voc if args.input != "resident" else None)
 
-    # ---- after the timed region, rank 0 only, nothing else on the GPU
+    # ---- --full: after the timed region, rank 0 only, nothing else on the GPU
     side = stages = iso = modes = voc2 = other = None
-    if rank == 0 and not args.no_side and state["last"] is not None:
+    if rank == 0 and args.full and not args.no_side and state["last"] is not None:
         gather_save, gather_on = gather_on, False       # the side measurements are single-rank
         side = {}
         for name, mode, n in (("inputs_resident", "resident", 6), ("tensor_api_incl_h2d", "tensors", 3)):
@@ -740,10 +753,11 @@ def main():
         achieved = FLOP_PER_FRAME_VOCODER * frames_rank / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
         # HBM bytes of the same kernel family: PMC counters cannot be read from inside the process, so the committed
         # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE result (profiles/r*_pmc_traffic.json of the newest round, corrected
-        # as MI355X_MICROARCH.md prescribes) is scaled by this run's frame count; null if the file is absent
+        # for the HBM counter convention: FETCH_SIZE doubled) is read from that committed file, not measured, and scaled by this
+        # run's frame count; only with --full, null if the file is absent
         traffic = traffic_src = None
         import glob
-        tps = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")))
+        tps = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json"))) if args.full else []
         if tps and conv_launches:
             with open(tps[-1]) as f:
                 tj = json.load(f)
@@ -754,7 +768,7 @@ def main():
         shapes = sorted({(b["B"], b["T_w"], b["L_k"]) for b in batches if b is not None})
         out = {
             "metric": "mel-frames/sec, end-to-end text->mel->wav (audio-samples/sec = 256x; RTF reported alongside)",
-            "value": value, "unit": "mel-frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "value": value, "unit": "mel-frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
             "scaling": "weak" if args.workload == "rotating" else "strong", "vs_baseline": None,
             "dtype": {"f16": "f16 (vocoder ResBlocks fp16 MFMA, serial convolutions bf16 hi/lo split; acoustic model fp32-grade: fp32 MFMA / bf16 three-piece operands x 6 products)",
@@ -795,7 +809,7 @@ def main():
                          "algorithmic_flop_per_mel_frame": FLOP_PER_FRAME_VOCODER,
                          "note": "achieved = algorithmic FLOPs (one product per MAC; the split-operand serial convolutions issue three) / "
                                  "hipEvent time of these kernels inside the timed region, where they share the CUs with the next batch's "
-                                 "text->mel kernels; 'isolated' = the same kernels on the last batch alone"},
+                                 "text->mel kernels; 'isolated' (--full) = the same kernels on the last batch alone"},
         }
         if iso is not None and iso[0] > 0:
             ia = FLOP_PER_FRAME_VOCODER * iso[2] / (iso[0] * 1e-3) / 1e12
@@ -803,6 +817,8 @@ def main():
                                            "kernel_ms_per_forward": iso[0], "launches": iso[1], "mel_frames": iso[2],
                                            "what": "three forwards of the LAST timed batch alone on the GPU; achieved / frac are priced on THAT batch's own valid "
                                                    "frame count (mel_frames), not on the run's average batch"}
+        if guard_info is not None:
+            out["range_guard"] = guard_info
         if dumped is not None:
             out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if side:
@@ -811,7 +827,7 @@ def main():
             out["vocoder_modes"] = modes
         if stages is not None:
             out["stages"] = stages
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cb = cpu_baseline(torch, np, synth, voc, args.cpu_baseline, args.cpu_budget)
             kept_all = cb.pop("_kept")
             out["cpu_baseline"] = cb

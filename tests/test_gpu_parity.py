@@ -1484,6 +1484,35 @@ def test_bench_config5_four_ranks_on_one_device_split():
     assert "dp4" in four["config"]["parallelism"] and "configs[4]" in four["config"]["workload"]
 
 
+def test_bench_plain_run_is_headline_only_and_full_adds_the_rest():
+    """bench.py without --full prints the headline and the range guard's count only; --full adds the side figures, the per-stage figures,
+    roofline.isolated / roofline.traffic and vocoder_modes (the CPU baseline, the slow part of --full, is left out with --no-cpu-baseline).
+    Both runs step through the same batches: the same frames per step and the same guarded forwards."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(extra):
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "1", "--warmup", "1"] + extra, cwd=root,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+
+    plain, full = run([]), run(["--full", "--no-cpu-baseline"])
+    for d in (plain, full):
+        assert all(k in d for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")) and d["value"] > 0
+        assert d["range_guard"]["guarded_forwards"] == 4 and d["range_guard"]["clamped_activations"] == 0
+    assert plain["full"] is False and full["full"] is True
+    assert not any(k in plain for k in ("side", "stages", "vocoder_modes", "cpu_baseline"))
+    assert "isolated" not in plain["roofline"] and plain["roofline"]["traffic"] is None
+    assert all(k in full for k in ("side", "stages", "vocoder_modes")) and "cpu_baseline" not in full
+    assert sorted(full["side"]) == ["inputs_resident", "tensor_api_incl_h2d"] and "long_form" in full["stages"]
+    assert "isolated" in full["roofline"] and full["roofline"]["traffic"] is not None
+    assert full["vocoder_modes"]["f16"]["range_guard"] == full["range_guard"]
+    assert plain["config"]["mel_frames_per_step_per_gpu"] == full["config"]["mel_frames_per_step_per_gpu"]
+
+
 # ------------------------------------------------------------------------------------------------ memory safety (VERDICT r3 #2)
 def _redzoned(t, pad_elems=4096, fill=float("nan")):
     """a copy of tensor t on the GPU whose storage has `pad_elems` sentinel elements before and after it: (view, check) where check()

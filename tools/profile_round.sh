@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-end measurement set, run ON THE GPU BOX from the repo root (gpurun -- 'bash tools/profile_round.sh <tag>').  Everything is
 # summarised on the box; only small text files land under gpurun_out/<tag>/ (copy the ones to keep into profiles/):
-#   bench.json               default bench.py line (with cpu_baseline)
+#   bench.json               bench.py --full line (with cpu_baseline)
 #   kernel_trace.md          rocprofv3 --kernel-trace --stats of `bench.py --no-cpu-baseline --no-side` (2 streams, as benched)
 #   kernel_trace_serial.md   the same with --no-pipeline (one stream: the kernels alone on the GPU)
 #   pmc_traffic.json         separate --pmc FETCH_SIZE / WRITE_SIZE passes of the one-stream run -> HBM bytes of the vocoder family
@@ -13,7 +13,7 @@ R=$(pwd)
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 B="python $R/bench.py --no-cpu-baseline --no-side"
 cd /tmp
 summ() {   # $1 = rocprof dir, $2 = bench JSON of the profiled run, $3 = title
