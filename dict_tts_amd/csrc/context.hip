@@ -1369,21 +1369,24 @@ int hifigan_forward_fused(dtts_ctx* h, const float* mel, const int32_t* lens, in
             // (experiment, tune bit 12) C = 32 only: the first TWO ResBlocks in one launch — the k = 3 launch alone is HBM-bound (x in, stage sum out:
             // 4.6 TB/s), together with k = 7 its bytes ride on that launch's compute; the last ResBlock (fused conv_post) stays on its own
             if (fuse && DTTS_TUNE(h, 4096) && !DTTS_TUNE(h, 512) && nk == 3 && ch == 32 && !h->rbf1[(size_t)i * nk].empty() && !h->rbf1[(size_t)i * nk + 1].empty()) {
-                const int k2 = std::max(h->rbf1[(size_t)i * nk][0].K, h->rbf1[(size_t)i * nk + 1][0].K), TT2 = 1024 - 12 * (k2 - 1);
-                if (TT2 >= 64 && (long long)B * ((rows + TT2 - 1) / TT2) >= 2LL * h->n_cu) fuse_n[i] = 2;
+                int halo2 = 0;   // the launch's halo (rblock.h rblock_halo over its two ResBlocks)
+                for (int j = 0; j < 2; ++j) halo2 = std::max(halo2, rblock_halo_of(h->rbf1[(size_t)i * nk + j][0].K, c.resblock_dilation_sizes[j]));
+                const int TT2 = rblock_stage_tile_rows(ch, halo2);
+                if (TT2 >= 64 && rblock_stage_launch_fits(ch, halo2, B, false) && (long long)B * ((rows + TT2 - 1) / TT2) >= 2LL * h->n_cu) fuse_n[i] = 2;
                 continue;
             }
             bool all = fuse && DTTS_TUNE(h, 512) && nk >= 2 && nk <= 3 && (ch == 32 || ch == 64);
-            int kmax = 0;
+            int halo = 0;
             for (int j = 0; j < nk && all; ++j) {
                 all = !h->rbf1[(size_t)i * nk + j].empty();
-                if (all) kmax = std::max(kmax, h->rbf1[(size_t)i * nk + j][0].K);
+                if (all) halo = std::max(halo, rblock_halo_of(h->rbf1[(size_t)i * nk + j][0].K, c.resblock_dilation_sizes[j]));
             }
             if (!all) continue;
-            const int W = ch == 32 ? 1024 : 512, TT = W - 12 * (kmax - 1);
-            if (TT < 64 || (long long)B * ((rows + TT - 1) / TT) < 2LL * h->n_cu) continue;
-            if (i == nup - 1 && h->post_w) {   // with the fused conv_post the tiles overlap: one private strip of the stage sum per tile
-                const long long prow = rblock_private_rows(ch, kmax, B, (int)rows);
+            const bool with_post = i == nup - 1 && h->post_w;
+            const int TT = rblock_stage_tile_rows(ch, halo);
+            if (TT < 64 || !rblock_stage_launch_fits(ch, halo, B, with_post) || (long long)B * ((rows + TT - 1) / TT) < 2LL * h->n_cu) continue;
+            if (with_post) {   // with the fused conv_post the tiles overlap: one private strip of the stage sum per tile
+                const long long prow = rblock_private_rows(ch, halo, B, (int)rows);
                 if (prow <= 0 || (size_t)prow * ch * sizeof(float) >= (size_t)INT_MAX) continue;
                 s_elems = std::max(s_elems, (size_t)prow * ch);
             }

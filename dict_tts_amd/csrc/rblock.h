@@ -24,7 +24,7 @@ struct RBlockParams {
     int nrb;
     const int* lens;       // [B] valid rows
     int B, T;
-    int K;                 // the LARGEST kernel size of the launch: the tile's halo is 6 (K - 1) rows per side
+    int K;                 // the LARGEST kernel size of the launch (the tile's halo: rblock_halo)
     int mode;              // what the (first) ResBlock of the launch does with the stage sum: 0: xs = r ; 1: xs += r ; 2: xs = (xs + r) / div, and emit Sa
     int last_mode;         // nrb > 1: the same for the launch's LAST ResBlock (2 when it is the stage's last, else 1); those in between accumulate (1)
     int drop_S;            // mode 2 with Sa: do not write the fp32 xs (nothing reads it after the stage)
@@ -45,11 +45,31 @@ struct RBlockParams {
     int dbg;               // -DDTTS_ABLATE builds only; tuning ablations (DTTS_VCONV_DBG): 1 skip contractions, 2 skip epilogue, 4 skip the x load, 8 skip write_act
 };
 
+// rows of halo per side of a tile for one ResBlock of kernel size K: the sum of its six convolutions' receptive half-widths,
+// (K - 1) / 2 * (d0 + d1 + d2 + 3), and never less than 6 (K - 1) — exactly that for dilations (1, 3, 5)
+__host__ __device__ inline int rblock_halo_of(int K, const int* dil) {
+    const int need = (K - 1) / 2 * (dil[0] + dil[1] + dil[2] + 3);
+    return need > 6 * (K - 1) ? need : 6 * (K - 1);
+}
+// the halo of a launch: the largest of its ResBlocks' (and at least 6 (p.K - 1))
+__host__ __device__ inline int rblock_halo(const RBlockParams& p) {
+    int h = 6 * (p.K - 1);
+    for (int j = 0; j < p.nrb && j < 3; ++j) {
+        const int need = rblock_halo_of(p.rb[j].K, p.rb[j].dil);
+        h = need > h ? need : h;
+    }
+    return h;
+}
+
 bool rblock_supported(int C, int K);
 int rblock_padded_taps(int C, int K);
 hipError_t rblock_launch(const RBlockParams& p, int C, hipStream_t stream);
+// the launches with ALL ResBlocks of a stage (nrb > 1; tune bits 9 / 12), for a launch halo of `halo` rows (rblock_halo):
 // rows a fused launch with the fused conv_post needs in S (one private strip per tile), or 0 when the configuration does not fuse
-long long rblock_private_rows(int C, int Kmax, int B, int T);
+long long rblock_private_rows(int C, int halo, int B, int T);
+// valid rows per tile of that launch (conv_post not counted), and whether its LDS — incl. the tile table of B utterances — fits
+int rblock_stage_tile_rows(int C, int halo);
+bool rblock_stage_launch_fits(int C, int halo, int B, bool wav);
 // rblock2.hip: two phase-shifted groups of waves per workgroup (one computing while the other rewrites / loads / stores)
 bool rblock2_supported(int C, int K, bool wav);
 hipError_t rblock2_launch(const RBlockParams& p, int C, hipStream_t stream);

@@ -7,7 +7,8 @@
 //   * the bf16 leaky_relu copy that feeds the next convolution lives in ONE LDS buffer (A and the intermediate
 //     xt time-share it: conv reads -> barrier -> overwrite -> barrier),
 //   * weights stream from L2 through a 4-deep register ring (22..90 KB per conv, shared by every workgroup),
-//   * the tile carries a halo of 6*(k-1) rows per side (sum of the six receptive half-widths) that is recomputed;
+//   * the tile carries a halo of 6*(k-1) rows per side (sum of the six receptive half-widths at dilations (1, 3, 5); more
+//     for larger dilations: rblock_halo) that is recomputed;
 //     rows outside the utterance are forced to zero after every activation = the reference's zero padding.
 // HBM traffic per ResBlock drops from ~9 passes to: read x once, read-modify-write the stage accumulator once.
 // PS = 1 (all but C = 32): persistent workgroups walk the batch's valid tiles, the next tile's x is fetched straight into the
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
     // per-thread coordinates; PS refreshes them through an opaque move at every tile (see the tile loop)
     int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int wt = wave % WT, wc = wave / WT;
-    const int H = 6 * (p.K - 1);
+    const int H = rblock_halo(p);
     const int TT = W - 2 * H;
     // fused conv_post (p.wav): the tile's TT valid rows give TT - (PK - 1) output samples, so tiles step by that and start
     // (PK - 1) / 2 rows early
@@ -587,24 +588,31 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
 #endif
 }
 
+// dynamic LDS of an rb_launch_cfg configuration for TT valid rows per tile, WITHOUT the persistent form's tile table
+template <int C, int MT, int WT, bool TB>
+static size_t rb_lds_bytes(int TT, bool wav) {
+    constexpr int W = 32 * MT * WT, PITCH = C * 2 + 16, EP = C * 4 + 16;
+    constexpr size_t ACT = (size_t)(W + 2 * RB_GUARD) * PITCH;
+    if (wav)   // fused conv_post (7 taps): the fp32 output tile may be larger than the activation tile it replaces
+        return TB ? std::max(2 * ACT, (size_t)TT * C * 4 + (size_t)WT * 32 * EP) : std::max((size_t)TT * C * 4, ACT) + (size_t)WT * 32 * EP;
+    return TB ? std::max(2 * ACT, ACT + (size_t)RB_GUARD * PITCH + (size_t)WT * 32 * EP) : ACT + (size_t)WT * 32 * EP;   // TB: the staging rows lie over the xt buffer
+}
+static size_t rb_table_bytes(int B) { return (size_t)(3 * B + 2) * sizeof(int); }   // tile table: prefix sums [B + 1], counts [B], lengths [B]
+
+// hipErrorOutOfMemory: the configuration's LDS (with the tile table of p.B utterances) exceeds 160 KB — the caller picks another one
 template <int C, int MT, int NT, int WT, int WC, int EL, int PS, bool GUARD = false, bool TB = false>
 static hipError_t rb_launch_cfg(const RBlockParams& p, hipStream_t stream) {
-    constexpr int W = 32 * MT * WT, PITCH = C * 2 + 16, EP = C * 4 + 16;
-    const int H = 6 * (p.K - 1), TT = W - 2 * H;
+    constexpr int W = 32 * MT * WT;
+    const int H = rblock_halo(p), TT = W - 2 * H;
     if (TT < 32) return hipErrorInvalidValue;
     if ((long long)p.T * C * 4 >= (1LL << 31)) return hipErrorInvalidValue;   // 32-bit byte offsets inside an utterance's buffer resource
-    constexpr size_t ACT = (size_t)(W + 2 * RB_GUARD) * PITCH;
-    size_t lds = TB ? std::max(2 * ACT, ACT + (size_t)RB_GUARD * PITCH + (size_t)WT * 32 * EP) : ACT + (size_t)WT * 32 * EP;   // TB: the staging rows lie over the xt buffer
-    int TTo = TT;
-    if (p.wav) {   // fused conv_post (7 taps): the fp32 output tile may be larger than the activation tile it replaces
-        if (C != 32 || (p.nrb == 1 && p.mode != 2) || !p.post_w || !p.post_b) return hipErrorInvalidValue;
-        lds = TB ? std::max(2 * ACT, (size_t)TT * C * 4 + (size_t)WT * 32 * EP) : std::max((size_t)TT * C * 4, ACT) + (size_t)WT * 32 * EP;
-        TTo = TT - 6;
-    }
+    if (p.wav && (C != 32 || (p.nrb == 1 && p.mode != 2) || !p.post_w || !p.post_b)) return hipErrorInvalidValue;
+    size_t lds = rb_lds_bytes<C, MT, WT, TB>(TT, p.wav != nullptr);
+    const int TTo = p.wav ? TT - 6 : TT;
     RBlockParams q = p;
-    q.pre_off = (int)lds;                          // tile table: prefix sums [B + 1], counts [B], lengths [B]
-    if (PS) lds += (size_t)(3 * p.B + 2) * sizeof(int);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    q.pre_off = (int)lds;
+    if (PS) lds += rb_table_bytes(p.B);
+    if (lds > 160 * 1024) return hipErrorOutOfMemory;
     if constexpr (EL == EL_F16 && !GUARD) {
         if (p.ovf) return rb_launch_cfg<C, MT, NT, WT, WC, EL, PS, true, TB>(p, stream);
     }
@@ -647,9 +655,21 @@ bool rblock_supported(int C, int K) {
     return C == 32 || C == 64 || ((C == 128 || C == 256) && K == 3);
 }
 
-long long rblock_private_rows(int C, int Kmax, int B, int T) {
+// the one-launch forms (nrb > 1) run on rb_launch_cfg<32, 4, 1, 8, 1, ., 1> (C = 32) / <64, 4, 1, 4, 2, ., 1> (C = 64): rb_launch_el
+int rblock_stage_tile_rows(int C, int halo) {
+    return (C == 32 ? 1024 : 512) - 2 * halo;
+}
+
+bool rblock_stage_launch_fits(int C, int halo, int B, bool wav) {
+    const int TT = rblock_stage_tile_rows(C, halo);
+    if (C != 32 && C != 64) return false;
+    const size_t lds = (C == 32 ? rb_lds_bytes<32, 4, 8, false>(TT, wav) : rb_lds_bytes<64, 4, 4, false>(TT, wav)) + rb_table_bytes(B);
+    return TT >= 32 && lds <= 160 * 1024;
+}
+
+long long rblock_private_rows(int C, int halo, int B, int T) {
     if (C != 32) return 0;
-    const int W = 1024, TT = W - 12 * (Kmax - 1), TTo = TT - 6;    // rb_launch_cfg<32, 4, 1, 8, 1, ., 1> with the fused conv_post
+    const int TT = rblock_stage_tile_rows(C, halo), TTo = TT - 6;    // with the fused conv_post
     if (TTo < 32) return 0;
     return (long long)B * ((T + TTo - 1) / TTo) * TT;
 }
@@ -680,8 +700,8 @@ static hipError_t rb_launch_el(const RBlockParams& p, int C, hipStream_t stream)
         hipDeviceProp_t prop;
         cus = hipGetDeviceProperties(&prop, cur_dev) == hipSuccess ? prop.multiProcessorCount : 256;
     }
-    auto few = [&](int W) {   // tiles of W rows (valid: W - 12 (k - 1), the fused conv_post 6 less): at most half the CUs get one
-        const int tt = W - 12 * (p.K - 1) - (p.wav ? 6 : 0);
+    auto few = [&](int W) {   // tiles of W rows (valid: W - 2 rblock_halo, the fused conv_post 6 less): at most half the CUs get one
+        const int tt = W - 2 * rblock_halo(p) - (p.wav ? 6 : 0);
         return small_ok && tt >= 32 && 2 * (long long)p.B * ((p.T + tt - 1) / tt) <= cus;
     };
     if (p.nrb < 1 || p.nrb > 3) return hipErrorInvalidValue;
@@ -692,7 +712,7 @@ static hipError_t rb_launch_el(const RBlockParams& p, int C, hipStream_t stream)
     }
     // (experiment, tune bit 7) C = 32 without the fused conv_post: two phase-shifted groups per workgroup (rblock2.hip)
 #ifdef DTTS_ABLATE   // (rblock2.hip is compiled into the ablation library only)
-    if (p.pingpong && rblock2_supported(C, p.K, p.wav != nullptr) && !few(512)) return rblock2_launch(p, C, stream);
+    if (p.pingpong && rblock_halo(p) == 6 * (p.K - 1) && rblock2_supported(C, p.K, p.wav != nullptr) && !few(512)) return rblock2_launch(p, C, stream);
 #endif
 #if defined(RB_TB32)   // experiment: two activation buffers at C = 32, k >= 7: 768-row tiles (MT = 3), two barriers per iteration instead of four
     if (C == 32 && rb32 && p.K >= 7 && !few(768)) return rb_launch_cfg<32, 3, 1, 8, 1, EL, 1, false, true>(p, stream);
@@ -700,12 +720,19 @@ static hipError_t rb_launch_el(const RBlockParams& p, int C, hipStream_t stream)
 #if defined(RB_X32) && RB_X32 == 1   // experiment: 12 waves (3 per SIMD) over 1152 rows at C = 32, k >= 7
     if (C == 32 && rb32 && p.K >= 7 && !few(1152)) {   // (with the fused conv_post the 1152-row output tile does not fit the LDS: falls through)
         const hipError_t e = rb_launch_cfg<32, 3, 1, 12, 1, EL, 1>(p, stream);
-        if (e != hipErrorInvalidValue) return e;
+        if (e != hipErrorInvalidValue && e != hipErrorOutOfMemory) return e;
     }
 #elif defined(RB_X32) && RB_X32 == 2 // experiment: 12 waves (3 per SIMD) over 768 rows, MT = 2
     if (C == 32 && rb32 && p.K >= 7 && !few(768)) return rb_launch_cfg<32, 2, 1, 12, 1, EL, 1>(p, stream);
 #endif
-    if (C == 32 && rb32 && p.K >= 7 && !few(1024)) return rb_launch_cfg<32, 4, 1, 8, 1, EL, 1>(p, stream);
+    // RB_TRY: a persistent configuration whose LDS cannot hold the tile table of this many utterances (hipErrorOutOfMemory: the fused
+    // conv_post's 1024-row tile above ~940 utterances, the 128-row C = 256 tile above ~1730) falls through to the next one down
+#define RB_TRY(call)                                   \
+    do {                                               \
+        const hipError_t e_ = (call);                  \
+        if (e_ != hipErrorOutOfMemory) return e_;      \
+    } while (0)
+    if (C == 32 && rb32 && p.K >= 7 && !few(1024)) RB_TRY((rb_launch_cfg<32, 4, 1, 8, 1, EL, 1>(p, stream)));
     if (C == 64 && few(512)) return rb_launch_cfg<64, 4, 1, 2, 2, EL, 1>(p, stream);     // 256-row tile, 4 waves
     if (C == 128 && few(256)) return rb_launch_cfg<128, 4, 1, 1, 4, EL, 1>(p, stream);   // 128-row tile, 4 waves
     if (C == 256 && few(128)) return rb_launch_cfg<256, 2, 1, 1, 8, EL, 1>(p, stream);   // 64-row tile
@@ -720,10 +747,14 @@ static hipError_t rb_launch_el(const RBlockParams& p, int C, hipStream_t stream)
 #if defined(RB_X128)  // experiment: 12 waves (3 time x 4 channel), 288-row tiles at C = 128 (k = 3)
     if (C == 128) return rb_launch_cfg<128, 3, 1, 3, 4, EL, 1>(p, stream);
 #endif
-    if (C == 64 && p.K >= 7 && !p.small_tile) return rb_launch_cfg<64, 5, 1, 4, 2, EL, 1>(p, stream);
-    if (C == 64) return rb_launch_cfg<64, 4, 1, 4, 2, EL, 1>(p, stream);      // 512-row tile, 8 waves (4 time x 2 channel)
-    if (C == 128) return rb_launch_cfg<128, 4, 1, 2, 4, EL, 1>(p, stream);    // 256-row tile, 8 waves (2 time x 4 channel)
-    if (C == 256) return rb_launch_cfg<256, 4, 1, 1, 8, EL, 1>(p, stream);    // 128-row tile, 8 waves over channels
+    if (C == 64 && p.K >= 7 && !p.small_tile) RB_TRY((rb_launch_cfg<64, 5, 1, 4, 2, EL, 1>(p, stream)));
+    if (C == 64) RB_TRY((rb_launch_cfg<64, 4, 1, 4, 2, EL, 1>(p, stream)));    // 512-row tile, 8 waves (4 time x 2 channel)
+    if (C == 64) return rb_launch_cfg<64, 4, 1, 2, 2, EL, 1>(p, stream);       // (the tile table of a very large batch) 256-row tile
+    if (C == 128) RB_TRY((rb_launch_cfg<128, 4, 1, 2, 4, EL, 1>(p, stream)));  // 256-row tile, 8 waves (2 time x 4 channel)
+    if (C == 128) return rb_launch_cfg<128, 4, 1, 1, 4, EL, 1>(p, stream);     // (ditto) 128-row tile
+    if (C == 256) RB_TRY((rb_launch_cfg<256, 4, 1, 1, 8, EL, 1>(p, stream)));  // 128-row tile, 8 waves over channels
+    if (C == 256) return rb_launch_cfg<256, 2, 1, 1, 8, EL, 1>(p, stream);     // (ditto) 64-row tile
+#undef RB_TRY
     return hipErrorInvalidValue;
 }
 
