@@ -202,9 +202,10 @@ struct dtts_ctx {
     unsigned spk_gen = 0, enc_spk_gen = 0;   // arming count; the one the last encode consumed
     bool enc_spk = false;                    // the last encode was conditioned on spk_rows
     // ---- FVAE posterior pass (dtts_text2mel_fetch(DTTS_OUT_POSTERIOR); modules/dict_tts/fvae_semantics.py:84-108), packed when the checkpoint carries
-    // fvae.encoder.*; otherwise post_missing names the first absent tensor and the call is refused
+    // fvae.encoder.*; otherwise post_missing names the first absent tensor and the call is refused.  A shape the pass does not support
+    // still loads for inference: post_unsupported says why, and the posterior call is refused with it
     bool post_ready = false;
-    std::string post_missing;
+    std::string post_missing, post_unsupported;
     PackedConv post_pre;                     // encoder.pre_net.0: Conv1d(n_mel -> hidden, k = 8, s = 4, p = 2)
     WNet post_wn;                            // encoder.wn (fvae_enc_n_layers layers, conditioned on g_sqz)
     float *post_wt = nullptr, *post_bias = nullptr;   // encoder.out_proj as W^T [hidden][2 latent] + bias [2 latent]
@@ -599,9 +600,16 @@ int build_speaker(dtts_ctx* h) {
 int build_posterior(dtts_ctx* h) {
     h->post_ready = false;
     h->post_missing.clear();
+    h->post_unsupported.clear();
     h->flows_fwd.clear();
     const dtts_config& c = h->cfg;
     const std::string p = "model.fvae.encoder";
+    if (c.latent_size != 16 || c.fvae_enc_dec_hidden > 512 || c.frames_multiple % 4) {
+        h->post_unsupported = "the posterior pass supports latent_size 16, fvae_enc_dec_hidden <= 512 and frames_multiple % 4 == 0 (latent_size " +
+                              std::to_string(c.latent_size) + ", fvae_enc_dec_hidden " + std::to_string(c.fvae_enc_dec_hidden) +
+                              ", frames_multiple " + std::to_string(c.frames_multiple) + ")";
+        return DTTS_OK;
+    }
     if (!h->w.count(p + ".pre_net.0.weight") && !h->w.count(p + ".pre_net.0.weight_v")) {
         h->post_missing = p + ".pre_net.0.weight";
         return DTTS_OK;
@@ -692,8 +700,6 @@ int build_posterior(dtts_ctx* h) {
         if (h->err.empty()) return fail(h, DTTS_E_NOMEM, "packing / uploading the FVAE posterior encoder failed");
         return DTTS_E_INVAL;
     }
-    if (Z != 16 || Hd > 512 || c.frames_multiple % 4)
-        return fail(h, DTTS_E_INVAL, "the posterior pass supports latent_size 16, fvae_enc_dec_hidden <= 512 and frames_multiple % 4 == 0");
     h->post_ready = true;
     return DTTS_OK;
 }
@@ -825,7 +831,8 @@ int build_acoustic(dtts_ctx* h) {
             }
         }
     }
-    if (ok && parity != 0) return fail(h, DTTS_E_INVAL, "odd number of flow blocks is not supported");
+    if (ok && parity != 0)
+        return fail(h, DTTS_E_INVAL, "prior_glow_n_blocks %d: an odd number of flow blocks is not supported", c.prior_glow_n_blocks);
     h->fs_w = nullptr;
     if (ok && fuse_flows && !h->flows.empty()) {
         h->fs_w = upload(h, fs_host);
@@ -2590,6 +2597,8 @@ int dtts_text2mel_decode(dtts_handle h, const float* z_p, float* mel_out, dtts_s
 // (dtts_text2mel_fetch(DTTS_OUT_POSTERIOR): the argument block has been checked by the caller)
 static int posterior_impl(dtts_handle h, const float* tgt_mels, int mel_ld, const float* eps, int eps_ld, float* mel_out, int mel_cap,
                           float* m_q, float* logs_q, float* z_p, float* kl, dtts_stream stream) {
+    if (!h->post_ready && !h->post_unsupported.empty())
+        return fail(h, DTTS_E_INVAL, "dtts_text2mel_fetch(DTTS_OUT_POSTERIOR): %s", h->post_unsupported.c_str());
     if (!h->post_ready)
         return fail(h, DTTS_E_STATE, "dtts_text2mel_fetch(DTTS_OUT_POSTERIOR): the checkpoint lacks the posterior encoder (missing weight "
                     "tensor '%s')", h->post_missing.empty() ? "model.fvae.encoder.pre_net.0.weight" : h->post_missing.c_str());

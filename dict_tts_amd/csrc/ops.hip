@@ -881,8 +881,9 @@ __global__ __launch_bounds__(S2PA_NTHR, DM4 == 1 ? S2PA_WPE : S2PA_WPE3) void s2
         n = s2pa_list(sh, r, L, tid);
         // a word past its utterance whose key_map row turned out all zero (the collater's padding; CHECKED here, the tensors are the caller's)
         // and that is not forced to a sense: uniform weights, no sense carries weight, zero context — the same values the general path below
-        // computes with eight more barriers (52 % of the B x T_w slots of a B = 60 batch)
-        if (n == 0 && dead && pre.mod == 0) {
+        // computes with eight more barriers (52 % of the B x T_w slots of a B = 60 batch).  Not a table row of entry -1 (the padded batch's
+        // last row): it lists no rows either, but its key_map row is all ONES, so sense 1 carries all the weight (pron_attn = 1)
+        if (n == 0 && dead && pre.mod == 0 && r.special != -1) {
             const float u = 1.0f / (float)L;
             float* da = a.dict_attn + (long long)row * L;
             for (int l = tid; l < L; l += S2PA_NTHR) da[l] = u;

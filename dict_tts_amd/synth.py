@@ -85,15 +85,15 @@ def _wn(sd, seed, p, hidden, k, layers, gin):
 SPK_EMBED_DIM = 256   # utterance speaker embeddings of use_spk_embed (modules/portaspeech/model.py:163)
 
 
-def speaker_state_dict(seed=1234, speaker="embed", num_spk=4):
+def speaker_state_dict(seed=1234, speaker="embed", num_spk=4, hidden=HIDDEN):
     """seeded spk_embed_proj weights (modules/portaspeech/model.py:159-163): "embed" = nn.Linear(256, hidden) (weight + bias),
     "id" = Embedding(num_spk, hidden) (weight only).  Rows of about the size of the word encoder output's, so that speakers move
     the durations."""
     sd = {}
     if speaker == "embed":
-        _linear(sd, seed, "spk_embed_proj", HIDDEN, SPK_EMBED_DIM, gain=0.5, bias=0.1)
+        _linear(sd, seed, "spk_embed_proj", hidden, SPK_EMBED_DIM, gain=0.5, bias=0.1)
     elif speaker == "id":
-        sd["spk_embed_proj.weight"] = randn(seed, "spk_embed_proj.table", (num_spk, HIDDEN), 0.5)
+        sd["spk_embed_proj.weight"] = randn(seed, "spk_embed_proj.table", (num_spk, hidden), 0.5)
     else:
         raise ValueError(f"speaker must be 'embed' or 'id', got {speaker!r}")
     return sd
@@ -110,36 +110,53 @@ def speaker_inputs(seed, speaker, B, num_spk=4, name="spk"):
     raise ValueError(f"speaker must be 'embed' or 'id', got {speaker!r}")
 
 
-def dict_tts_state_dict(seed=1234, n_phone=6, word_size=WORD_SIZE, speaker=None, num_spk=4):
+# the acoustic hparams dict_tts_state_dict(acoustic=...) reads, with the defaults it draws without them (hparams.BIAOBEI_DEFAULTS; the
+# prior flow's WaveNets have 4 layers, modules/dict_tts/fvae_semantics.py:77-78)
+ACOUSTIC_SHAPE = {"hidden_size": HIDDEN, "num_heads": 2, "enc_ffn_kernel_size": 5, "dur_predictor_layers": 3, "dur_predictor_kernel": 5,
+                  "latent_size": 16, "fvae_enc_dec_hidden": HIDDEN, "fvae_kernel_size": 5, "fvae_dec_n_layers": 4, "fvae_enc_n_layers": 8,
+                  "prior_glow_hidden": 64, "glow_kernel_size": 3, "prior_glow_n_blocks": 4}
+
+
+def acoustic_shape(hp=None):
+    """the ACOUSTIC_SHAPE keys of hparams dict hp (others ignored), defaults filled in, as ints"""
+    hp = dict(hp or {})
+    return {k: int(hp.get(k, v)) for k, v in ACOUSTIC_SHAPE.items()}
+
+
+def dict_tts_state_dict(seed=1234, n_phone=6, word_size=WORD_SIZE, speaker=None, num_spk=4, acoustic=None):
     """numpy state dict with the key names / shapes of ``state_dict['model']``.  speaker = "embed" / "id" (opt-in)
-    adds the spk_embed_proj of a multi-speaker checkpoint (speaker_state_dict); every other tensor is the same as without it."""
+    adds the spk_embed_proj of a multi-speaker checkpoint (speaker_state_dict); every other tensor is the same as without it.
+    acoustic: hparams (ACOUSTIC_SHAPE keys) giving the model's shape, e.g. {"hidden_size": 256, "num_heads": 4}; None or {} = the
+    ps_flow.yaml shape, drawn bit for bit as before.  num_heads shapes no tensor (it is read at run time only)."""
+    sh = acoustic_shape(acoustic)
     sd = {}
-    h = HIDDEN
+    h = sh["hidden_size"]
+    Hd, Z, Hf = sh["fvae_enc_dec_hidden"], sh["latent_size"], sh["prior_glow_hidden"]
     # PortaSpeech leftovers: loaded, never used by PortaSpeech_dict (modules/portaspeech/model.py:153-158)
     for n in ("enc_pos_proj", "dec_query_proj", "dec_res_proj"):
         _linear(sd, seed, n, h, 2 * h, bias=0.02)
     sd["attn.in_proj_weight"] = randn(seed, "attn.in_proj_weight", (3 * h, h), h ** -0.5)
     _linear(sd, seed, "attn.out_proj", h, h)
-    # duration predictor (modules/portaspeech/model.py:38-66)
-    for i in range(3):
-        _conv(sd, seed, f"dur_predictor.conv.{i}.1", 128, h if i == 0 else 128, 5, gain=1.3)
+    # duration predictor (modules/portaspeech/model.py:38-66, n_chans = 128: :164-169)
+    for i in range(sh["dur_predictor_layers"]):
+        _conv(sd, seed, f"dur_predictor.conv.{i}.1", 128, h if i == 0 else 128, sh["dur_predictor_kernel"], gain=1.3)
         _ln(sd, seed, f"dur_predictor.conv.{i}.3", 128, "weight", "bias")
     sd["dur_predictor.linear.0.weight"] = randn(seed, "dur.lin.w", (1, 128), 0.6 / np.sqrt(128))
     sd["dur_predictor.linear.0.bias"] = np.array([2.2], np.float32)  # ~ exp(2.3)-1 = 9 frames / word
     # FVAE (modules/dict_tts/fvae_semantics.py:61-82)
     _conv(sd, seed, "fvae.g_pre_net.0", h, h, 8, gain=1.0)
-    _conv(sd, seed, "fvae.encoder.pre_net.0", h, N_MEL, 8)
-    _wn(sd, seed, "fvae.encoder.wn", h, 5, 8, h)
-    _conv(sd, seed, "fvae.encoder.out_proj", 32, h, 1)
-    for f in (0, 2, 4, 6):
+    _conv(sd, seed, "fvae.encoder.pre_net.0", Hd, N_MEL, 8)
+    _wn(sd, seed, "fvae.encoder.wn", Hd, sh["fvae_kernel_size"], sh["fvae_enc_n_layers"], h)
+    _conv(sd, seed, "fvae.encoder.out_proj", 2 * Z, Hd, 1)
+    for f in range(0, 2 * sh["prior_glow_n_blocks"], 2):
         p = f"fvae.prior_flow.flows.{f}"
-        _conv(sd, seed, p + ".pre", 64, 8, 1, gain=1.0)
-        _wn(sd, seed, p + ".enc", 64, 3, 4, h)
-        _conv(sd, seed, p + ".post", 8, 64, 1, gain=0.5)
-    _conv(sd, seed, "fvae.decoder.pre_net.0", h, 16, 4, gain=1.0, transposed=True)
+        _conv(sd, seed, p + ".pre", Hf, Z // 2, 1, gain=1.0)
+        _wn(sd, seed, p + ".enc", Hf, sh["glow_kernel_size"], 4, h)
+        _conv(sd, seed, p + ".post", Z // 2, Hf, 1, gain=0.5)
+    _conv(sd, seed, "fvae.decoder.pre_net.0", Hd, Z, 4, gain=1.0, transposed=True)
     # ConvTranspose1d keeps a [cout] bias
-    _wn(sd, seed, "fvae.decoder.wn", h, 5, 4, h)
-    _conv(sd, seed, "fvae.decoder.out_proj", N_MEL, h, 1, gain=1.5)
+    _wn(sd, seed, "fvae.decoder.wn", Hd, sh["fvae_kernel_size"], sh["fvae_dec_n_layers"], h)
+    _conv(sd, seed, "fvae.decoder.out_proj", N_MEL, Hd, 1, gain=1.5)
     sd["fvae.decoder.out_proj.bias"] = (sd["fvae.decoder.out_proj.bias"] - 2.5).astype(np.float32)  # log-mel range
     # dictionary encoder (modules/dict_tts/layers/dict_encoder.py:69-128)
     p = "dict_encoder.S2PA_module"
@@ -147,7 +164,7 @@ def dict_tts_state_dict(seed=1234, n_phone=6, word_size=WORD_SIZE, speaker=None,
     sd[p + ".word_emb.weight"] = randn(seed, p + ".word_emb", (word_size, h), h ** -0.5)
     sd[p + ".emb.weight"][0] = 0
     sd[p + ".word_emb.weight"][0] = 0
-    _rel_encoder(sd, seed, p + ".semantic_encoder")
+    _rel_encoder(sd, seed, p + ".semantic_encoder", h=h, f=4 * h, k=sh["enc_ffn_kernel_size"])
     a = p + ".s2pa_attention"
     _linear(sd, seed, a + ".q_transform", h, h, gain=6.0)
     _linear(sd, seed, a + ".k_transform", h, GLOSS_DIM, gain=6.0)
@@ -155,9 +172,9 @@ def dict_tts_state_dict(seed=1234, n_phone=6, word_size=WORD_SIZE, speaker=None,
     _linear(sd, seed, a + ".output_transform", h, h)
     sd[a + ".pinyin_embedding.weight"] = randn(seed, a + ".pinyin", (N_PINYIN, h), 1.0)
     sd[a + ".pinyin_embedding.weight"][0] = 0
-    _rel_encoder(sd, seed, p + ".linguistic_encoder")
+    _rel_encoder(sd, seed, p + ".linguistic_encoder", h=h, f=4 * h, k=sh["enc_ffn_kernel_size"])
     if speaker is not None:
-        sd.update(speaker_state_dict(seed, speaker, num_spk))
+        sd.update(speaker_state_dict(seed, speaker, num_spk, hidden=h))
     return sd
 
 

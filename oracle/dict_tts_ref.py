@@ -86,15 +86,16 @@ def s2pa_attention(sd, p, x, keys, values, key_map, pinyin, pinyin_map, pron_mod
     context = F.linear(context, sd[p + ".output_transform.weight"]).transpose(1, 2)
     # pronunciation branch: utils.py:49-58 mask_weights_attn
     pin = F.embedding(pinyin, sd[p + ".pinyin_embedding.weight"])            # [B,T,P,192]
-    res = torch.zeros(weights.size(0), weights.size(1), pin.size(2))
+    dt = weights.dtype                                                       # fp32 (the oracle) or float64 (tests/acoustic_ref.py)
+    res = torch.zeros(weights.size(0), weights.size(1), pin.size(2), dtype=dt)
     for i in range(1, int(key_map.max()) + 1):
-        merge = (weights * key_map.eq(i).float()).sum(dim=-1, keepdim=True)
-        res = res + merge * pinyin_map.eq(i).float()
+        merge = (weights * key_map.eq(i).to(dt)).sum(dim=-1, keepdim=True)
+        res = res + merge * pinyin_map.eq(i).to(dt)
     if language == "zh":                                                     # utils.py:109-115 add_pron_rule
         forced = res.clone()
         for i in range(1, int(pinyin_map.max()) + 1):
             sel = pron_modified == i
-            forced[sel] = (pinyin_map[sel] == i).float()
+            forced[sel] = (pinyin_map[sel] == i).to(dt)
         res = forced - res + res  # the straight-through form of utils.py:114, kept for its fp32 rounding
     pron = torch.matmul(res.unsqueeze(-2), pin).squeeze(-2).transpose(1, 2)
     return context, align, pron, res
@@ -116,7 +117,7 @@ def dict_encoder(sd, word_tokens, dict_msg, pron_modified, hidden=192, n_heads=2
     context = context * x_mask
     x = context + pron
     x = rel_encoder(sd, p + ".linguistic_encoder", x, x_mask, 4, n_heads, ffn_k)
-    x = x.transpose(1, 2) * (word_tokens > 0).float()[:, :, None]
+    x = x.transpose(1, 2) * (word_tokens > 0).to(x.dtype)[:, :, None]
     return x, dict_attn, pron_align, context.transpose(1, 2)
 
 
@@ -127,7 +128,7 @@ def duration_predictor(sd, xs, x_masks, n_layers=3, k=5):
     """DurationPredictor.forward, padding='SAME' (modules/portaspeech/model.py:58-66) with the torch
     LayerNorm(eps=1e-5) over channels (modules/fastspeech/tts_modules.py:60-79)"""
     xs = xs.transpose(1, -1)
-    keep = (1 - x_masks.float())[:, None, :]
+    keep = (1 - x_masks.to(xs.dtype))[:, None, :]
     for i in range(n_layers):
         xs = F.pad(xs, ((k - 1) // 2, (k - 1) // 2))
         xs = F.conv1d(xs, sd[f"dur_predictor.conv.{i}.1.weight"], sd[f"dur_predictor.conv.{i}.1.bias"])
@@ -137,7 +138,7 @@ def duration_predictor(sd, xs, x_masks, n_layers=3, k=5):
         xs = xs * keep
     xs = F.linear(xs.transpose(1, -1), sd["dur_predictor.linear.0.weight"], sd["dur_predictor.linear.0.bias"])
     xs = F.softplus(xs)[:, :, 0]
-    return xs * (1 - x_masks.float())
+    return xs * (1 - x_masks.to(xs.dtype))
 
 
 def length_regulator(dur, ilens):
@@ -159,10 +160,10 @@ def length_regulator(dur, ilens):
     return out
 
 
-def add_dur(sd, dur_input, mel2word):
-    """PortaSpeech_dict.add_dur (modules/dict_tts/model.py:64-82), dur_scale='log'"""
+def add_dur(sd, dur_input, mel2word, n_layers=3, k=5):
+    """PortaSpeech_dict.add_dur (modules/dict_tts/model.py:64-82), dur_scale='log'; n_layers / k: dur_predictor_layers / _kernel"""
     src_padding = dur_input.abs().sum(-1) == 0
-    dur = duration_predictor(sd, dur_input, src_padding)
+    dur = duration_predictor(sd, dur_input, src_padding, n_layers, k)
     if mel2word is None:
         d = torch.clamp(torch.round(dur.exp() - 1), min=0).long()
         mel2word = length_regulator(d, (1 - src_padding.long()).sum(-1))
@@ -174,7 +175,7 @@ def expand(word_encoder_out, mel2word, frames_multiple=4):
     if mel2word.shape[1] % frames_multiple > 0:
         pad_len = frames_multiple - mel2word.shape[1] % frames_multiple
         mel2word = torch.cat([mel2word] + [mel2word[:, -1:]] * pad_len, -1)
-    tgt_nonpadding = (mel2word > 0).float()[:, :, None]
+    tgt_nonpadding = (mel2word > 0).to(word_encoder_out.dtype)[:, :, None]
     x = F.pad(word_encoder_out, [0, 0, 1, 0])
     x = torch.gather(x, 1, mel2word[..., None].repeat([1, 1, x.shape[-1]]))
     return x, tgt_nonpadding, mel2word
@@ -183,12 +184,15 @@ def expand(word_encoder_out, mel2word, frames_multiple=4):
 # ---------------------------------------------------------------------------------------------------------
 # A8-A10: FVAE prior flow + decoder
 # ---------------------------------------------------------------------------------------------------------
-def wn(sd, p, x, g, hidden, k, n_layers):
-    """WN.forward with x_mask = 1, dilation_rate 1 (modules/commons/wavenet.py:54-78, :5-11)"""
+def wn(sd, p, x, g, hidden, k, n_layers, hook=None):
+    """WN.forward with x_mask = 1, dilation_rate 1 (modules/commons/wavenet.py:54-78, :5-11).  hook(p, i, x, x_in) -> x_in, if given,
+    may replace layer i's dilated-convolution output (tests plant kernel defects through it; None = the reference)"""
     output = torch.zeros_like(x)
     g = F.conv1d(g, sd[p + ".cond_layer.weight"], sd[p + ".cond_layer.bias"])
     for i in range(n_layers):
         x_in = F.conv1d(x, sd[f"{p}.in_layers.{i}.weight"], sd[f"{p}.in_layers.{i}.bias"], padding=(k - 1) // 2)
+        if hook is not None:
+            x_in = hook(p, i, x, x_in)
         in_act = x_in + g[:, i * 2 * hidden:(i + 1) * 2 * hidden, :]
         acts = torch.tanh(in_act[:, :hidden, :]) * torch.sigmoid(in_act[:, hidden:, :])
         rs = F.conv1d(acts, sd[f"{p}.res_skip_layers.{i}.weight"], sd[f"{p}.res_skip_layers.{i}.bias"])
@@ -200,7 +204,7 @@ def wn(sd, p, x, g, hidden, k, n_layers):
     return output
 
 
-def prior_flow_reverse(sd, z, g_sqz, n_flows=4, hidden=64, k=3, n_layers=4):
+def prior_flow_reverse(sd, z, g_sqz, n_flows=4, hidden=64, k=3, n_layers=4, hook=None):
     """ResidualCouplingBlock.forward(reverse=True) (modules/portaspeech/glow_modules.py:157-163): for flow
     in reversed([rcl0, flip, rcl1, flip, ...]); ResidualCouplingLayer.forward mean_only (:108-128); Flip (:9-13)"""
     half = z.shape[1] // 2
@@ -209,7 +213,7 @@ def prior_flow_reverse(sd, z, g_sqz, n_flows=4, hidden=64, k=3, n_layers=4):
         p = f"fvae.prior_flow.flows.{2 * f}"
         x0, x1 = z[:, :half], z[:, half:]
         h = F.conv1d(x0, sd[p + ".pre.weight"], sd[p + ".pre.bias"])
-        h = wn(sd, p + ".enc", h, g_sqz, hidden, k, n_layers)
+        h = wn(sd, p + ".enc", h, g_sqz, hidden, k, n_layers, hook)
         m = F.conv1d(h, sd[p + ".post.weight"], sd[p + ".post.bias"])
         x1 = (x1 - m) * torch.exp(-torch.zeros_like(m))
         z = torch.cat([x0, x1], 1)
@@ -236,8 +240,8 @@ def forward_infer(sd, word_tokens, dict_msg, pron_modified, mel2word=None, z_p=N
     with torch.no_grad():
         ret = {}
         padding_mask = word_tokens.eq(0)
-        nonpadding = (1 - padding_mask.float())[:, :, None]
         weo, dict_attn, pron_attn, context = dict_encoder(sd, word_tokens, dict_msg, pron_modified)
+        nonpadding = (1 - padding_mask.to(weo.dtype))[:, :, None]
         ret.update(dict_attn=dict_attn, pron_attn=pron_attn, word_encoder_out=weo, context=context)
         dur, mel2word = add_dur(sd, weo * nonpadding, mel2word)
         ret["dur"] = dur

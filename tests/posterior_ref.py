@@ -147,18 +147,22 @@ def decoder_masked(sd, z, x_mask, g, hidden=192, k=5, n_layers=4):
     return F.conv1d(x, sd["fvae.decoder.out_proj.weight"], sd["fvae.decoder.out_proj.bias"])
 
 
-def forward_posterior(sd, word_tokens, dict_msg, pron_modified, tgt_mels, mel2word, eps, form=None, spk=None):
+def forward_posterior(sd, word_tokens, dict_msg, pron_modified, tgt_mels, mel2word, eps, form=None, spk=None, hp=None):
     """PortaSpeech_dict.forward(infer=False) under no_grad, no post-glow (modules/dict_tts/model.py:36-62,84-121; fvae_semantics.py:84-108).
-    sd: folded state dict (torch); tgt_mels [B,T_mel,80]; mel2word [B,T] or None (predicted durations); eps [B,16,T_mel/4];
-    form / spk: speaker conditioning as in tests/speaker_ref.py (None = none)."""
+    sd: folded state dict (torch, fp32 or float64: every float input must have its dtype); tgt_mels [B,T_mel,80]; mel2word [B,T] or None
+    (predicted durations); eps [B,latent,T_mel/4]; form / spk: speaker conditioning as in tests/speaker_ref.py (None = none); hp: the acoustic
+    hparams of the shape (synth.acoustic_shape; None = ps_flow.yaml's)."""
+    sh = synth.acoustic_shape(hp)
+    Hd, kf = sh["fvae_enc_dec_hidden"], sh["fvae_kernel_size"]
     with torch.no_grad():
         ret = {}
-        nonpadding = (1 - word_tokens.eq(0).float())[:, :, None]
-        weo, dict_attn, pron_attn, context = ref.dict_encoder(sd, word_tokens, dict_msg, pron_modified)
+        weo, dict_attn, pron_attn, context = ref.dict_encoder(sd, word_tokens, dict_msg, pron_modified, sh["hidden_size"], sh["num_heads"],
+                                                              sh["enc_ffn_kernel_size"])
+        nonpadding = (1 - word_tokens.eq(0).to(weo.dtype))[:, :, None]
         if form is not None:
             weo = weo + sr.project(sd, form, spk)[:, None, :]                  # model.py:94
         ret.update(dict_attn=dict_attn, pron_attn=pron_attn, word_encoder_out=weo)
-        dur, mel2word = ref.add_dur(sd, weo * nonpadding, mel2word)
+        dur, mel2word = ref.add_dur(sd, weo * nonpadding, mel2word, sh["dur_predictor_layers"], sh["dur_predictor_kernel"])
         ret["dur"] = dur
         x, tgt_nonpadding, mel2word = ref.expand(weo, mel2word)
         ret["mel2word"] = mel2word
@@ -167,9 +171,10 @@ def forward_posterior(sd, word_tokens, dict_msg, pron_modified, tgt_mels, mel2wo
         g = x.transpose(1, 2)
         x_mask = tgt_nonpadding.transpose(1, 2)
         g_sqz = F.conv1d(g, sd["fvae.g_pre_net.0.weight"], sd["fvae.g_pre_net.0.bias"], stride=4, padding=2)   # semantics = 0
-        z_q, m_q, logs_q, x_mask_sqz = posterior_encoder(sd, tgt_mels.transpose(1, 2), x_mask, g_sqz, eps)
-        mel = decoder_masked(sd, z_q, x_mask, g)
-        z_p = prior_flow_forward(sd, z_q, x_mask_sqz, g_sqz)
+        z_q, m_q, logs_q, x_mask_sqz = posterior_encoder(sd, tgt_mels.transpose(1, 2), x_mask, g_sqz, eps, Hd, kf, sh["fvae_enc_n_layers"],
+                                                         sh["latent_size"])
+        mel = decoder_masked(sd, z_q, x_mask, g, Hd, kf, sh["fvae_dec_n_layers"])
+        z_p = prior_flow_forward(sd, z_q, x_mask_sqz, g_sqz, sh["prior_glow_n_blocks"], sh["prior_glow_hidden"], sh["glow_kernel_size"])
         ret["kl"] = kl_term(z_q, m_q, logs_q, z_p, x_mask_sqz)
         ret.update(z_p=z_p, m_q=m_q, logs_q=logs_q)
         ret["mel_out"] = ret["mel_out_fvae"] = mel.transpose(1, 2)
