@@ -37,7 +37,9 @@ class PosteriorArgs(C.Structure):
 
 
 class DttsConfig(C.Structure):
-    """struct dtts_config (include/dicttts_hip.h); field <- reference hparams key"""
+    """struct dtts_config (include/dicttts_hip.h); field <- reference hparams key.
+    resblock_dilation_sizes: one row per kernel size; three dilations >= 1 = ResBlock1, a row whose third entry is 0 = a two-dilation
+    (ResBlock2, ``resblock: "2"``) row; all used rows of one kind (hparams.fill_abi_config writes them from the generator config)."""
     _fields_ = [(n, C.c_int32) for n in (
         "hidden_size", "num_heads", "enc_ffn_kernel_size", "enc_layers", "gloss_dim", "word_size",
         "value_embedding_size", "n_phone", "audio_num_mel_bins", "latent_size", "fvae_enc_dec_hidden",

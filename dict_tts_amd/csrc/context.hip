@@ -23,6 +23,7 @@
 #include "vconv.h"
 #include "rblock.h"
 #include "vpair.h"
+#include "rb2x.h"
 #include "flowstack.h"
 
 using namespace dtts;
@@ -160,6 +161,9 @@ struct dtts_ctx {
     std::vector<PackedConv> ups;
     std::vector<std::vector<PackedConv>> rb1, rb2;  // [resblock][3]
     std::vector<std::vector<PackedConv>> rbf1, rbf2;  // fused-ResBlock copies (taps zero padded), empty where unsupported
+    // ResBlock2 generators (two-dilation rows: resblock_dilation_sizes[j][2] == 0): rb1[i] = convs.{0,1} for the per-convolution path,
+    // rbf1[i] = the same, tap-padded, for the fused kernel (rb2x.hip); rb2 / rbf2 stay empty
+    bool resblock2 = false;
     int hop = 1;
     int tune = 0;
     float *post_w = nullptr, *post_b = nullptr;   // conv_post as [taps][C] fp32 for the fused epilogue of the last ResBlock (rblock.hip), or null
@@ -941,7 +945,21 @@ bool vocoder_fp16_analysis(dtts_ctx* h, Need& need) {
             for (int j = 0; j < nk; ++j) {
                 std::vector<double> x = ux, xm = mx, xt, xtm, y, ym, xa(co_n), xam(co_n);
                 const std::string rb = v + "resblocks." + std::to_string(i * nk + j);
-                for (int mth = 0; mth < 3; ++mth) {
+                // ResBlock2 (hifigan.py:67-84): two convolutions, the residual added after each; the fp16 operands are leaky_relu(x) in front of both
+                for (int mth = 0; h->resblock2 && mth < 2; ++mth) {
+                    for (int q = 0; q < co_n; ++q) {
+                        pt_wc[pass].push_back(x[q]);
+                        pt_m2[pass].push_back(xm[q]);
+                        xa[q] = x[q];
+                        xam[q] = 0.505 * xm[q];
+                    }
+                    if (!conv(rb + ".convs." + std::to_string(mth), xa, xam, y, ym)) return false;
+                    for (int q = 0; q < co_n; ++q) {
+                        x[q] += y[q];
+                        xm[q] += ym[q];
+                    }
+                }
+                for (int mth = 0; !h->resblock2 && mth < 3; ++mth) {
                     for (int q = 0; q < co_n; ++q) {
                         pt_wc[pass].push_back(x[q]);                             // fp16 operand: leaky_relu(x) (and, iterations 1 / 2, the stored fp16 stream)
                         pt_m2[pass].push_back(xm[q]);
@@ -1024,7 +1042,16 @@ int build_vocoder(dtts_ctx* h) {
     const int nk = c.n_resblock_kernels;
     h->rb1.assign((size_t)c.n_upsamples * nk, {});
     h->rb2.assign((size_t)c.n_upsamples * nk, {});
-    for (int i = 0; ok && i < c.n_upsamples * nk; ++i) {
+    const bool rb2x = h->resblock2;
+    for (int i = 0; ok && rb2x && i < c.n_upsamples * nk; ++i) {   // ResBlock2: convs.{0,1}, both dilated
+        const int j = i % nk, k = c.resblock_kernel_sizes[j];
+        h->rb1[i].resize(2);
+        for (int mth = 0; ok && mth < 2; ++mth) {
+            const int d = c.resblock_dilation_sizes[j][mth];
+            ok = ok && pack_plain(h, need, h->rb1[i][mth], eng_rb, v + "resblocks." + std::to_string(i) + ".convs." + std::to_string(mth), d, 1, (k * d - d) / 2);
+        }
+    }
+    for (int i = 0; ok && !rb2x && i < c.n_upsamples * nk; ++i) {
         const int j = i % nk, k = c.resblock_kernel_sizes[j];
         h->rb1[i].resize(3);
         h->rb2[i].resize(3);
@@ -1039,7 +1066,33 @@ int build_vocoder(dtts_ctx* h) {
     // number of k-steps is a multiple of the register ring depth
     h->rbf1.assign((size_t)c.n_upsamples * nk, {});
     h->rbf2.assign((size_t)c.n_upsamples * nk, {});
-    for (int i = 0; ok && eng_rb != ENG_BF16X3 && i < c.n_upsamples * nk; ++i) {
+    for (int i = 0; ok && rb2x && eng_rb != ENG_BF16X3 && i < c.n_upsamples * nk; ++i) {   // ResBlock2: the fused kernel's packs (rb2x.hip)
+        const int j = i % nk, k = c.resblock_kernel_sizes[j];
+        const int ch = c.upsample_initial_channel >> (i / nk + 1);
+        const int d0 = c.resblock_dilation_sizes[j][0], d1 = c.resblock_dilation_sizes[j][1];
+        if (!rb2x_supported(ch, k, d0, d1) || h->rb1[i][0].C_in_pad != ch || nk < 2) {   // (nk = 1: no stage sum to fold the block into)
+            if (eng_rb == ENG_F16)
+                return fail(h, DTTS_E_INVAL, "DTTS_VOC_F16 needs ResBlock2 widths 32/64/128/256, odd kernels 3..11 and a dilation pair whose halo fits the tile "
+                            "(resblock %d: %d channels, k=%d, dilations (%d, %d)); use DTTS_VOC_BF16X3", i, ch, k, d0, d1);
+            continue;   // bf16: this ResBlock runs convolution by convolution (vconv)
+        }
+        const int kp = rblock_padded_taps(ch, k);
+        h->rbf1[i].resize(2);
+        for (int mth = 0; ok && mth < 2; ++mth) {
+            const std::string base = v + "resblocks." + std::to_string(i) + ".convs." + std::to_string(mth);
+            const HostTensor* w = folded_weight(h, need, base);
+            std::vector<float> bias = bias_of(need, base);
+            if (!w || bias.empty()) { ok = false; break; }
+            const float* pw = w->f.data();
+            PackedConv& L = h->rbf1[i][mth];
+            const int slack = ch >= 64 ? 1 : 2;   // >= 4 zero k-steps behind the last tap: the weight prefetch never clamps
+            ok = pack_conv(h, L, eng_rb, ch, ch, kp + slack,
+                           [=](int co, int ci, int tap) { return tap < k ? pw[((size_t)co * ch + ci) * k + tap] : 0.f; }, bias,
+                           c.resblock_dilation_sizes[j][mth], 1, 0);
+            L.K = k;
+        }
+    }
+    for (int i = 0; ok && !rb2x && eng_rb != ENG_BF16X3 && i < c.n_upsamples * nk; ++i) {
         const int j = i % nk, k = c.resblock_kernel_sizes[j];
         const int ch = c.upsample_initial_channel >> (i / nk + 1);
         if (!rblock_supported(ch, k) || (DTTS_TUNE(h, 8) && ch >= 128)) {   // DTTS_TUNE bit 3: the wide stages' k = 3 ResBlocks per iteration (vpair) again
@@ -1375,6 +1428,7 @@ int hifigan_forward_fused(dtts_ctx* h, const float* mel, const int32_t* lens, in
             ch /= 2;
             // (experiment, tune bit 12) C = 32 only: the first TWO ResBlocks in one launch — the k = 3 launch alone is HBM-bound (x in, stage sum out:
             // 4.6 TB/s), together with k = 7 its bytes ride on that launch's compute; the last ResBlock (fused conv_post) stays on its own
+            if (h->resblock2) continue;   // (stage-fused launches, tune bits 9 / 12, exist for ResBlock1 only)
             if (fuse && DTTS_TUNE(h, 4096) && !DTTS_TUNE(h, 512) && nk == 3 && ch == 32 && !h->rbf1[(size_t)i * nk].empty() && !h->rbf1[(size_t)i * nk + 1].empty()) {
                 int halo2 = 0;   // the launch's halo (rblock.h rblock_halo over its two ResBlocks)
                 for (int j = 0; j < 2; ++j) halo2 = std::max(halo2, rblock_halo_of(h->rbf1[(size_t)i * nk + j][0].K, c.resblock_dilation_sizes[j]));
@@ -1478,6 +1532,10 @@ int hifigan_forward_fused(dtts_ctx* h, const float* mel, const int32_t* lens, in
         for (int j = 0; j < nk; ++j) {
             const auto& c1 = h->rb1[(size_t)i * nk + j];
             const bool fused_rb = fuse && !h->rbf1[(size_t)i * nk + j].empty();
+            if (h->resblock2) {
+                need_xa = need_xa || !fused_rb;
+                continue;
+            }
             const bool fused_vp = fuse && vpair_supported(ch, c1[0].K, c1[0].dil) && vpair_supported(ch, c1[2].K, c1[2].dil) && c1[0].C_in_pad == ch;
             need_xa = need_xa || !(fused_rb || fused_vp);
         }
@@ -1494,7 +1552,74 @@ int hifigan_forward_fused(dtts_ctx* h, const float* mel, const int32_t* lens, in
         }
         Tcur *= u;
         const bool last_stage = i == nup - 1;
-        for (int j = 0; j < nk; ++j) {
+        for (int j = 0; h->resblock2 && j < nk; ++j) {   // ResBlock2 generators
+            const auto& cv = h->rb1[(size_t)i * nk + j];
+            const auto& fv = h->rbf1[(size_t)i * nk + j];
+            if (fuse && !fv.empty()) {   // whole ResBlock2 in one kernel (rb2x.hip); tune bits 9 / 12 / 15 have no meaning here
+                RB2xParams rp;
+                memset(&rp, 0, sizeof rp);
+                rp.x = Xf;
+                rp.S = Sf;
+                rp.lens = lout;
+                rp.B = B;
+                rp.T = Tcur;
+                rp.K = fv[0].K;
+                rp.Kp = rblock_padded_taps(ch, fv[0].K);
+                for (int m = 0; m < 2; ++m) {
+                    rp.w[m] = (const uint4*)fv[m].w_hi;
+                    rp.b[m] = fv[m].bias;
+                    rp.dil[m] = fv[m].dil;
+                }
+                rp.mode = j == 0 ? 0 : (j == nk - 1 ? 2 : 1);
+                rp.div = (float)nk;
+                rp.slope = last_stage ? 0.01f : 0.1f;
+                rp.Sa = exact ? nullptr : Sa;
+                rp.drop_S = exact ? 0 : 1;   // bf16 mode: after a stage only its bf16 leaky_relu copy is consumed (by ups[i+1] / conv_post)
+                if (last_stage && j == nk - 1 && h->post_w) {   // conv_post + tanh in this kernel's epilogue: the stage output stays on chip
+                    rp.wav = wav;
+                    rp.post_w = h->post_w;
+                    rp.post_b = h->post_b;
+                    rp.Sa = nullptr;
+                    post_done = true;
+                }
+                rp.el = el;
+                rp.tile_ctr = (dyn_tiles && n_ctr < N_CTR) ? ctrs + n_ctr++ : nullptr;
+                rp.ovf = (exact && h->guard_on) ? h->ovf_dev : nullptr;
+                rp.bad = h->bad_dev;
+                Timed tm(h, TV, s);
+                LAUNCH(rb2x_launch(rp, ch, s));
+                continue;
+            }
+            if (exact) return fail(h, DTTS_E_STATE, "DTTS_VOC_F16: resblock %d has no fused kernel", i * nk + j);   // build_vocoder rejects such configs
+            for (int m = 0; m < 2; ++m) {   // x = c(leaky_relu(x)) + x, convolution by convolution (vconv)
+                VConvParams p = vparams(cv[m], m == 0 ? Xa : Ra, lout, B, Tcur);
+                p.res = m == 0 ? Xf : Rf;
+                p.ldres = ch;
+                if (m == 0) {
+                    p.yf = Rf;
+                    p.ldyf = ch;
+                    p.ya = Ra;
+                    p.ldya = ch;
+                    p.slope = 0.1f;
+                } else {   // xs (+)= x ; the last resblock also applies / num_kernels and emits the next stage's input
+                    p.yf = Sf;
+                    p.ldyf = ch;
+                    if (j > 0) {
+                        p.res2 = Sf;
+                        p.ldres2 = ch;
+                    }
+                    if (j == nk - 1) {
+                        p.div = (float)nk;
+                        p.ya = Sa;
+                        p.ldya = ch;
+                        p.slope = last_stage ? 0.01f : 0.1f;  // F.leaky_relu default before conv_post (hifigan.py:138)
+                    }
+                }
+                Timed tm(h, TV, s);
+                LAUNCH(vconv_launch(p, s));
+            }
+        }
+        for (int j = 0; !h->resblock2 && j < nk; ++j) {
             const auto& c1 = h->rb1[(size_t)i * nk + j];
             const auto& c2 = h->rb2[(size_t)i * nk + j];
             if (fuse && !h->rbf1[(size_t)i * nk + j].empty()) {   // whole ResBlock in one kernel (rblock.hip)
@@ -1763,6 +1888,21 @@ int dtts_create(const dtts_config* cfg, dtts_handle* out) {
                  "-DDTTS_ABLATE builds)", (unsigned)cfg->tune_flags, (unsigned)TUNE_MASK);
         return fail(nullptr, DTTS_E_INVAL, "%s", msg);
     }
+    // the block type of the generator is encoded in the dilation rows (include/dicttts_hip.h): a third entry of 0 = a two-dilation
+    // (ResBlock2) row.  All used rows are of one kind
+    if (cfg->n_resblock_kernels >= 0 && cfg->n_resblock_kernels <= 4) {
+        int two = 0;
+        for (int j = 0; j < cfg->n_resblock_kernels; ++j) {
+            const int32_t* d = cfg->resblock_dilation_sizes[j];
+            if (d[0] < 1 || d[1] < 1 || d[2] < 0)
+                return fail(nullptr, DTTS_E_INVAL, "dtts_create: resblock_dilation_sizes[%d] = (%d, %d, %d): the first two dilations must be >= 1, the third >= 1 (ResBlock1) or 0 (ResBlock2)",
+                            j, (int)d[0], (int)d[1], (int)d[2]);
+            two += d[2] == 0 ? 1 : 0;
+        }
+        if (two != 0 && two != cfg->n_resblock_kernels)
+            return fail(nullptr, DTTS_E_INVAL, "dtts_create: resblock_dilation_sizes mixes two-dilation (ResBlock2, third entry 0) and three-dilation (ResBlock1) rows: "
+                        "%d of %d rows have a third entry of 0", two, (int)cfg->n_resblock_kernels);
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(nullptr, DTTS_E_HIP, "dtts_create: no HIP device visible (the HIP path has no CPU fallback)");
@@ -1788,6 +1928,7 @@ int dtts_create(const dtts_config* cfg, dtts_handle* out) {
         h->noise_seed = z ^ (z >> 31);
     }
     h->guard_on = cfg->vocoder_range_guard != 0;
+    h->resblock2 = cfg->n_resblock_kernels > 0 && cfg->resblock_dilation_sizes[0][2] == 0;
     (void)hipGetDevice(&h->device);
     if (hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || h->n_cu <= 0) h->n_cu = 256;
     h->debug_rz = cfg->debug_redzone != 0;
@@ -2065,6 +2206,24 @@ int dtts_hifigan_forward(dtts_handle h, const float* mel, const int32_t* lens, i
         Tcur *= u;
         for (int j = 0; j < nk; ++j) {
             const auto& c1 = h->rb1[(size_t)i * nk + j];
+            for (int m = 0; h->resblock2 && m < 2; ++m) {   // ResBlock2: x = c(leaky_relu(x)) + x ; the second one also folds xs (+)= x and / num_kernels
+                const bool last = m == 1;
+                const float* xin = m == 0 ? bufX : bufR;
+                ConvParams p = base_params(xin, ch, B, Tcur, Tcur, last ? bufS : bufR, ch);
+                p.in_lens = lout;
+                p.out_lens = lout;
+                p.pre_act = 1;
+                p.pre_slope = 0.1f;
+                set_res(p, 0, xin, ch);
+                if (last && j > 0) {
+                    p.seg[0].res2 = bufS;
+                    p.seg[0].ld_res2 = ch;
+                }
+                if (last && j == nk - 1) p.out_div = (float)nk;
+                Timed tm(h, TV, s);
+                LAUNCH(conv1d_launch(c1[m], p, s));
+            }
+            if (h->resblock2) continue;
             const auto& c2 = h->rb2[(size_t)i * nk + j];
             for (int mth = 0; mth < 3; ++mth) {
                 const float* xin = mth == 0 ? bufX : bufR;

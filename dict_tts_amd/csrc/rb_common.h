@@ -1,4 +1,4 @@
-// Shared device helpers of the fused HifiGAN kernels (rblock.hip, vpair.hip): bf16 conversion, the weight-fragment
+// Shared device helpers of the fused HifiGAN kernels (rblock.hip, vpair.hip, rb2x.hip): bf16 conversion, the weight-fragment
 // ring preload and the static-offset MFMA contraction loop over an LDS activation tile.
 #pragma once
 // Cache policy of the fused vocoder kernels' global accesses (buffer-instruction aux bits on gfx950: 1 = sc0, 2 = nt, 16 = sc1).

@@ -94,6 +94,13 @@ BIAOBEI_DEFAULTS = {
     "vocoder": "dict_tts_amd.vocoder.HifiGAN", "vocoder_ckpt": "", "use_word_input": True, "use_dict": True,
 }
 
+# the light "V3" generator of the original HifiGAN release (config_v3.json): ResBlock2, three upsamplers, hop 256
+HIFIGAN_V3 = {
+    "resblock": "2", "upsample_rates": [8, 8, 4], "upsample_kernel_sizes": [16, 16, 8],
+    "upsample_initial_channel": 256, "resblock_kernel_sizes": [3, 5, 7],
+    "resblock_dilation_sizes": [[1, 2], [2, 6], [3, 12]],
+}
+
 HIFIGAN_DEFAULTS = {
     "resblock": "1", "upsample_rates": [8, 8, 2, 2], "upsample_kernel_sizes": [16, 16, 4, 4],
     "upsample_initial_channel": 512, "resblock_kernel_sizes": [3, 7, 11],
@@ -133,8 +140,11 @@ def fill_abi_config(cfg, hp=None, voc=None, n_phone=None, vocoder_precision=None
     if n_phone is not None:
         cfg.n_phone = int(n_phone)
     if voc is not None:
-        if str(voc.get("resblock", "1")) != "1":
-            raise NotImplementedError("only ResBlock1 generators are implemented (hifigan.yaml: resblock '1')")
+        # modules/hifigan/hifigan.py:109: ResBlock1 if h['resblock'] == '1' else ResBlock2 (YAML / JSON deliver a string or an int)
+        resblock = str(voc.get("resblock", "1")).strip()
+        if resblock not in ("1", "2"):
+            raise NotImplementedError(f"resblock={voc.get('resblock')!r}: the generator's 'resblock' is '1' (ResBlock1) or '2' (ResBlock2)")
+        n_dil = 3 if resblock == "1" else 2
         ur, uk = list(voc["upsample_rates"]), list(voc["upsample_kernel_sizes"])
         rk, rd = list(voc["resblock_kernel_sizes"]), [list(d) for d in voc["resblock_dilation_sizes"]]
         cfg.upsample_initial_channel = int(voc["upsample_initial_channel"])
@@ -145,10 +155,14 @@ def fill_abi_config(cfg, hp=None, voc=None, n_phone=None, vocoder_precision=None
         cfg.n_resblock_kernels = len(rk)
         for i in range(len(rk)):
             cfg.resblock_kernel_sizes[i] = int(rk[i])
-            if len(rd[i]) != 3:
-                raise NotImplementedError("ResBlock1 expects 3 dilations per kernel size")
+            if len(rd[i]) != n_dil:
+                raise NotImplementedError(f"resblock_dilation_sizes[{i}] = {rd[i]}: resblock '{resblock}' (ResBlock{resblock}) expects exactly "
+                                          f"{n_dil} dilations per kernel size")
+            if any(int(d) < 1 for d in rd[i]):
+                raise ValueError(f"resblock_dilation_sizes[{i}] = {rd[i]}: dilations must be >= 1")
+            # the struct has no block-type field: a row whose third entry is 0 is a two-dilation (ResBlock2) row (include/dicttts_hip.h)
             for j in range(3):
-                cfg.resblock_dilation_sizes[i][j] = int(rd[i][j])
+                cfg.resblock_dilation_sizes[i][j] = int(rd[i][j]) if j < n_dil else 0
     if vocoder_precision is not None:
         cfg.vocoder_precision = int(vocoder_precision)
     # A/B switches of tuning experiments (include/dicttts_hip.h: dtts_config.tune_flags; 0 = the measured defaults).  An explicit

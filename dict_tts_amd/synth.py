@@ -210,6 +210,14 @@ def hifigan_config():
             "resblock_dilation_sizes": [[1, 3, 5], [1, 3, 5], [1, 3, 5]]}
 
 
+def hifigan_config_v3():
+    """the light "V3" generator of the original HifiGAN release (config_v3.json): ``resblock: "2"`` (ResBlock2,
+    modules/hifigan/hifigan.py:61-89), three upsamplers (hop 256), stage widths 128 / 64 / 32"""
+    return {"resblock": "2", "upsample_rates": [8, 8, 4], "upsample_kernel_sizes": [16, 16, 8],
+            "upsample_initial_channel": 256, "resblock_kernel_sizes": [3, 5, 7],
+            "resblock_dilation_sizes": [[1, 2], [2, 6], [3, 12]]}
+
+
 def hifigan_state_dict(seed=1234, weight_norm=True, cfg=None):
     """numpy state dict of ``HifiGanGenerator`` (``state_dict.model_gen``), weight-norm form by default."""
     cfg = cfg or hifigan_config()
@@ -229,8 +237,13 @@ def hifigan_state_dict(seed=1234, weight_norm=True, cfg=None):
             nrm = np.sqrt((v.reshape(v.shape[0], -1) ** 2).sum(1)).reshape(-1, 1, 1)
             sd[f"ups.{i}.weight_g"] = (nrm / 1.7 * (1.0 + 0.1 * randn(seed, f"ups.{i}.g", (v.shape[0], 1, 1)))
                                         ).astype(np.float32)
+        nk = len(cfg["resblock_kernel_sizes"])
         for j, kk in enumerate(cfg["resblock_kernel_sizes"]):
-            r = f"resblocks.{i * 3 + j}"
+            r = f"resblocks.{i * nk + j}"
+            if str(cfg.get("resblock", "1")) == "2":   # ResBlock2 (modules/hifigan/hifigan.py:62-66): convs.{0,1}
+                for m in range(len(cfg["resblock_dilation_sizes"][j])):
+                    _conv(sd, seed, f"{r}.convs.{m}", ch, ch, kk, gain=1.0, wn=weight_norm)
+                continue
             for m in range(3):
                 _conv(sd, seed, f"{r}.convs1.{m}", ch, ch, kk, gain=1.0, wn=weight_norm)
                 _conv(sd, seed, f"{r}.convs2.{m}", ch, ch, kk, gain=0.6, wn=weight_norm)

@@ -93,6 +93,15 @@ typedef struct dtts_config {
     int32_t upsample_kernel_sizes[8]; /* 16,16,4,4 */
     int32_t n_resblock_kernels;       /* 3   */
     int32_t resblock_kernel_sizes[4]; /* 3,7,11 */
+    /* One row per resblock kernel size.  The block type of the generator (modules/hifigan/hifigan.py:109, config key `resblock`) is
+     * encoded in the rows: three dilations >= 1 = ResBlock1 (`resblock: "1"`, state-dict names resblocks.N.convs1.M / convs2.M);
+     * a row whose THIRD entry is 0 is a two-dilation row = ResBlock2 (`resblock: "2"`, the V3 family: (d0, d1, 0), names
+     * resblocks.N.convs.{0,1}).  All used rows are of one kind and the first two dilations are >= 1, else dtts_create fails with
+     * DTTS_E_INVAL.  DTTS_VOC_F16 / DTTS_VOC_BF16 run a ResBlock2 as one fused launch for widths 32 / 64 / 128 / 256, odd kernels
+     * 3..11 and every pair (d0, d1) whose halo (K - 1) / 2 * (d0 + d1) leaves at least 32 output rows in a tile of 512 / 512 / 256 /
+     * 128 rows within the LDS (dict_tts_amd/csrc/rb2x.h: rb2x_supported); other shapes run convolution by convolution in
+     * DTTS_VOC_BF16 and DTTS_VOC_BF16X3 and are refused by dtts_finalize_weights in DTTS_VOC_F16.  tune_flags bits 9 / 12 / 14 / 15
+     * concern ResBlock1 kernels only and do not change a ResBlock2 result. */
     int32_t resblock_dilation_sizes[4][3]; /* (1,3,5) x3 */
     int32_t vocoder_precision;        /* DTTS_VOC_F16 (default) | DTTS_VOC_BF16 | DTTS_VOC_BF16X3 */
     /* FFT block stack (FFTBlocks, modules/fastspeech/tts_modules.py:458-493); width = hidden_size, heads = num_heads */

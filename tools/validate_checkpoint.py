@@ -59,6 +59,9 @@ def operand_peaks(fsd, cfg, mel_T80):
                 p, r = f"resblocks.{i * nk + j}", x
                 for m, d in enumerate(rd):
                     peak = max(peak, float(r.abs().max()))
+                    if str(cfg.get("resblock", "1")) == "2":   # ResBlock2 (hifigan.py:67-84): one dilated convolution per iteration, the operand is x
+                        r = F.conv1d(F.leaky_relu(r, L), fsd[f"{p}.convs.{m}.weight"], fsd[f"{p}.convs.{m}.bias"], padding=href._pad(rk, d), dilation=d) + r
+                        continue
                     xt = F.conv1d(F.leaky_relu(r, L), fsd[f"{p}.convs1.{m}.weight"], fsd[f"{p}.convs1.{m}.bias"], padding=href._pad(rk, d), dilation=d)
                     peak = max(peak, float(xt.abs().max()))
                     r = F.conv1d(F.leaky_relu(xt, L), fsd[f"{p}.convs2.{m}.weight"], fsd[f"{p}.convs2.{m}.bias"], padding=href._pad(rk, 1)) + r
@@ -67,10 +70,34 @@ def operand_peaks(fsd, cfg, mel_T80):
     return peak
 
 
+def oracle_spec2wav(fsd, cfg, mel_T80):
+    """the CPU fp32 oracle: oracle/hifigan_ref.py for ResBlock1 generators; for ``resblock: "2"`` the same forward with the ResBlock2
+    body (modules/hifigan/hifigan.py:67-84: x = c(leaky_relu(x, 0.1)) + x for the two dilated convolutions)"""
+    if str(cfg.get("resblock", "1")) != "2":
+        return href.spec2wav(fsd, cfg, mel_T80).numpy()
+    L = href.LRELU_SLOPE
+    with torch.no_grad():
+        x = torch.as_tensor(mel_T80, dtype=torch.float32).unsqueeze(0).transpose(2, 1)
+        x = F.conv1d(x, fsd["conv_pre.weight"], fsd["conv_pre.bias"], padding=3)
+        nk = len(cfg["resblock_kernel_sizes"])
+        for i, (u, k) in enumerate(zip(cfg["upsample_rates"], cfg["upsample_kernel_sizes"])):
+            x = F.conv_transpose1d(F.leaky_relu(x, L), fsd[f"ups.{i}.weight"], fsd[f"ups.{i}.bias"], stride=u, padding=(k - u) // 2)
+            xs = None
+            for j, (rk, rd) in enumerate(zip(cfg["resblock_kernel_sizes"], cfg["resblock_dilation_sizes"])):
+                p, r = f"resblocks.{i * nk + j}", x
+                for m, d in enumerate(rd):
+                    r = F.conv1d(F.leaky_relu(r, L), fsd[f"{p}.convs.{m}.weight"], fsd[f"{p}.convs.{m}.bias"], padding=href._pad(rk, d), dilation=d) + r
+                xs = r if xs is None else xs + r
+            x = xs / nk
+        x = F.conv1d(F.leaky_relu(x), fsd["conv_post.weight"], fsd["conv_post.bias"], padding=3)
+        return torch.tanh(x).view(-1).numpy()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("ckpt_dir", nargs="?", help="vocoder checkpoint directory (vocoders/hifigan.py:16-52 discovery rule)")
     ap.add_argument("--synthetic", action="store_true", help="the repo's seeded synthetic generator instead of a checkpoint")
+    ap.add_argument("--v3", action="store_true", help="(with --synthetic) the V3 ResBlock2 generator (synth.hifigan_config_v3)")
     ap.add_argument("--scale-resblocks", type=float, default=1.0, help="(with --synthetic) multiply every ResBlock weight_g: moves the checkpoint across the margin")
     ap.add_argument("--mels", type=int, default=16, help="synthetic mels to run when no --mel-npy is given")
     ap.add_argument("--frames", type=int, default=200)
@@ -81,8 +108,8 @@ def main():
         sys.exit("validate_checkpoint.py needs a ROCm GPU (the HIP path has no CPU fallback)")
     T_ = lambda x: torch.from_numpy(np.ascontiguousarray(x))
     if a.synthetic:
-        cfg = synth.hifigan_config()
-        sd = {k: T_(v) for k, v in synth.hifigan_state_dict(1234).items()}
+        cfg = synth.hifigan_config_v3() if a.v3 else synth.hifigan_config()
+        sd = {k: T_(v) for k, v in synth.hifigan_state_dict(1234, cfg=cfg).items()}
         if a.scale_resblocks != 1.0:
             sd = {k: (v * a.scale_resblocks if k.startswith("resblocks.") and k.endswith("weight_g") else v) for k, v in sd.items()}
         src = f"synthetic generator (seed 1234, ResBlock gains x{a.scale_resblocks:g})"
@@ -139,7 +166,8 @@ def main():
             clamped += g.ctx.vocoder_clamped(s)
         torch.cuda.synchronize()
         bad = int(g.ctx.vocoder_nonfinite())
-        print(f"   fp16: {clamped} activations beyond the fp16 range (72 conversion points x every output row), detector count {bad}")
+        n_points = len(full_cfg["upsample_rates"]) * len(full_cfg["resblock_kernel_sizes"]) * (2 if str(full_cfg.get("resblock", "1")) == "2" else 6)
+        print(f"   fp16: {clamped} activations beyond the fp16 range ({n_points} conversion points x every output row), detector count {bad}")
 
     print(f"\n4. waveform gate against the oracle (first {a.gate} mels): RMS(gpu - ref) <= 1e-4 and |RMS(gpu) - RMS(ref)| <= 1e-4")
     gate = {}
@@ -149,7 +177,7 @@ def main():
         worst = (0.0, 0.0)
         ok = True
         for m in mels[:a.gate]:
-            ref = href.spec2wav(fsd, full_cfg, m).numpy()
+            ref = oracle_spec2wav(fsd, full_cfg, m)
             try:
                 w = v.forward_batch(T_(m[None]).cuda()).view(-1).cpu().numpy()
             except abi.DttsError as e:
