@@ -17,7 +17,6 @@
 #include <vector>
 
 #include "../../include/dicttts_hip.h"
-#include "tune_env.h"
 #include "conv1d.h"
 #include "ops.h"
 #include "vconv.h"
@@ -27,6 +26,14 @@
 #include "flowstack.h"
 
 using namespace dtts;
+
+// dtts_config.tune_flags (include/dicttts_hip.h).  The library honours only the bits that have a parity / bit-identity test behind them
+// (tests/test_gpu_parity.py): 8 prior flow launch by launch on the exact-fp32 kernels, 9 all ResBlocks of a C <= 64 stage in one launch,
+// 12 the first two ResBlocks of the C = 32 stage in one launch, 13 two-product fp16 ups.1, 14 512-row tiles for every k at C = 64, 15 the fp32
+// inter-iteration stream of the per-iteration ResBlock kernels (round 5's form; default since round 6: fp16).  dtts_create REJECTS every
+// other bit (DTTS_E_INVAL) instead of ignoring it.
+constexpr int TUNE_RELEASE_MASK = (1 << 8) | (1 << 9) | (1 << 12) | (1 << 13) | (1 << 14) | (1 << 15);
+#define DTTS_TUNE(h, bit) (((h)->tune & (bit)) != 0)
 
 namespace {
 
@@ -193,7 +200,6 @@ struct dtts_ctx {
     int t_entries = 0;
     int *t_off = nullptr, *t_poff = nullptr, *t_pmmax = nullptr;
     float *t_keys = nullptr, *t_values = nullptr, *t_key_map = nullptr;
-    bool t_projected = false;   // t_keys / t_values hold K = key Wk^T and V = value Wv^T (hidden_size wide) instead of the raw gloss rows
     int64_t *t_pinyin = nullptr, *t_pinyin_map = nullptr;
     // ---- speaker conditioning (dtts_text2mel_speakers; modules/portaspeech/model.py:159-163, modules/dict_tts/model.py:44-45,94-96)
     int spk_kind = 0;                        // 0 = no spk_embed_proj loaded, DTTS_SPK_EMBED (Linear 256 -> hidden), DTTS_SPK_ID (Embedding)
@@ -368,7 +374,7 @@ bool pack_conv(dtts_ctx* h, PackedConv& L, int engine, int C_out, int C_in, int 
     if (engine == ENG_F32) {
         L.w_hi = upload(h, wf);
         // + the same weights as three bf16 pieces in k-groups of 16 (conv1d.h: ENG_BF16X6) for the short-sequence kernel
-        if (!DTTS_TUNE(h, 131072) && L.C_in_pad % 16 == 0) {   // DTTS_TUNE bit 17: fp32 MFMA only
+        if (L.C_in_pad % 16 == 0) {
             const int KG6 = 16, E6 = 8, NG6 = L.C_in_pad / KG6;
             std::vector<uint16_t> pc[3];
             for (auto& v : pc) v.assign(n, 0);
@@ -497,7 +503,7 @@ bool pack_transposed(dtts_ctx* h, Need& need, PackedConv& L, int engine, const s
             return (j >= 0 && j < k) ? pw[((size_t)ci * C_out + co) * k + j] : 0.f;
         },
         bias, 1, 1, pad, 0, 2.0 * C_in * C_out * k /* per INPUT row: u outputs x k/u taps */);
-    L.poly_half = (half && !DTTS_TUNE(h, 2)) ? 1 : 0;
+    L.poly_half = half ? 1 : 0;
     return ok;
 }
 
@@ -748,13 +754,12 @@ int build_acoustic(dtts_ctx* h) {
     h->dur_bias = upload_named(h, need, m + "dur_predictor.linear.0.bias");
     ok = ok && h->dur_w && h->dur_bias;
     // FVAE
-    ok = ok && pack_plain(h, need, h->g_pre, (c.decoder_fp32 || DTTS_TUNE(h, 1024)) ? ENG_F32 : ENG_BF16X3, m + "fvae.g_pre_net.0", 1, 4, 2);   // DTTS_TUNE bit 10: fp32 (round 2)
+    ok = ok && pack_plain(h, need, h->g_pre, c.decoder_fp32 ? ENG_F32 : ENG_BF16X3, m + "fvae.g_pre_net.0", 1, 4, 2);
     // g_pre_net = Conv1d(k = 8, stride 4, pad 2) as a STRIDE-1, 3-tap convolution over 4-frame groups: [B][T][C] is also [B][T/4][4C]
     // (T is a multiple of frames_multiple = 4), out[q] = sum_j W_j x[4q + j - 2] reads group q - 1 (frames 2, 3), q (all four) and q + 1
     // (frames 0, 1) — on the split-operand vconv kernel, which skips the two all-zero half taps per input chunk (vconv.hip: in_half).
-    // DTTS_TUNE bit 16: the strided form on the generic kernel.
     h->g_pre_poly = PackedConv();
-    if (ok && !c.decoder_fp32 && !DTTS_TUNE(h, 1024) && !DTTS_TUNE(h, 65536) && c.frames_multiple == 4 && c.hidden_size % 64 == 0) {
+    if (ok && !c.decoder_fp32 && c.frames_multiple == 4 && c.hidden_size % 64 == 0) {
         const HostTensor* wg = folded_weight(h, need, m + "fvae.g_pre_net.0");
         std::vector<float> bg = bias_of(need, m + "fvae.g_pre_net.0");
         if (wg && wg->shape.size() == 3 && wg->shape[2] == 8 && !bg.empty()) {
@@ -843,7 +848,7 @@ int build_acoustic(dtts_ctx* h) {
         const int n_c = (int)fs_cond_b.size(), Cg = c.hidden_size;
         const float* pc = fs_cond_w.data();
         // (split-bf16 operands on the vconv kernel like the WaveNet layers it conditions, unless the exact-fp32 decoder was asked for)
-        ok = ok && h->fs_w && pack_conv(h, h->fs_cond, (c.decoder_fp32 || Cg % 64 || n_c % 256 || DTTS_TUNE(h, 2048)) ? ENG_F32 : ENG_BF16X3, n_c, Cg, 1,
+        ok = ok && h->fs_w && pack_conv(h, h->fs_cond, (c.decoder_fp32 || Cg % 64 || n_c % 256) ? ENG_F32 : ENG_BF16X3, n_c, Cg, 1,
                                          [=](int co, int ci, int) { return pc[(size_t)co * Cg + ci]; }, fs_cond_b, 1, 1, 0);
     }
     ok = ok && pack_transposed(h, need, h->dec_pre, ENG_F32, m + "fvae.decoder.pre_net.0", 4, 0);
@@ -1095,7 +1100,7 @@ int build_vocoder(dtts_ctx* h) {
     for (int i = 0; ok && !rb2x && eng_rb != ENG_BF16X3 && i < c.n_upsamples * nk; ++i) {
         const int j = i % nk, k = c.resblock_kernel_sizes[j];
         const int ch = c.upsample_initial_channel >> (i / nk + 1);
-        if (!rblock_supported(ch, k) || (DTTS_TUNE(h, 8) && ch >= 128)) {   // DTTS_TUNE bit 3: the wide stages' k = 3 ResBlocks per iteration (vpair) again
+        if (!rblock_supported(ch, k)) {
             bool vp = h->rb1[i][0].C_in_pad == ch;
             for (int mth = 0; mth < 3; ++mth) vp = vp && vpair_supported(ch, k, c.resblock_dilation_sizes[j][mth]);
             if (eng_rb == ENG_F16 && !vp)
@@ -1130,7 +1135,7 @@ int build_vocoder(dtts_ctx* h) {
         bool fusable = ok && eng_rb != ENG_BF16X3 && last_ch == 32 && w && w->shape.size() == 3 && w->shape[0] == 1 && w->shape[1] == 32 &&
                        w->shape[2] == 7 && b.size() == 1 && nk >= 2;
         for (int j = 0; fusable && j < nk; ++j) fusable = !h->rbf1[(size_t)(c.n_upsamples - 1) * nk + j].empty();
-        if (fusable && !DTTS_TUNE(h, 1)) {
+        if (fusable) {
             std::vector<float> wt((size_t)7 * 32);
             for (int ci = 0; ci < 32; ++ci)
                 for (int k = 0; k < 7; ++k) wt[(size_t)k * 32 + ci] = w->f[(size_t)ci * 7 + k];
@@ -1151,13 +1156,6 @@ int build_vocoder(dtts_ctx* h) {
 
 // ---------------------------------------------------------------------------------------------------------
 // vconv parameter blocks (vocoder convolutions and the decoder's split-operand WaveNet layers)
-// -DDTTS_ABLATE builds: phase-ablation bits for the vocoder kernels, read ONCE when the library is loaded (never per launch)
-#ifdef DTTS_ABLATE
-static const int g_ablate = ablate_env("DTTS_VCONV_DBG") ? atoi(ablate_env("DTTS_VCONV_DBG")) : 0;
-#else
-constexpr int g_ablate = 0;
-#endif
-
 VConvParams vparams(const PackedConv& L, const unsigned short* x, const int* lens, int B, int T) {
     VConvParams p;
     memset(&p, 0, sizeof p);
@@ -1179,7 +1177,6 @@ VConvParams vparams(const PackedConv& L, const unsigned short* x, const int* len
     p.in_slope = 1.f;
     p.C_in = L.C_in;
     p.poly_half = L.poly_half;
-    p.dbg = g_ablate & 15;
     return p;
 }
 // waveform-exact form: fp32 input [B][T][ld] (leaky_relu(in_slope) applied while staging), hi/lo split operands
@@ -1473,8 +1470,7 @@ int hifigan_forward_fused(dtts_ctx* h, const float* mel, const int32_t* lens, in
     unsigned* ctrs = A.alloc<unsigned>(N_CTR);
     int n_ctr = 0;
     if (!Xf || !Rf || !Sf || !Rg || !Xa || !Ra || !Ta || !Sa || !melb || !lensS || !ctrs) return fail(h, DTTS_E_NOMEM, "vocoder workspace");
-    const bool dyn_tiles = !DTTS_TUNE(h, 4);   // DTTS_TUNE bit 2: static tile assignment (round 2)
-    if (dyn_tiles) HIPCHK(hipMemsetAsync(ctrs, 0, N_CTR * sizeof(unsigned), s));
+    HIPCHK(hipMemsetAsync(ctrs, 0, N_CTR * sizeof(unsigned), s));
     {
         StageMult mult;
         mult.m[0] = 1;
@@ -1489,8 +1485,8 @@ int hifigan_forward_fused(dtts_ctx* h, const float* mel, const int32_t* lens, in
     } else if (lens) HIPCHK(hipMemsetAsync(wav, 0, (size_t)B * T * h->hop * sizeof(float), s));
     const int TV = DTTS_TIMER_VOC_CONV;
     // The family's launches are consecutive on the stream (nothing else runs between conv_pre and the last ResBlock / conv_post): ONE
-    // hipEvent pair per forward spans them all — the per-launch pairs of round 2 put 50 event packets between the kernels of every forward
-    // (DTTS_TUNE bit 4 brings them back).  The span includes the kernel boundaries; launches are still counted one by one.
+    // hipEvent pair per forward spans them all — the per-launch pairs of round 2 put 50 event packets between the kernels of every forward.
+    // The span includes the kernel boundaries; launches are still counted one by one.
     struct SpanGuard {
         dtts_ctx* h;
         Timed* t;
@@ -1499,7 +1495,7 @@ int hifigan_forward_fused(dtts_ctx* h, const float* mel, const int32_t* lens, in
             delete t;   // closes the span (records the end event)
         }
     } span{h, nullptr};
-    if (h->timers[TV].enabled && !DTTS_TUNE(h, 16)) {
+    if (h->timers[TV].enabled) {
         span.t = new Timed(h, TV, s);
         if (span.t->e1) h->timers[TV].launches -= 1;   // (the span itself is not a launch; e1 is null when no event could be created)
         h->voc_span = true;
@@ -1541,7 +1537,7 @@ int hifigan_forward_fused(dtts_ctx* h, const float* mel, const int32_t* lens, in
         }
         {   // ups[i] (polyphase): Sa [B,Tcur,2ch] -> Xf / Xa [B,Tcur,u*ch] == [B,Tcur*u,ch]
             VConvParams p = exact ? vparams_x3(h->ups[i], Sf, 2 * ch, 0.1f, lin, B, Tcur) : vparams(h->ups[i], Sa, lin, B, Tcur);
-            p.small_tiles = exact && !DTTS_TUNE(h, 32);   // narrow split-operand upsamplers: 64-row tiles, 4 workgroups / CU (-0.15 ms same-box)
+            p.small_tiles = exact;   // narrow split-operand upsamplers: 64-row tiles, 4 workgroups / CU (-0.15 ms same-box)
             p.yf = Xf;
             p.ldyf = u * ch;
             p.ya = need_xa ? Xa : nullptr;
@@ -1583,7 +1579,7 @@ int hifigan_forward_fused(dtts_ctx* h, const float* mel, const int32_t* lens, in
                     post_done = true;
                 }
                 rp.el = el;
-                rp.tile_ctr = (dyn_tiles && n_ctr < N_CTR) ? ctrs + n_ctr++ : nullptr;
+                rp.tile_ctr = n_ctr < N_CTR ? ctrs + n_ctr++ : nullptr;
                 rp.ovf = (exact && h->guard_on) ? h->ovf_dev : nullptr;
                 rp.bad = h->bad_dev;
                 Timed tm(h, TV, s);
@@ -1674,38 +1670,13 @@ int hifigan_forward_fused(dtts_ctx* h, const float* mel, const int32_t* lens, in
                     if (stage_fused) rp.s_private = (int)std::min<size_t>(s_cap_bytes, (size_t)INT_MAX);   // one private strip of S per tile (the tiles overlap)
                 }
                 rp.el = el;
-                rp.tile_ctr = (dyn_tiles && n_ctr < N_CTR) ? ctrs + n_ctr++ : nullptr;
+                rp.tile_ctr = n_ctr < N_CTR ? ctrs + n_ctr++ : nullptr;
                 rp.ovf = (exact && h->guard_on) ? h->ovf_dev : nullptr;
                 rp.bad = h->bad_dev;
                 rp.small_tile = DTTS_TUNE(h, 16384) ? 1 : 0;
-                rp.pingpong = DTTS_TUNE(h, 128) ? 1 : 0;   // tune bit 7 (-DDTTS_ABLATE builds only): the two-group form of rblock2.hip (experiment)
-                rp.dbg = (g_ablate >> 4) & 15;
                 if (nk == 1) return fail(h, DTTS_E_INVAL, "fused ResBlock path needs >= 2 resblock kernels");
-#ifdef DTTS_ABLATE
-                static unsigned long long* rstats = nullptr;
-                if (ablate_env("DTTS_RB_STATS")) {   // per-phase cycle sums of rblock2's two groups, printed per launch
-                    if (!rstats) hipMalloc((void**)&rstats, 18 * sizeof(unsigned long long));
-                    hipMemsetAsync(rstats, 0, 18 * sizeof(unsigned long long), s);
-                    rp.stats = rstats;
-                }
-#endif
-                {
-                    Timed tm(h, TV, s);
-                    LAUNCH(rblock_launch(rp, ch, s));
-                }
-#ifdef DTTS_ABLATE
-                if (rp.stats) {
-                    unsigned long long hs[18];
-                    hipStreamSynchronize(s);
-                    hipMemcpy(hs, rp.stats, sizeof hs, hipMemcpyDeviceToHost);
-                    for (int g = 0; g < 2 && hs[8]; ++g) {
-                        const double n = hs[g * 9 + 8] ? (double)hs[g * 9 + 8] : 1.0;
-                        const unsigned long long* a = hs + g * 9;
-                        fprintf(stderr, "rblock2 C=%d K=%d grp %d tiles=%llu cycles/tile: write_x %.0f  bar_after_N %.0f  conv1 %.0f  bar_after_M %.0f  rewrite_xt %.0f  conv2 %.0f  rewrite_x %.0f  epilogue %.0f\n",
-                                ch, rp.K, g, a[8], a[0] / n, a[1] / n, a[2] / n, a[3] / n, a[4] / n, a[5] / n, a[6] / n, a[7] / n);
-                    }
-                }
-#endif
+                Timed tm(h, TV, s);
+                LAUNCH(rblock_launch(rp, ch, s));
                 continue;
             }
             if (fuse && vpair_supported(ch, c1[0].K, c1[0].dil) && vpair_supported(ch, c1[2].K, c1[2].dil) && c1[0].C_in_pad == ch) {
@@ -1727,29 +1698,17 @@ int hifigan_forward_fused(dtts_ctx* h, const float* mel, const int32_t* lens, in
                     vp.div = (float)nk;
                     vp.slope = last_stage ? 0.01f : 0.1f;
                     vp.el = el;
-                    vp.tile_ctr = (dyn_tiles && n_ctr < N_CTR) ? ctrs + n_ctr++ : nullptr;
+                    vp.tile_ctr = n_ctr < N_CTR ? ctrs + n_ctr++ : nullptr;
                     vp.ovf = (exact && h->guard_on) ? h->ovf_dev : nullptr;
-                    vp.dbg = g_ablate >> 8;
-#ifdef DTTS_ABLATE
-                    if (ablate_env("DTTS_VP_STATS")) {   // per-phase cycles of wave 0 (staging, c1, rewrite, c2, epilogue incl. store acks), printed per launch
-                        static unsigned long long* dstats = nullptr;
-                        if (!dstats) hipMalloc((void**)&dstats, 64);
-                        hipMemsetAsync(dstats, 0, 64, s);
-                        vp.stats = dstats;
-                    }
-#endif
                     // round 6: the stream BETWEEN the three iterations is fp16 (DTTS_VOC_F16 only; tune bit 15: fp32 as in round 5).  fp16(x) is what the
                     // next iteration's convolution operand was anyway; the residual add sees the rounded value (tools/precision_sim.py --stream:
                     // waveform error 5.3e-5 -> 6.7e-5, gate 1e-4).  The ResBlock's RESULT (iteration 2) stays fp32.
                     const bool s16 = exact && !DTTS_TUNE(h, 32768);
-                    // (ablation builds: DTTS_S16 = mask of the hops that are 16-bit — bit 2 i: iteration 0 -> 1 of stage i, bit 2 i + 1: iteration 1 -> 2)
-                    static const int s16m = ablate_env("DTTS_S16") ? atoi(ablate_env("DTTS_S16")) : ~0;
-                    const bool hop_a = s16 && ((s16m >> (2 * i)) & 1), hop_b = s16 && ((s16m >> (2 * i + 1)) & 1);
-                    vp.x16 = (mth == 1 ? hop_a : (mth == 2 ? hop_b : false)) ? 1 : 0;
+                    vp.x16 = (s16 && mth > 0) ? 1 : 0;
                     if (mth < 2) {
                         vp.y = mth == 0 ? Rf : Rg;
                         vp.mode = 1;
-                        vp.y16 = (mth == 0 ? hop_a : hop_b) ? 1 : 0;
+                        vp.y16 = s16 ? 1 : 0;
                     } else {
                         vp.y = Sf;
                         vp.mode = j == 0 ? 1 : (j == nk - 1 ? 3 : 2);
@@ -1759,16 +1718,6 @@ int hifigan_forward_fused(dtts_ctx* h, const float* mel, const int32_t* lens, in
                     xin = vp.y;
                     Timed tm(h, TV, s);
                     LAUNCH(vpair_launch(vp, ch, s));
-#ifdef DTTS_ABLATE
-                    if (vp.stats) {
-                        unsigned long long hs[8];
-                        hipStreamSynchronize(s);
-                        hipMemcpy(hs, vp.stats, 64, hipMemcpyDeviceToHost);
-                        const double n = hs[5] ? (double)hs[5] : 1.0;
-                        fprintf(stderr, "vpair C=%d K=%d d=%d mode=%d tiles=%llu  cycles/tile: stage %.0f c1 %.0f rewrite %.0f c2 %.0f epilogue %.0f\n", ch, vp.K, vp.dil,
-                                vp.mode, hs[5], hs[0] / n, hs[1] / n, hs[2] / n, hs[3] / n, hs[4] / n);
-                    }
-#endif
                 }
                 continue;
             }
@@ -1882,12 +1831,9 @@ void dtts_default_config(dtts_config* c) {
 
 int dtts_create(const dtts_config* cfg, dtts_handle* out) {
     if (!cfg || !out) return fail(nullptr, DTTS_E_INVAL, "dtts_create: null argument");
-    if (cfg->tune_flags & ~TUNE_MASK) {   // (release library: an untested experiment's bit is refused, never silently ignored)
-        char msg[160];
-        snprintf(msg, sizeof msg, "dtts_create: tune_flags 0x%x carries bits this build does not honour (supported mask 0x%x; the others exist only in "
-                 "-DDTTS_ABLATE builds)", (unsigned)cfg->tune_flags, (unsigned)TUNE_MASK);
-        return fail(nullptr, DTTS_E_INVAL, "%s", msg);
-    }
+    if (cfg->tune_flags & ~TUNE_RELEASE_MASK)   // (a bit without a test behind it is refused, never silently ignored)
+        return fail(nullptr, DTTS_E_INVAL, "dtts_create: tune_flags 0x%x carries bits this library does not honour (supported mask 0x%x)",
+                    (unsigned)cfg->tune_flags, (unsigned)TUNE_RELEASE_MASK);
     // the block type of the generator is encoded in the dilation rows (include/dicttts_hip.h): a third entry of 0 = a two-dilation
     // (ResBlock2) row.  All used rows are of one kind
     if (cfg->n_resblock_kernels >= 0 && cfg->n_resblock_kernels <= 4) {
@@ -1912,10 +1858,8 @@ int dtts_create(const dtts_config* cfg, dtts_handle* out) {
         return fail(nullptr, DTTS_E_INVAL, "dtts_create: unsupported configuration");
     dtts_ctx* h = new dtts_ctx();
     h->cfg = *cfg;
-    // A/B switches of tuning experiments: dtts_config.tune_flags (0 = the measured defaults; bits documented in include/dicttts_hip.h).
-    // The release library does NOT read the environment; -DDTTS_ABLATE builds (tools/ab_*.sh) OR the DTTS_TUNE variable in.
+    // dtts_config.tune_flags (0 = the measured defaults; bits documented in include/dicttts_hip.h).  The library never reads the environment.
     h->tune = cfg->tune_flags;
-    if (const char* e = ablate_env("DTTS_TUNE")) h->tune |= atoi(e);
     {   // prior-sample seed: different per context, process, device and start time (data-parallel ranks and restarts must not draw the
         // same z_p sequence); dtts_set_noise_seed makes it reproducible
         static unsigned long long instance = 0;
@@ -2342,7 +2286,7 @@ static int encode_impl(dtts_handle h, const int64_t* word_tokens, const float* k
         ConvParams p = base_params(enc1, C, B, T_w, T_w, q, C);
         p.out_mul = (float)std::pow((double)D, -0.5);  // q * key_depth_per_head ** -0.5 (dict_encoder.py:45-46)
         LAUNCH(conv1d_launch(h->s2_q, p, s));
-        const bool projected = entry_ids && h->t_projected;   // resident table of projected rows: logits = K . q, context = Wo sum_l w_l V_l
+        const bool projected = entry_ids != nullptr;   // resident table of projected rows: logits = K . q, context = Wo sum_l w_l V_l
         if (!projected) {
             p = base_params(q, C, B, T_w, T_w, qk, D);
             LAUNCH(conv1d_launch(h->s2_kT, p, s));
@@ -2540,54 +2484,47 @@ int dtts_dict_table_upload(dtts_handle h, int n_entries, const int32_t* tok_off,
     };
     // SURVEY 8d "resident-table path": the table holds the PROJECTED rows K = k_transform(key), V = v_transform(value)
     // (dict_encoder.py:36-39: the reference projects every gloss row of every batch; here once, at upload) — 2 x hidden_size floats per
-    // row instead of 768 (+ 768), and the logit becomes k . q in the reference's own association order.  tune bit 64 keeps the raw
-    // rows (round 2's table: the re-associated kernel of the tensor API reads them).
-    const bool projected = !DTTS_TUNE(h, 64);
-    if (projected && !h->acoustic_ready)
+    // row instead of 768 (+ 768), and the logit becomes k . q in the reference's own association order.
+    if (!h->acoustic_ready)
         return fail(h, DTTS_E_STATE, "dtts_dict_table_upload: the acoustic weights must be finalized first (the table stores k_transform / v_transform projections)");
-    if (projected && nL > (size_t)INT_MAX / 2) return fail(h, DTTS_E_INVAL, "dtts_dict_table_upload: %zu gloss rows", nL);
+    if (nL > (size_t)INT_MAX / 2) return fail(h, DTTS_E_INVAL, "dtts_dict_table_upload: %zu gloss rows", nL);
     int* n_off = (int*)up(tok_off, sizeof(int) * (n_entries + 1));
     int* n_poff = (int*)up(pin_off, sizeof(int) * (n_entries + 1));
     int* n_pmmax = (int*)up(pmmax.data(), sizeof(int) * n_entries);
     float *n_keys = nullptr, *n_values = nullptr;
-    if (projected) {
-        const int C = h->cfg.hidden_size;
-        float* raw = nullptr;
-        hipStream_t ps = nullptr;   // the projection runs on its own stream, on the device that is current now (= the context's: its weights live there)
-        if (!what && (herr = hipMalloc((void**)&raw, std::max<size_t>(nL * D * sizeof(float), 16))) != hipSuccess) what = "staging buffer allocation";
-        if (!what && (herr = hipStreamCreate(&ps)) != hipSuccess) what = "hipStreamCreate";
-        auto proj = [&](const float* src, const PackedConv& L) -> float* {   // [nL][D] host rows -> [nL][C] device rows
-            if (what) return nullptr;
-            float* out = (float*)dev_alloc(h, nL * C * sizeof(float));
-            if (!out) {
-                what = "device allocation";
-                return nullptr;
-            }
-            fresh.push_back(out);
-            if (nL == 0) return out;
-            if ((herr = hipMemcpyAsync(raw, src, nL * D * sizeof(float), hipMemcpyHostToDevice, ps)) != hipSuccess) {
-                what = "host-to-device copy";
-                return nullptr;
-            }
-            ConvParams p = base_params(raw, D, 1, (int)nL, (int)nL, out, C);
-            if ((herr = conv1d_launch(L, p, ps)) != hipSuccess) {
-                what = "projection kernel launch";
-                return nullptr;
-            }
-            if ((herr = hipStreamSynchronize(ps)) != hipSuccess) {
-                what = "projection kernel";
-                return nullptr;
-            }
-            return out;
-        };
-        n_keys = proj(keys, h->s2_k);
-        n_values = proj(values ? values : keys, h->s2_v);
-        if (ps) (void)hipStreamDestroy(ps);
-        if (raw) (void)hipFree(raw);
-    } else {
-        n_keys = (float*)up(keys, nL * D * sizeof(float));
-        n_values = values ? (float*)up(values, nL * D * sizeof(float)) : n_keys;  // the reference stores key == value
-    }
+    const int C = h->cfg.hidden_size;
+    float* raw = nullptr;
+    hipStream_t ps = nullptr;   // the projection runs on its own stream, on the device that is current now (= the context's: its weights live there)
+    if (!what && (herr = hipMalloc((void**)&raw, std::max<size_t>(nL * D * sizeof(float), 16))) != hipSuccess) what = "staging buffer allocation";
+    if (!what && (herr = hipStreamCreate(&ps)) != hipSuccess) what = "hipStreamCreate";
+    auto proj = [&](const float* src, const PackedConv& L) -> float* {   // [nL][D] host rows -> [nL][C] device rows
+        if (what) return nullptr;
+        float* out = (float*)dev_alloc(h, nL * C * sizeof(float));
+        if (!out) {
+            what = "device allocation";
+            return nullptr;
+        }
+        fresh.push_back(out);
+        if (nL == 0) return out;
+        if ((herr = hipMemcpyAsync(raw, src, nL * D * sizeof(float), hipMemcpyHostToDevice, ps)) != hipSuccess) {
+            what = "host-to-device copy";
+            return nullptr;
+        }
+        ConvParams p = base_params(raw, D, 1, (int)nL, (int)nL, out, C);
+        if ((herr = conv1d_launch(L, p, ps)) != hipSuccess) {
+            what = "projection kernel launch";
+            return nullptr;
+        }
+        if ((herr = hipStreamSynchronize(ps)) != hipSuccess) {
+            what = "projection kernel";
+            return nullptr;
+        }
+        return out;
+    };
+    n_keys = proj(keys, h->s2_k);
+    n_values = proj(values ? values : keys, h->s2_v);
+    if (ps) (void)hipStreamDestroy(ps);
+    if (raw) (void)hipFree(raw);
     float* n_key_map = (float*)up(key_map, nL * sizeof(float));
     int64_t* n_pinyin = (int64_t*)up(pinyin, nP * sizeof(int64_t));
     int64_t* n_pinyin_map = (int64_t*)up(pinyin_map, nP * sizeof(int64_t));
@@ -2612,7 +2549,6 @@ int dtts_dict_table_upload(dtts_handle h, int n_entries, const int32_t* tok_off,
     h->t_key_map = n_key_map;
     h->t_pinyin = n_pinyin;
     h->t_pinyin_map = n_pinyin_map;
-    h->t_projected = projected;
     h->t_entries = n_entries;
     return DTTS_OK;
 }

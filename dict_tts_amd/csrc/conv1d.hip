@@ -10,7 +10,6 @@
 // For fp32 each lane reads 4 consecutive channels (one ds_read_b128) and spends them on 4 successive
 // 32x32x2 MFMAs; the weight packing uses the same k permutation, so the contraction is unchanged.
 #include "conv1d.h"
-#include "tune_env.h"
 #include <type_traits>
 #include <cstdlib>
 
@@ -744,7 +743,6 @@ static bool launch_short_policy(const ConvParams& p, hipStream_t stream, hipErro
     // The contraction is summed in P parts fixed by the LAYER (see the kernel); the parts are spread over 4 / 2 / 1 waves (each output
     // tile's chain 4x / 2x shorter, 4x / 2x the workgroups) as far as ALL workgroups stay co-resident: a second round of workgroups
     // costs more than the shorter chains give.  That choice depends on the grid and the device — the result does not.
-    static const int ks_env = [] { const char* e = ablate_env("DTTS_C1D_KS"); return e ? atoi(e) : 0; }();   // A/B override
     const int n_cu = cu_count();
     const int NG = p.C_in_pad / KG;
     const int P = NG % 4 == 0 ? 4 : (NG % 2 == 0 ? 2 : 1);
@@ -758,7 +756,6 @@ static bool launch_short_policy(const ConvParams& p, hipStream_t stream, hipErro
         const size_t wgs = tiles * ((p.C_out_pad + 32 * (4 / k) - 1) / (32 * (4 / k)));
         if (wgs <= (size_t)n_cu * (occ < per_cu_lds ? occ : per_cu_lds)) ks = k;
     }
-    if ((ks_env == 1 || ks_env == 2 || ks_env == 4) && P % ks_env == 0) ks = ks_env;
     if (P == 4) {
         if (ks == 4) *err = launch_short<ENGINE, 1, 1, 4, 1>(p, stream);         // 32 t x 32 co, one part per wave
         else if (ks == 2) *err = launch_short<ENGINE, 1, 2, 2, 2>(p, stream);    // 32 t x 64 co, two parts per wave

@@ -1,6 +1,5 @@
 // Non-GEMM kernels of the Dict-TTS path.  See ops.h for the contracts and the reference lines they follow.
 #include "ops.h"
-#include "tune_env.h"
 
 #include <algorithm>
 #include <climits>
@@ -564,8 +563,7 @@ hipError_t mha_launch(const float* qkv, float* out, const int* lens, int B, int 
         // long sequences (T > 128): keys split over the waves (see mha_mfma_split_kernel; built for few long sequences, where the
         // 128-query form fills < half the CUs).  The rule depends on T ONLY — not on B or the device — because the two kernels merge their
         // partial softmax sums in different orders: an utterance must get the same encoder output alone and inside any batch
-        static const bool split_ok = [] { const char* e = ablate_env("DTTS_MHA_SPLIT"); return !e || atoi(e) != 0; }();
-        if (split_ok && T > 128) {
+        if (T > 128) {
             constexpr int LDS = 8 * MHX_KT * MHX_PITCH + 8 * 32 * (int)sizeof(float);
             static bool configured_dev[64] = {};
             int cur_dev = 0;
@@ -589,13 +587,8 @@ hipError_t mha_launch(const float* qkv, float* out, const int* lens, int B, int 
 // ---------------------------------------------------------------------------------------------------------
 // S2PA dictionary attention: one block per word, gloss rows streamed once with 16 B/lane loads.
 constexpr int S2PA_LMAX = 1024, S2PA_DMAX4 = 3;  // D <= 768 (3 float4 per lane), L_k <= 1024
-#ifndef S2PA_RU_P
-#define S2PA_RU_P 4
-#endif
-#ifndef S2PA_RU_T
-#define S2PA_RU_T 4
-#endif
-constexpr int S2PA_NW = 4, S2PA_RU = S2PA_RU_T;           // waves per workgroup; gloss rows a wave keeps in flight (3 x 16 B per lane each)
+constexpr int S2PA_NW = 4, S2PA_RU = 4;                   // waves per workgroup; gloss rows a wave keeps in flight (3 x 16 B per lane each)
+constexpr int S2PA_RU_P = 4;                              // the same for collated rows <= 256 wide (one 16 B piece per lane each)
 constexpr int S2PA_NTHR = S2PA_NW * 64;
 
 // The workgroup's LDS, carved from DYNAMIC shared memory sized for the launch's L_k and row width D (round 5): the static form was sized for
@@ -811,9 +804,8 @@ __device__ __forceinline__ void s2pa_tail(S2paShared& sh, const S2paArgs& a, con
 // part - 235 us.  Net zero by the stream's clock, so the simple form stays.)
 // DM4: float4 pieces of a row per lane (3: the 768-wide gloss embeddings; 1: rows <= 256 wide = the PRE-PROJECTED table, K = key Wk^T /
 // V = value Wv^T, 192 wide); RU: 2 x the rows of a chunk (a wave keeps RU / 2 key rows + RU / 2 value rows, or RU aliased rows, in flight).
-#ifndef S2PA_WPE
-#define S2PA_WPE 6   // waves per SIMD = workgroups per CU of the table form: 80 VGPRs without a spill (7: 2 spilled, same time; 8: 18 spilled, 2x slower)
-#endif
+constexpr int S2PA_WPE = 6;    // waves per SIMD = workgroups per CU of the table form: 80 VGPRs without a spill (7: 2 spilled, same time; 8: 18 spilled, 2x slower)
+constexpr int S2PA_WPE3 = 4;   // the same for the 768-wide rows (DM4 = 3)
 #ifdef S2PA_STAMP   // phase stamps of every workgroup (tools/s2pa_stamps.py; a variant build, never the release library)
 __device__ unsigned long long s2pa_stamps[8 * 4096];
 extern "C" __attribute__((visibility("default"))) int dtts_debug_s2pa_stamps(unsigned long long* host) {
@@ -827,9 +819,6 @@ extern "C" __attribute__((visibility("default"))) int dtts_debug_s2pa_stamps(uns
 // SPEC: the resident-table form (a.entry != null): the entry's contiguous rows streamed speculatively (below); its own instantiation, so that
 // the list-driven loops of the tensor API do not count against its registers
 template <int DM4, int RU, bool SPEC>
-#ifndef S2PA_WPE3
-#define S2PA_WPE3 4
-#endif
 __global__ __launch_bounds__(S2PA_NTHR, DM4 == 1 ? S2PA_WPE : S2PA_WPE3) void s2pa_kernel(const S2paArgs a) {
     extern __shared__ __attribute__((aligned(16))) char s2pa_smem[];
     S2paShared sh = s2pa_carve(s2pa_smem, a.L_k, a.D);
@@ -1168,7 +1157,7 @@ hipError_t s2pa_launch(const S2paArgs& a, hipStream_t s) {
         hipLaunchKernelGGL((s2pa_kernel<1, 3, true>), g, t, lds, s, a);
     } else if (a.entry && a.D <= 256) {
         hipLaunchKernelGGL((s2pa_kernel<1, 4, true>), g, t, lds, s, a);
-    } else {   // collated tensors — or, ablation builds (tune bit 6), a resident table of raw 768-wide gloss rows
+    } else {   // collated tensors (the tensor API)
         if (a.D <= 256) hipLaunchKernelGGL((s2pa_kernel<1, S2PA_RU_P, false>), g, t, lds, s, a);
         else hipLaunchKernelGGL((s2pa_kernel<S2PA_DMAX4, S2PA_RU, false>), g, t, lds, s, a);
     }

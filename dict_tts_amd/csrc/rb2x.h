@@ -1,5 +1,4 @@
-// Fused HifiGAN ResBlock2 (two dilated convolutions, a residual add after each): see rb2x.hip.  Not to be confused with rblock2.hip, the
-// ablation-only two-group experiment on ResBlock1.
+// Fused HifiGAN ResBlock2 (two dilated convolutions, a residual add after each): see rb2x.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -17,7 +17,6 @@
 // HBM traffic per ResBlock: read x once, read-modify-write the stage sum once (the per-convolution path: ~5 passes).
 #include "rb2x.h"
 #include "rblock.h"
-#include "tune_env.h"
 #include "rb_common.h"
 #include "../../include/dicttts_hip.h"
 
@@ -204,9 +203,9 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
         const uint4* wq = p.w[it] + wlane;
         if constexpr (REAL_STEPS) {
             f32x16 unused[NT];
-            rb2_contract<EL, MT, NT, NKG, PITCH, 4, false, true>(xr, ring, act, xlane - ((p.K - 1) / 2) * d * PITCH, wq, S, d * PITCH, unused);
+            rb2_contract<EL, MT, NT, NKG, PITCH, 4, false>(xr, ring, act, xlane - ((p.K - 1) / 2) * d * PITCH, wq, S, d * PITCH, unused);
         } else
-            rb_contract<EL, MT, NT, NKG, PITCH, false, 1, true>(xr, ring, act, xlane - ((p.K - 1) / 2) * d * PITCH, wq, S, d * PITCH, kg_stride);
+            rb_contract<EL, MT, NT, NKG, PITCH, false, 1>(xr, ring, act, xlane - ((p.K - 1) / 2) * d * PITCH, wq, S, d * PITCH, kg_stride);
         if (it == 0) rb_preload<NT>(ring, p.w[1] + wlane, kg_stride);   // the second convolution's first weights fly during barrier + rewrite
         if (p.tile_ctr && it == 1 && tid == 0) pre[3 * p.B + 1] = G + (int)claim;   // the claimed tile, for everyone (read behind the barrier)
         __syncthreads();               // every wave is done reading the operand tile
@@ -412,7 +411,7 @@ static hipError_t rb2x_launch_cfg(const RB2xParams& p, hipStream_t stream) {
     // persistent workgroups: as many as are resident at once (LDS / thread limits), never more than there can be tiles
     const int per_cu = std::max(1, std::min({(int)(160 * 1024 / lds), 2048 / THREADS, THREADS <= 256 ? 2 : 1}));
     const long long max_tiles = (long long)p.B * ((p.T + TTo - 1) / TTo);
-    const int grid = (int)std::min<long long>((long long)std::max(1, cus - cu_reserve()) * per_cu, max_tiles);
+    const int grid = (int)std::min<long long>((long long)cus * per_cu, max_tiles);
     if (grid <= 0) return hipSuccess;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), lds, stream, q);
     return hipGetLastError();

@@ -39,10 +39,8 @@ struct RBlockParams {
     unsigned* bad;         // always-on detector of the fused conv_post: device counter of NON-FINITE pre-tanh values (an fp16 operand overflowed upstream), or null
     unsigned long long* ovf;   // fp16 range guard: device counter of unrepresentable activations (launches the GUARD instantiation), or null
     int small_tile;        // tune bit 14: C = 64 keeps 512-row tiles at k >= 7 (A/B against the default 640)
-    int pingpong;          // 1: the phase-shifted two-group form (rblock2.hip; an experiment, dtts_config.tune_flags bit 7)
+    int : 32;              // (an unused word: with s_private moved up into it hipcc merges the kernels' scalar argument loads differently)
     int s_private;         // 0, or the byte capacity of S when it holds one private TT-row strip per TILE (fused launch + fused conv_post)
-    unsigned long long* stats;   // -DDTTS_ABLATE builds only (DTTS_RB_STATS): per-phase cycle sums of each group's wave 0 (rblock2.hip)
-    int dbg;               // -DDTTS_ABLATE builds only; tuning ablations (DTTS_VCONV_DBG): 1 skip contractions, 2 skip epilogue, 4 skip the x load, 8 skip write_act
 };
 
 // rows of halo per side of a tile for one ResBlock of kernel size K: the sum of its six convolutions' receptive half-widths,
@@ -70,8 +68,5 @@ long long rblock_private_rows(int C, int halo, int B, int T);
 // valid rows per tile of that launch (conv_post not counted), and whether its LDS — incl. the tile table of B utterances — fits
 int rblock_stage_tile_rows(int C, int halo);
 bool rblock_stage_launch_fits(int C, int halo, int B, bool wav);
-// rblock2.hip: two phase-shifted groups of waves per workgroup (one computing while the other rewrites / loads / stores)
-bool rblock2_supported(int C, int K, bool wav);
-hipError_t rblock2_launch(const RBlockParams& p, int C, hipStream_t stream);
 
 } // namespace dtts

@@ -14,7 +14,6 @@
 // PS = 1 (all but C = 32): persistent workgroups walk the batch's valid tiles, the next tile's x is fetched straight into the
 // residual registers (accumulator layout, no LDS transposition) slab by slab as the epilogue releases them.
 #include "rblock.h"
-#include "tune_env.h"
 #include "rb_common.h"
 
 #include <algorithm>
@@ -39,7 +38,7 @@ extern "C" __attribute__((visibility("default"))) int dtts_debug_rb_stamps(unsig
 #define RB_T(k)
 #endif
 
-// TB (two LDS activation buffers, experiment of round 5): leaky_relu(x) and leaky_relu(xt) live in SEPARATE buffers, so the rewrite after a
+// TB (two LDS activation buffers; no launch configuration selects it: slower, LABNOTES (O)): leaky_relu(x) and leaky_relu(xt) live in SEPARATE buffers, so the rewrite after a
 // contraction needs no write-after-read barrier (nobody reads the buffer it writes): two workgroup barriers per iteration instead of four.
 template <int C, int MT, int NT, int WT, int WC, int EL, int PS, bool GUARD, bool TB = false>
 __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void rblock_kernel(const RBlockParams p) {
@@ -49,20 +48,8 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
     constexpr int W = 32 * MT * WT;
     constexpr int PITCH = C * 2 + 16;
     constexpr int NKG = C / 16;
-    // ONE activation-fragment set (rb_common.h: XA1) in the 640-row C = 64 instantiation: with the double buffer it sat at 256 VGPRs with 13 of them
-    // spilled; the single set (a row tile's next fragment is read right behind the MFMAs that consumed the current one and lands while the other row
-    // tiles' MFMAs run) takes 249 and spills nothing.  Same instruction order per accumulator: same bits; -0.7 % on the vocoder (LABNOTES round 5 (Y)).
-#ifndef RB_XA1
-#define RB_XA1 1
-#endif
-#ifndef RB_XA1_ALL
-#define RB_XA1_ALL 1   // every C >= 64 instantiation (C = 32: neutral / +2 %, keeps the double buffer)
-#endif
-    constexpr bool XA1 = RB_XA1 && ((C == 64 && MT == 5) || (RB_XA1_ALL && C >= 64));
-#ifndef RB_XA1_32
-#define RB_XA1_32 1
-#endif
-    constexpr bool XA1_32 = RB_XA1_32 != 0;   // the same in the C = 32 contraction (rb2_contract)
+    // (the contractions keep ONE activation-fragment set, rb_common.h: with a double buffer the 640-row C = 64 instantiation sat at 256 VGPRs with 13 of
+    // them spilled; the single set takes 249 and spills nothing.  LABNOTES round 5 (Y))
     constexpr int EP = C * 4 + 16;                 // fp32 staging row
     constexpr int F4 = C / 4, SROWS = WT * 32;
     constexpr size_t ACT_BYTES = (size_t)(W + 2 * RB_GUARD) * PITCH;
@@ -136,8 +123,7 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
         for (int n = 0; n < NT; ++n)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                u32x4 v = u32x4{0u, 0u, 0u, 0u};
-                if (!DTTS_DBG(p, 4)) v = __builtin_amdgcn_raw_buffer_load_b128(rs, o0 + (m * 32 * C + n * 32 + 8 * q) * 4, 0, RB_X_AUX);
+                const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, o0 + (m * 32 * C + n * 32 + 8 * q) * 4, 0, RB_X_AUX);
                 const f32x4 f = __builtin_bit_cast(f32x4, v);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) d[n][4 * q + e] = f[e];
@@ -168,14 +154,11 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
         // before the first LDS round trip: one exposed HBM latency per tile.
         const auto rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + (long long)b * p.T * C), 0, len * C * 4, 0x00020000);
         const int g0 = ((t0 - H + r0) * C + c4 * 4) * 4;
-        u32x4 ld[MT][PER];
+        u32x4 ld[MT][PER] = {};   // (every element is loaded below; without the initialiser hipcc schedules the GUARD instantiation differently)
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
-            for (int u = 0; u < PER; ++u) {
-                ld[m][u] = u32x4{0u, 0u, 0u, 0u};
-                if (!DTTS_DBG(p, 4)) ld[m][u] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, g0 + (tile_row(m, u) - r0) * (C * 4), 0, RB_X_AUX);
-            }
+            for (int u = 0; u < PER; ++u) ld[m][u] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, g0 + (tile_row(m, u) - r0) * (C * 4), 0, RB_X_AUX);
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
             if (m) __syncthreads();
@@ -221,11 +204,7 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
     // C = 32 (two k-groups per tap): the packs' zero padding to a multiple of four steps would be 25 / 12.5 / 8 % of the MFMAs at k = 3 / 7 / 11:
     // those configurations run the real steps only (rb2_contract, uniform exit at tap boundaries)
     constexpr bool REAL_STEPS = (NKG < 4);
-#ifdef RB_WINO_PROBE   // TIMING PROBE ONLY (wrong results): k = 3 at C >= 128 with 2/3 of the k-steps = the MFMA / LDS-read count of Winograd F(2,3)
-    const int S = (C >= 128 && Kr == 3) ? 2 * NKG : (REAL_STEPS ? Kr : R.Kp) * NKG;
-#else
-    const int S = DTTS_DBG(p, 1) ? 0 : (REAL_STEPS ? Kr : R.Kp) * NKG;   // k-steps (packed taps are zero padded so that Kp * NKG % 4 == 0)
-#endif
+    const int S = (REAL_STEPS ? Kr : R.Kp) * NKG;   // k-steps (packed taps are zero padded so that Kp * NKG % 4 == 0)
     const bool last_rb = !PS || r + 1 == p.nrb;
     // what the epilogue does with the stage sum: one ResBlock per launch: p.mode; all of the stage's: write, accumulate.., finish
     const int mode = (!PS || p.nrb == 1 || r == 0) ? p.mode : (last_rb ? p.last_mode : 1);
@@ -296,13 +275,6 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
                 for (int q = 0; q < 4; ++q) {
                     const int co = (wc * NT + n) * 32 + 8 * q + 4 * (lane >> 5);
                     f32x4 v4 = {v[m][n][4 * q], v[m][n][4 * q + 1], v[m][n][4 * q + 2], v[m][n][4 * q + 3]};
-#if defined(RB_WINO_PROBE) && RB_WINO_PROBE >= 2   // (the output transform: one fp32 add per value, as two packed adds per four)
-                    if constexpr (C >= 128) {
-                        f32x2_t lo2 = {v4[0], v4[1]}, hi2 = {v4[2], v4[3]};
-                        asm volatile("v_pk_add_f32 %0, %0, %2\n\tv_pk_add_f32 %1, %1, %2" : "+v"(lo2), "+v"(hi2) : "v"(f32x2_t{0.f, 0.f}));
-                        v4 = f32x4{lo2[0], lo2[1], hi2[0], hi2[1]};
-                    }
-#endif
                     uint2 pk = act4<EL>(v4, 0.1f);
                     if constexpr (GUARD) n_ovf += counted ? ovf4(v4, 0.1f) : 0;
                     if constexpr (MASKED) {
@@ -313,7 +285,6 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
         }
     };
     auto write_act = [&](char* dst, const f32x16 (&v)[MT][NT]) {
-        if (DTTS_DBG(p, 8)) return;
         if (all_inb) write_act_impl(dst, v, std::false_type{});
         else write_act_impl(dst, v, std::true_type{});
     };
@@ -342,10 +313,12 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
         load_bias(bb, R.b2[it]);       // lands while conv1 runs
         const int d = R.dil[it];
         if constexpr (REAL_STEPS) {
-            if (S) rb2_contract<EL, MT, NT, NKG, PITCH, 4, true, XA1_32>(acc, ring, act, xlane - ((Kr - 1) / 2) * d * PITCH, R.w1[it] + wlane, S, d * PITCH, cinit);
-            else rb_contract<EL, MT, NT, NKG, PITCH, true, 1, XA1>(acc, ring, act, 0, R.w1[it] + wlane, 0, 0, kg_stride, &cinit);
+            // S > 0 always, which the compiler cannot know.  The two tests on S and the S == 0 arm (acc = cinit, by way of rb_contract) stay: without them,
+            // or with the arm written out, hipcc allocates the C = 32 kernels' registers differently (LABNOTES: retired switches)
+            if (S) rb2_contract<EL, MT, NT, NKG, PITCH, 4, true>(acc, ring, act, xlane - ((Kr - 1) / 2) * d * PITCH, R.w1[it] + wlane, S, d * PITCH, cinit);
+            else rb_contract<EL, MT, NT, NKG, PITCH, true, 1>(acc, ring, act, 0, R.w1[it] + wlane, 0, 0, kg_stride, &cinit);
         } else
-            rb_contract<EL, MT, NT, NKG, PITCH, true, 1, XA1>(acc, ring, act, xlane - ((Kr - 1) / 2) * d * PITCH, R.w1[it] + wlane, S, d * PITCH, kg_stride, &cinit);
+            rb_contract<EL, MT, NT, NKG, PITCH, true, 1>(acc, ring, act, xlane - ((Kr - 1) / 2) * d * PITCH, R.w1[it] + wlane, S, d * PITCH, kg_stride, &cinit);
         rb_preload<NT>(ring, R.w2[it] + wlane, kg_stride);   // next conv's first weights fly during barrier + write
         RB_T(2);
         if constexpr (!TB) __syncthreads();   // every wave is done reading A (TB: xt has its own buffer, last read before the previous barrier)
@@ -365,9 +338,9 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
                     for (int e = 0; e < 4; ++e) xr[m][n][4 * q + e] += bb[n][q][e];
         if (it < 2) load_bias(bb, R.b1[it + 1]);
         if constexpr (REAL_STEPS) {
-            if (S) rb2_contract<EL, MT, NT, NKG, PITCH, 4, false, XA1_32>(xr, ring, act2, xlane - ((Kr - 1) / 2) * PITCH, R.w2[it] + wlane, S, PITCH, cinit);
+            if (S) rb2_contract<EL, MT, NT, NKG, PITCH, 4, false>(xr, ring, act2, xlane - ((Kr - 1) / 2) * PITCH, R.w2[it] + wlane, S, PITCH, cinit);
         } else
-            rb_contract<EL, MT, NT, NKG, PITCH, false, 1, XA1>(xr, ring, act2, xlane - ((Kr - 1) / 2) * PITCH, R.w2[it] + wlane, S, PITCH, kg_stride);
+            rb_contract<EL, MT, NT, NKG, PITCH, false, 1>(xr, ring, act2, xlane - ((Kr - 1) / 2) * PITCH, R.w2[it] + wlane, S, PITCH, kg_stride);
         if (it < 2) rb_preload<NT>(ring, R.w1[it + 1] + wlane, kg_stride);
         if (PS && p.tile_ctr && last_rb && it == 2 && tid == 0) pre[3 * p.B + 1] = G + (int)claim;   // the claimed tile, for everyone (read behind the barrier)
         RB_T(6);
@@ -385,13 +358,7 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
         jn = __builtin_amdgcn_readfirstlane(pre[3 * p.B + 1]);
         plan_next();
     }
-    if (DTTS_DBG(p, 2)) {
-        if (xr[0][0][0] == 123.456f) p.S[0] = 1.f;
-        if (has_next) {
-#pragma unroll
-            for (int m = 0; m < MT; ++m) load_x(xr[m], m, bn, t0n - H, lenn);
-        }
-    } else {
+    {
     // ---- epilogue: rows [H, H+TT) of the tile leave as whole rows through the fp32 staging buffer; the old
     // accumulator values (xs += ...) of all MT passes are fetched up front.  Buffer ops: rows >= len are dropped by the
     // range check, halo rows are sent out of range explicitly.
@@ -405,7 +372,7 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
     const int goffw = (p.s_private ? (j * TT - H) * C : base_t * C) * 4 + (wc * CW + ec * 4) * 4;
     // Which of the slab's 32 rows an octet reads in access u.  Consecutive rows (u * 8 + er: rounds 3 - 5) put the 16-lane groups of a ds_read_b128
     // ({0-3, 12-15, 20-27}, ...) on overlapping 16-byte slots of the 256-byte bank row — 3-way at C >= 64, 2-way at C = 32: 12 / 8 LDS cycles per read instead
-    // of 4, a quarter of the kernels' bank-conflict cycles (round 6: tools/lds_conflict_attrib.sh; the model reproduces the counter to 1 %).  Rows
+    // of 4, a quarter of the kernels' bank-conflict cycles (round 6: LABNOTES (c6), profiles/r06_lds_conflict_attrib.txt; the model reproduces the counter to 1 %).  Rows
     // base + {0, 16, 8, 24} for the four octets of a half-wave (base = 2 u + half) spread every group over all 16 slots for each row pitch in use (9 / 17 / 33 / 65
     // slots): conflict-free; an octet still moves one whole 128-byte row segment, so the global accesses coalesce as before.  Same values, same order per row.
     static_assert(F4W == 8 && RPI == 8 && NRD == 4, "the conflict-free row order below is for 8 lanes per row, 8 rows per access");
@@ -642,7 +609,7 @@ static hipError_t rb_launch_cfg(const RBlockParams& p, hipStream_t stream) {
     }
     const int per_cu = std::max(1, std::min({(int)(160 * 1024 / lds), 2048 / THREADS, THREADS <= 256 ? 2 : 1}));
     const long long max_tiles = (long long)p.B * ((p.T + TTo - 1) / TTo);
-    const int grid = (int)std::min<long long>((long long)std::max(1, cus - cu_reserve()) * per_cu, max_tiles);
+    const int grid = (int)std::min<long long>((long long)cus * per_cu, max_tiles);
     if (grid <= 0) return hipSuccess;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), lds, stream, q);
     return hipGetLastError();
@@ -687,11 +654,9 @@ template <int EL>
 static hipError_t rb_launch_el(const RBlockParams& p, int C, hipStream_t stream) {
     // C = 32: k >= 7 on 1024-row tiles (8 waves over time, one persistent workgroup per CU: the 6 (k - 1)-row halo costs 12 % of a
     // k = 11 tile instead of 23 %; -8 % on that launch), k = 3 on 512-row tiles, two 4-wave workgroups per CU, one tile each (the
-    // 1024-row form is 14 % slower there).  DTTS_RB32=0: 512-row tiles for every k (round 2).
-    static const int rb32 = ablate_env("DTTS_RB32") ? atoi(ablate_env("DTTS_RB32")) : 1;
+    // 1024-row form is 14 % slower there).
     // small batches (B = 1: one sentence): when the default tiles leave more than half of the CUs without one, the launch takes as long
     // as ONE tile -> half-size tiles (more halo recomputed, but twice the CUs at work)
-    static const bool small_ok = [] { const char* e = ablate_env("DTTS_RB_SMALL"); return !e || atoi(e) != 0; }();
     static int cus_dev[64] = {};
     int cur_dev = 0;
     (void)hipGetDevice(&cur_dev);
@@ -702,7 +667,7 @@ static hipError_t rb_launch_el(const RBlockParams& p, int C, hipStream_t stream)
     }
     auto few = [&](int W) {   // tiles of W rows (valid: W - 2 rblock_halo, the fused conv_post 6 less): at most half the CUs get one
         const int tt = W - 2 * rblock_halo(p) - (p.wav ? 6 : 0);
-        return small_ok && tt >= 32 && 2 * (long long)p.B * ((p.T + tt - 1) / tt) <= cus;
+        return tt >= 32 && 2 * (long long)p.B * ((p.T + tt - 1) / tt) <= cus;
     };
     if (p.nrb < 1 || p.nrb > 3) return hipErrorInvalidValue;
     if (p.nrb > 1) {   // every ResBlock of the stage in one launch: the persistent full-size configurations only
@@ -710,21 +675,6 @@ static hipError_t rb_launch_el(const RBlockParams& p, int C, hipStream_t stream)
         if (C == 64) return rb_launch_cfg<64, 4, 1, 4, 2, EL, 1>(p, stream);
         return hipErrorInvalidValue;
     }
-    // (experiment, tune bit 7) C = 32 without the fused conv_post: two phase-shifted groups per workgroup (rblock2.hip)
-#ifdef DTTS_ABLATE   // (rblock2.hip is compiled into the ablation library only)
-    if (p.pingpong && rblock_halo(p) == 6 * (p.K - 1) && rblock2_supported(C, p.K, p.wav != nullptr) && !few(512)) return rblock2_launch(p, C, stream);
-#endif
-#if defined(RB_TB32)   // experiment: two activation buffers at C = 32, k >= 7: 768-row tiles (MT = 3), two barriers per iteration instead of four
-    if (C == 32 && rb32 && p.K >= 7 && !few(768)) return rb_launch_cfg<32, 3, 1, 8, 1, EL, 1, false, true>(p, stream);
-#endif
-#if defined(RB_X32) && RB_X32 == 1   // experiment: 12 waves (3 per SIMD) over 1152 rows at C = 32, k >= 7
-    if (C == 32 && rb32 && p.K >= 7 && !few(1152)) {   // (with the fused conv_post the 1152-row output tile does not fit the LDS: falls through)
-        const hipError_t e = rb_launch_cfg<32, 3, 1, 12, 1, EL, 1>(p, stream);
-        if (e != hipErrorInvalidValue && e != hipErrorOutOfMemory) return e;
-    }
-#elif defined(RB_X32) && RB_X32 == 2 // experiment: 12 waves (3 per SIMD) over 768 rows, MT = 2
-    if (C == 32 && rb32 && p.K >= 7 && !few(768)) return rb_launch_cfg<32, 2, 1, 12, 1, EL, 1>(p, stream);
-#endif
     // RB_TRY: a persistent configuration whose LDS cannot hold the tile table of this many utterances (hipErrorOutOfMemory: the fused
     // conv_post's 1024-row tile above ~940 utterances, the 128-row C = 256 tile above ~1730) falls through to the next one down
 #define RB_TRY(call)                                   \
@@ -732,21 +682,13 @@ static hipError_t rb_launch_el(const RBlockParams& p, int C, hipStream_t stream)
         const hipError_t e_ = (call);                  \
         if (e_ != hipErrorOutOfMemory) return e_;      \
     } while (0)
-    if (C == 32 && rb32 && p.K >= 7 && !few(1024)) RB_TRY((rb_launch_cfg<32, 4, 1, 8, 1, EL, 1>(p, stream)));
+    if (C == 32 && p.K >= 7 && !few(1024)) RB_TRY((rb_launch_cfg<32, 4, 1, 8, 1, EL, 1>(p, stream)));
     if (C == 64 && few(512)) return rb_launch_cfg<64, 4, 1, 2, 2, EL, 1>(p, stream);     // 256-row tile, 4 waves
     if (C == 128 && few(256)) return rb_launch_cfg<128, 4, 1, 1, 4, EL, 1>(p, stream);   // 128-row tile, 4 waves
     if (C == 256 && few(128)) return rb_launch_cfg<256, 2, 1, 1, 8, EL, 1>(p, stream);   // 64-row tile
     if (C == 32) return rb_launch_cfg<32, 4, 1, 4, 1, EL, 0>(p, stream);      // 512-row tile, 4 waves over time
     // C = 64, k >= 7: 640-row tiles (MT = 5; the halo 12 (k - 1) is 11 / 19 % of the tile instead of 14 / 23 %: -4.8 % at k = 11, nothing at k = 3
     // where 13 spilled registers cost what the halo gives); tune bit 14: 512-row tiles for every k (round 3)
-#if defined(RB_X64) && RB_X64 <= 2   // experiment: 12 waves (3 per SIMD: 6 time x 2 channel), 576-row tiles, 168 registers: RB_X64 = 1 for k >= 7, 2 for every k
-    if (C == 64 && (p.K >= 7 || RB_X64 >= 2) && !p.small_tile) return rb_launch_cfg<64, 3, 1, 6, 2, EL, 1>(p, stream);
-#elif defined(RB_X64)                // experiment: 16 waves (4 per SIMD: 8 time x 2 channel), 512-row tiles, 128 registers, every k
-    if (C == 64 && !p.small_tile) return rb_launch_cfg<64, 2, 1, 8, 2, EL, 1>(p, stream);
-#endif
-#if defined(RB_X128)  // experiment: 12 waves (3 time x 4 channel), 288-row tiles at C = 128 (k = 3)
-    if (C == 128) return rb_launch_cfg<128, 3, 1, 3, 4, EL, 1>(p, stream);
-#endif
     if (C == 64 && p.K >= 7 && !p.small_tile) RB_TRY((rb_launch_cfg<64, 5, 1, 4, 2, EL, 1>(p, stream)));
     if (C == 64) RB_TRY((rb_launch_cfg<64, 4, 1, 4, 2, EL, 1>(p, stream)));    // 512-row tile, 8 waves (4 time x 2 channel)
     if (C == 64) return rb_launch_cfg<64, 4, 1, 2, 2, EL, 1>(p, stream);       // (the tile table of a very large batch) 256-row tile

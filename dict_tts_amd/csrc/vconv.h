@@ -46,7 +46,7 @@ struct VConvParams {
     float div;                // 1 or num_kernels (true division)
     int post_tanh;
     unsigned* bad;            // with post_tanh: device counter of non-finite pre-tanh values (the always-on overflow detector), or null
-    int dbg;                  // -DDTTS_ABLATE builds only (DTTS_VCONV_DBG): 1 = skip the contraction, 2 = skip the epilogue, 4 = skip staging
+    int : 32;                 // (an unused word: with row_mask right behind bad hipcc merges the kernels' scalar argument loads differently)
     const float* row_mask;    // optional [B][T] per-row factor (the FVAE posterior's x_mask), applied last to the first segment: the res half of a
                               // WaveNet res / skip layer ((x + res) * mask), a single-segment layer's output (the last layer's skip sum), a plain
                               // conv's output; never to the gated acts or the second (skip) segment.  Null: no multiply, the same arithmetic as before

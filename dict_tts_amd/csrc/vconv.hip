@@ -12,23 +12,14 @@
 //   * dual-output epilogue: fp32 residual stream + bf16 leaky_relu copy for the next convolution.
 // Same packed-weight format as conv1d.hip (context.hip:pack_conv), same contraction, same rounding points.
 #include "vconv.h"
-// the fp32 result rows are consumed by the next launch: non-temporal stores (rb_common.h: cache policy; -0.5 % same box)
-#ifndef VC_NT_STORE
-#define VC_NT_STORE 1
-#endif
 #include "rb_common.h"
 
-#ifndef VC_SB
-#define VC_SB 1
-#endif
-#ifndef VC_SB1
-#define VC_SB1 1   // the one-co-tile split-operand configurations (decoder WaveNet): one fragment set, three workgroups per CU
-#endif
-#ifndef VC_H2_RING
-#define VC_H2_RING 2
-#endif
 namespace dtts {
 
+constexpr int VC_H2_RING = 2;   // weight-fragment ring slots of the two-product fp16 form (H2)
+constexpr int VC_WPE_DEC = 4;   // workgroups per CU (launch bound) of the decoder WaveNet configuration: 64-row tiles, CK = 64, four waves over the channels
+// loads in flight per thread and staging batch on the 64-row split-operand tiles (LABNOTES (L): measured at 9; the default was left at 4 until round 5 (S))
+constexpr int VC_U_SMALL = 9;
 
 __device__ __forceinline__ unsigned vf2bf(float f) {  // round-to-nearest-even fp32 -> bf16 bits (hardware convert)
     const __bf16 h = (__bf16)f;
@@ -44,10 +35,7 @@ __device__ __forceinline__ unsigned vf2bf(float f) {  // round-to-nearest-even f
 // "hh/h": 7e-5 waveform RMS when ups.1 alone runs this way (gate 1e-4, 5.3e-5 with three products everywhere).  fp16 hi saturates at
 // 65504 and lo carries the rest, so the pair represents |a| up to 1.3e5.
 template <int MT, int NT, int WT, int WC, int CK, bool X3, bool H2 = false>
-#ifndef VC_WPE_DEC
-#define VC_WPE_DEC 4
-#endif
-__global__ __launch_bounds__(256, X3 ? (MT <= 2 ? (NT == 2 ? 3 : (CK == 64 && WC == 4 ? VC_WPE_DEC : 4)) : ((VC_SB1 && NT == 1) ? 3 : 2)) : (NT == 1 ? 3 : 2)) void vconv_kernel(const VConvParams p) {
+__global__ __launch_bounds__(256, X3 ? (MT <= 2 ? (NT == 2 ? 3 : (CK == 64 && WC == 4 ? VC_WPE_DEC : 4)) : (NT == 1 ? 3 : 2)) : (NT == 1 ? 3 : 2)) void vconv_kernel(const VConvParams p) {
     static_assert(!H2 || X3, "H2 is a variant of the fp32-input path");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int PITCH = CK * 2 + 16;
@@ -126,9 +114,6 @@ __global__ __launch_bounds__(256, X3 ? (MT <= 2 ? (NT == 2 ? 3 : (CK == 64 && WC
     for (int ci0 = 0; ci0 < p.C_in_pad; ci0 += CK) {
         if (ci0) __syncthreads();
         if constexpr (X3) {   // fp32 in: leaky_relu, bf16 hi / lo split, two LDS tiles; 4 channels per 16 B load
-#ifndef VC_U_SMALL
-#define VC_U_SMALL 9   // (LABNOTES (L): measured with -DVC_U_SMALL=9, and the default was left at 4 until round 5 (S))
-#endif
             // A thread keeps its 4-channel piece and walks the rows in steps of 256 / PIECES.  Buffer loads over the utterance's rows
             // [0, len): a row outside it (t < 0 wraps to a huge unsigned offset, t >= len exceeds num_records) returns zeros = the zero
             // padding, no per-access compare, one VGPR of address per load.  U loads in flight per thread and batch: the narrow 64-row
@@ -175,7 +160,7 @@ __global__ __launch_bounds__(256, X3 ? (MT <= 2 ? (NT == 2 ? 3 : (CK == 64 && WC
                     *(uint2*)(smem + lo_off + r * PITCH + c * 8) = make_uint2(pack2bf(lo[0], lo[1]), pack2bf(lo[2], lo[3]));
                 }
             }
-        } else if (!DTTS_DBG(p, 4)) {   // stage the activation tile: batches of U independent 16 B loads in flight per thread, then the LDS writes
+        } else {   // stage the activation tile: batches of U independent 16 B loads in flight per thread, then the LDS writes
             constexpr int U = 8, PIECES = CK / 8;
             const int total = rows * PIECES;
             for (int base = tid; base < total; base += 256 * U) {
@@ -200,8 +185,9 @@ __global__ __launch_bounds__(256, X3 ? (MT <= 2 ? (NT == 2 ? 3 : (CK == 64 && WC
         // activation fragments are double-buffered in registers: step s+1 is read from LDS before the MFMAs of step s.
         // SB (the two-co-tile split-operand configuration: 128 accumulators + hi / lo rings + two fragment sets = 256 VGPRs and 9-12
         // spilled): ONE fragment set; row tile m's next fragments are read right behind the MFMAs that consumed the current ones and land
-        // while the other row tiles' MFMAs execute.
-        constexpr bool SB = X3 && ((VC_SB && NT == 2) || (VC_SB1 && NT == 1 && MT == 4));
+        // while the other row tiles' MFMAs execute.  The same in the one-co-tile split-operand configurations on 128-row tiles (decoder
+        // WaveNet): one fragment set, three workgroups per CU.
+        constexpr bool SB = X3 && (NT == 2 || (NT == 1 && MT == 4));
         constexpr int XB = SB ? 1 : 2;
         uint4 xa[XB][MT], xl[X3 ? XB : 1][MT];
 #pragma unroll
@@ -209,10 +195,9 @@ __global__ __launch_bounds__(256, X3 ? (MT <= 2 ? (NT == 2 ? 3 : (CK == 64 && WC
             xa[0][m] = *(const uint4*)(smem + xoff + tap_lo * p.dil * PITCH + m * 32 * PITCH);
             if constexpr (X3) xl[0][m] = *(const uint4*)(smem + lo_off + xoff + tap_lo * p.dil * PITCH + m * 32 * PITCH);
         }
-        const int ntap = DTTS_DBG(p, 1) ? tap_lo : tap_hi;
         const int dilP = p.dil * PITCH;
         int arow = xoff + tap_lo * dilP;
-        for (int tap = tap_lo; tap < ntap; ++tap) {
+        for (int tap = tap_lo; tap < tap_hi; ++tap) {
 #pragma unroll
             for (int kg = 0; kg < NKG; ++kg) {
 #pragma unroll
@@ -260,10 +245,6 @@ __global__ __launch_bounds__(256, X3 ? (MT <= 2 ? (NT == 2 ? 3 : (CK == 64 && WC
         if (ci0 + CK < p.C_in_pad) preload(ci0 + CK);
     }
 
-    if (DTTS_DBG(p, 2)) {
-        if (acc[0][0][0] == 123.456f) p.yf[0] = 1.f;
-        return;
-    }
     // ---- epilogue.  The accumulators are D[co][t] (lane = one time row, 4 consecutive channels per register
     // quad).  Stored straight from that layout every wave instruction would touch 32 different rows with 32 B each;
     // instead each 32-row slab goes through LDS (the activation tile is dead by now) and leaves as whole rows:
@@ -398,13 +379,8 @@ __global__ __launch_bounds__(256, X3 ? (MT <= 2 ? (NT == 2 ? 3 : (CK == 64 && WC
                         for (int e = 0; e < 4; ++e) o[e] = tanhf(o[e]);
                     }
                     if (p.row_mask) o *= p.row_mask[off[u]];
-                    if (p.yf) {
-#if VC_NT_STORE
-                        __builtin_nontemporal_store(o, (f32x4*)(p.yf + off[u] * p.ldyf + co));
-#else
-                        *(f32x4*)(p.yf + off[u] * p.ldyf + co) = o;
-#endif
-                    }
+                    // the fp32 result rows are consumed by the next launch: non-temporal stores (rb_common.h: cache policy; -0.5 % same box)
+                    if (p.yf) __builtin_nontemporal_store(o, (f32x4*)(p.yf + off[u] * p.ldyf + co));
                     if (p.ya)
                         *(uint2*)(p.ya + off[u] * p.ldya + co) = make_uint2(pack2bf(lrelu(o[0], p.slope), lrelu(o[1], p.slope)),
                                                                             pack2bf(lrelu(o[2], p.slope), lrelu(o[3], p.slope)));
@@ -501,9 +477,6 @@ hipError_t vconv_launch(const VConvParams& p, hipStream_t stream) {
         if (ci % 64 == 0) return vlaunch<4, 2, 1, 4, 64>(p, stream);
         return vlaunch<4, 2, 1, 4, 32>(p, stream);
     }
-#ifdef VC_DEC_CK192   // experiment: the whole C_in = 192 of a decoder WaveNet layer as ONE chunk (one staging + barrier per tile instead of three)
-    if (p.xf && (p.gate_H || p.split) && co % 128 == 0 && ci == 192 && (VC_DEC_CK192 >= 2 || p.K == 1)) return vlaunch_x<2, 1, 1, 4, 192, true>(p, stream);
-#endif
     // the decoder WaveNet layers (gate / res-skip epilogue; 192 -> 384 channels, k = 5 / 1): 64-row tiles, four workgroups per CU.  On 128-row
     // tiles a B = 60 batch was 1,080 workgroups for 768 slots (two rounds for 1.4 rounds of work) and one sentence 12 workgroups:
     // decode 1.165 -> 1.117 ms at B = 60, 0.515 -> 0.446 ms at B = 1 (round 5, same contraction order: same bits)

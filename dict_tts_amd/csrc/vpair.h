@@ -26,8 +26,6 @@ struct VPairParams {
     int pre_off;          // (set by the launcher) byte offset of the tile table in dynamic LDS
     int tile_rows;        // (set by the launcher) rows of the LDS activation tile
     unsigned long long* ovf;     // fp16 range guard: device counter of unrepresentable activations (launches the GUARD instantiation), or null
-    unsigned long long* stats;   // -DDTTS_ABLATE builds only: per-phase cycle sums of wave 0 (see vpair.hip), or null
-    int dbg;              // -DDTTS_ABLATE builds only (DTTS_VCONV_DBG >> 8): 1 skip contractions, 2 skip epilogue, 4 skip staging, 8 skip xt write
 };
 
 bool vpair_supported(int C, int K, int dil);

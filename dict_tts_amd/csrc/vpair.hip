@@ -9,8 +9,6 @@
 //     epilogue and writes only the fp32 result (or accumulates into the stage sum xs for the last iteration).
 // HBM bytes per row and iteration: ~0.8 KB in + 0.5 KB out.  4 waves over output channels, 3 workgroups per CU.
 #include "vpair.h"
-#include "tune_env.h"
-
 #include "rb_common.h"
 
 #include <algorithm>
@@ -22,7 +20,7 @@ namespace dtts {
 // TT = 128: 3 workgroups per CU; TT = 256: every weight fragment feeds 8 MFMAs instead of 4 (half the weight stream
 // through the texture path, half the halo), 2 workgroups per CU when the LDS tile allows
 // C = 256 (NT = 2 co-tiles per wave): the stage-1 ResBlocks; 128-row tiles only.
-// WT = 2 (C = 128): the four waves as 2 (time) x 2 (output channels), two co-tiles per wave — every activation fragment read from LDS feeds two
+// WT = 2 (C = 128; no launch configuration selects it: 1.3 / 4 % slower, LABNOTES (K)): the four waves as 2 (time) x 2 (output channels), two co-tiles per wave — every activation fragment read from LDS feeds two
 // MFMAs instead of one (half the ds_read_b128 traffic; twice the weight fragments through the texture path, as at C = 256).
 // X16 (round 6; EL_F16 only): the INPUT stream x is fp16 — iterations 1 and 2 of a ResBlock, whose predecessor stored its result with
 // p.y16.  fp16(x) is exactly what the fp32 stream's staging computed as the convolution operand, so c1's operands keep their bits; what
@@ -38,16 +36,12 @@ __global__ __launch_bounds__(256, (C == 128 && TT == 128 && WT == 1) ? 3 : 2) vo
     constexpr int WC = 4 / WT, TW = TT / WT;     // waves over the output channels; rows of a time-wave
     constexpr int MT = (TW == 192 || TW == 96) ? 3 : (TW == 64 ? 2 : 4), NT = C / (32 * WC), MH = TW / (32 * MT), MTT = MT * MH;   // TW = 192: two passes of 3 row tiles
     constexpr int PITCH = C * 2 + 16, NKG = C / 16, NCT = C / 32;
-#ifndef VP_XA1
-#define VP_XA1 1
-#endif
-    constexpr bool XA1 = VP_XA1 != 0;   // one activation-fragment set in the contractions (rb_common.h)
     constexpr int EP = C * 4 + 16, F4 = C / 4;
     static_assert(NCT == WC * NT && (NT == 1 || MH == 1) && WT * WC == 4, "4 waves: WT over time x WC over the output channels");
     const int tid0 = threadIdx.x;
     const int h1 = p.dil * (p.K - 1) / 2, h2 = (p.K - 1) / 2;
     const int TTe = TT - 2 * h2;             // valid output rows per tile
-    const int S = DTTS_DBG(p, 1) ? 0 : p.K * NKG;
+    const int S = p.K * NKG;
     // ---- persistent workgroups (as in rblock.hip): the valid tiles of the batch, ceil(len_b / TTe) per utterance, are numbered
     // through and workgroup w takes tiles w, w + G, ...; the table of the per-utterance tile counts' prefix sums and the lengths
     // live in LDS behind the tile.  A tile's stores drain while the next tile is staged, and no workgroup is launched per tile.
@@ -96,13 +90,6 @@ __global__ __launch_bounds__(256, (C == 128 && TT == 128 && WT == 1) ? 3 : 2) vo
     }
     const long long brow = (long long)b * p.T;
 
-#ifdef DTTS_ABLATE
-    unsigned long long tq[6];
-#define VP_STAMP(i) tq[i] = __builtin_amdgcn_s_memtime()
-#else
-#define VP_STAMP(i)
-#endif
-    VP_STAMP(0);
     int n_ovf = 0;
     uint4 ring[4][NT];
     const size_t wlane = (size_t)wc * NT * 64 + lane;   // the wave's first co-tile
@@ -121,50 +108,42 @@ __global__ __launch_bounds__(256, (C == 128 && TT == 128 && WT == 1) ? 3 : 2) vo
     const int a0 = t0 - h2 - h1;
     const int arows = TT + 2 * h1;
     if constexpr (X16) {
-        if (!DTTS_DBG(p, 4)) {
-            constexpr int F8 = C / 8, RS8 = 256 / F8;   // 8 channels (16 bytes) per access; rows between two accesses of a thread (16 / 8)
-#ifndef VP_U16
-#define VP_U16 (RS8 == 16 ? 10 : 12)
-#endif
-            // independent loads in flight per thread and batch.  (All 19 / 23 accesses of a tile in ONE batch — one exposed round trip instead of
-            // two — shortens wave 0's staging phase and not the launch: LABNOTES round 6 (b).)
-            constexpr int U = VP_U16;
-            const int c8 = tid % F8, r8 = tid / F8;
-            const int nk = (arows + RS8 - 1) / RS8;
-            const int voff0 = ((a0 + r8) * C + c8 * 8) * 2;
-            char* lrow = smem + r8 * PITCH + c8 * 16;
-            const int rlim = p.tile_rows - r8;      // the last pass may reach past the tile's LDS rows (the tile table lives there)
-            const _Float16 hs = (_Float16)0.1f;
-            const f16x2_t slope2 = {hs, hs};
-            for (int kb = 0; kb < nk; kb += U) {
-                u32x4 v[U];
+        constexpr int F8 = C / 8, RS8 = 256 / F8;   // 8 channels (16 bytes) per access; rows between two accesses of a thread (16 / 8)
+        // independent loads in flight per thread and batch.  (All 19 / 23 accesses of a tile in ONE batch — one exposed round trip instead of
+        // two — shortens wave 0's staging phase and not the launch: LABNOTES round 6 (b).)
+        constexpr int U = RS8 == 16 ? 10 : 12;
+        const int c8 = tid % F8, r8 = tid / F8;
+        const int nk = (arows + RS8 - 1) / RS8;
+        const int voff0 = ((a0 + r8) * C + c8 * 8) * 2;
+        char* lrow = smem + r8 * PITCH + c8 * 16;
+        const int rlim = p.tile_rows - r8;      // the last pass may reach past the tile's LDS rows (the tile table lives there)
+        const _Float16 hs = (_Float16)0.1f;
+        const f16x2_t slope2 = {hs, hs};
+        for (int kb = 0; kb < nk; kb += U) {
+            u32x4 v[U];
 #pragma unroll
-                for (int u = 0; u < U; ++u)   // (an access past the tile's rows is sent out of range: zeros, no memory traffic)
-                    v[u] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, kb + u < nk ? voff0 + (kb + u) * (RS8 * C * 2) : (int)0x80000000, 0, 0);
+            for (int u = 0; u < U; ++u)   // (an access past the tile's rows is sent out of range: zeros, no memory traffic)
+                v[u] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, kb + u < nk ? voff0 + (kb + u) * (RS8 * C * 2) : (int)0x80000000, 0, 0);
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    if (kb + u >= nk || (kb + u) * RS8 >= rlim) continue;
-                    u32x4 r;
+            for (int u = 0; u < U; ++u) {
+                if (kb + u >= nk || (kb + u) * RS8 >= rlim) continue;
+                u32x4 r;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const unsigned w = v[u][e];   // (a scalar copy first: __builtin_bit_cast applied to a vector-element lvalue reads element 0 whatever the index)
-                        const f16x2_t hv = __builtin_bit_cast(f16x2_t, w);
-                        if constexpr (GUARD) {   // census: a stored value beyond the fp16 range arrives as +-inf (only the rows this tile outputs)
-                            const int rr = r8 + (kb + u) * RS8 - h1 - h2;
-                            if (rr >= 0 && rr < TTe)
-                                n_ovf += (__builtin_fabsf((float)hv[0]) > 65504.f ? 1 : 0) + (__builtin_fabsf((float)hv[1]) > 65504.f ? 1 : 0);
-                        }
-                        r[e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(hv, hv * slope2));
+                for (int e = 0; e < 4; ++e) {
+                    const unsigned w = v[u][e];   // (a scalar copy first: __builtin_bit_cast applied to a vector-element lvalue reads element 0 whatever the index)
+                    const f16x2_t hv = __builtin_bit_cast(f16x2_t, w);
+                    if constexpr (GUARD) {   // census: a stored value beyond the fp16 range arrives as +-inf (only the rows this tile outputs)
+                        const int rr = r8 + (kb + u) * RS8 - h1 - h2;
+                        if (rr >= 0 && rr < TTe)
+                            n_ovf += (__builtin_fabsf((float)hv[0]) > 65504.f ? 1 : 0) + (__builtin_fabsf((float)hv[1]) > 65504.f ? 1 : 0);
                     }
-                    *(u32x4*)(lrow + (kb + u) * (RS8 * PITCH)) = r;
+                    r[e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(hv, hv * slope2));
                 }
+                *(u32x4*)(lrow + (kb + u) * (RS8 * PITCH)) = r;
             }
         }
-    } else if (!DTTS_DBG(p, 4)) {
-#ifndef VP_U
-#define VP_U 12
-#endif
-        constexpr int U = VP_U;                     // independent loads in flight per thread and batch
+    } else {
+        constexpr int U = 12;                       // independent loads in flight per thread and batch
         const int nk = (arows + RSTEP - 1) / RSTEP;
         const int voff0 = ((a0 + r0) * C + c4 * 4) * 4;
         char* lrow = smem + r0 * PITCH + c4 * 8;
@@ -192,7 +171,6 @@ __global__ __launch_bounds__(256, (C == 128 && TT == 128 && WT == 1) ? 3 : 2) vo
 #pragma unroll
         for (int q = 0; q < 4; ++q) bb[n][q] = *(const f32x4*)(p.b1 + (wc * NT + n) * 32 + 8 * q + 4 * (lane >> 5));
     __syncthreads();
-    VP_STAMP(1);
 
     // ---- c1: xt rows r = 0..127  <->  global t0 - h2 + r ; reads staged rows r + tap * d
     f32x16 acc[MTT][NT];
@@ -211,14 +189,13 @@ __global__ __launch_bounds__(256, (C == 128 && TT == 128 && WT == 1) ? 3 : 2) vo
     };
     if (NT == 1) load_b2();   // lands while c1 runs; at C = 256 its 32 registers do not fit beside c1's (spills): fetched after c1 there
     const int xlane = (wt * TW + (lane & 31)) * PITCH + (lane >> 5) * 16;
-    rb_contract<EL, MT, NT, NKG, PITCH, true, MH, XA1>(acc, ring, smem, xlane, p.w1 + wlane, S, p.dil * PITCH, 0, &cinit);
+    rb_contract<EL, MT, NT, NKG, PITCH, true, MH>(acc, ring, smem, xlane, p.w1 + wlane, S, p.dil * PITCH, 0, &cinit);
     if (NT != 1) load_b2();
     rb_preload<NT>(ring, p.w2 + wlane, NCT * 64);
-    VP_STAMP(2);
     __syncthreads();   // every wave is done reading the x tile
     // ---- bf16(leaky_relu(xt)) overwrites it (rows 0..127), zero outside the utterance
 #pragma unroll
-    for (int m = 0; m < (DTTS_DBG(p, 8) ? 0 : MTT); ++m) {
+    for (int m = 0; m < MTT; ++m) {
         const int r = wt * TW + m * 32 + (lane & 31);
         const int t = t0 - h2 + r;
         const bool inb = t >= 0 && t < len;
@@ -234,7 +211,6 @@ __global__ __launch_bounds__(256, (C == 128 && TT == 128 && WT == 1) ? 3 : 2) vo
             }
     }
     __syncthreads();
-    VP_STAMP(3);
     // ---- c2: output rows o = 0..127 <-> global t0 + o (valid for o < TTe) ; reads xt rows o + tap
 #pragma unroll
     for (int n = 0; n < NT; ++n)
@@ -242,18 +218,11 @@ __global__ __launch_bounds__(256, (C == 128 && TT == 128 && WT == 1) ? 3 : 2) vo
         for (int q = 0; q < 4; ++q)
 #pragma unroll
             for (int e = 0; e < 4; ++e) cinit[n][4 * q + e] = bb[n][q][e];
-    rb_contract<EL, MT, NT, NKG, PITCH, true, MH, XA1>(acc, ring, smem, xlane, p.w2 + wlane, S, PITCH, 0, &cinit);
-    VP_STAMP(4);
+    rb_contract<EL, MT, NT, NKG, PITCH, true, MH>(acc, ring, smem, xlane, p.w2 + wlane, S, PITCH, 0, &cinit);
     __syncthreads();   // the xt tile is dead: the staging buffer of the epilogue aliases it
 
     if constexpr (GUARD) {
         if (n_ovf) atomicAdd(p.ovf, (unsigned long long)n_ovf);   // (output rows only: every in-utterance row exactly once per launch)
-    }
-    if (DTTS_DBG(p, 2)) {
-        if (acc[0][0][0] == 123.456f) p.y[0] = 1.f;
-        if constexpr (!PS) break;
-        j = j_static;
-        continue;
     }
     // ---- epilogue: 32-row slabs through LDS, whole rows out; residual x re-read (L2), xs accumulated per mode.
     // Buffer loads / stores again: rows >= len are dropped by the range check, the garbage rows o >= TTe of the last
@@ -272,15 +241,10 @@ __global__ __launch_bounds__(256, (C == 128 && TT == 128 && WT == 1) ? 3 : 2) vo
     };
     // The residual rows (and, modes 2 / 3, the stage sum) of a slab are requested XD - 1 (SD - 1) slabs ahead: one slab at C = 128, none at
     // C = 256 (registers).  Round 6 stamps had this epilogue at 34 k cycles of a 90 k-cycle tile at C = 128 — a chain of exposed round trips; a
-    // lookahead of 3 - 5 slabs (-DVP_XD / -DVP_SD; an fp16 row costs half the registers) shortens wave 0's phase by 27 - 40 % and leaves every
+    // lookahead of 3 - 5 slabs (an fp16 row costs half the registers) shortens wave 0's phase by 27 - 40 % and leaves every
     // launch where it was (the co-resident workgroup fills the gaps either way): the shallow ring stays.  LABNOTES round 6 (b).
-#ifndef VP_XD
-#define VP_XD (NT == 1 ? 2 : 1)
-#endif
-#ifndef VP_SD
-#define VP_SD (NT == 1 ? 2 : 1)
-#endif
-    constexpr int XD = VP_XD < MTT ? VP_XD : MTT, SD = VP_SD < MTT ? VP_SD : MTT;
+    constexpr int XD = NT == 1 ? 2 : 1, SD = XD;
+    static_assert(XD <= MTT, "the lookahead ring is no deeper than the tile has slabs");
     typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
     typedef typename std::conditional<X16, u32x2, u32x4>::type xrow_t;
     xrow_t xin[XD][PER];
@@ -343,16 +307,6 @@ __global__ __launch_bounds__(256, (C == 128 && TT == 128 && WT == 1) ? 3 : 2) vo
             }
         }
     }
-#ifdef DTTS_ABLATE
-    if (p.stats) {
-        asm volatile("s_waitcnt vmcnt(0)");   // the stores' acknowledgements are part of the epilogue's time here
-        VP_STAMP(5);
-        if (tid == 0) {
-            for (int i = 0; i < 5; ++i) atomicAdd(p.stats + i, tq[i + 1] - tq[i]);
-            atomicAdd(p.stats + 5, 1ull);
-        }
-    }
-#endif
     if constexpr (!PS) break;
     if (p.tile_ctr && tid0 == 0) pre[3 * p.B + 1] = (int)gridDim.x + (int)claim;
     __syncthreads();   // the epilogue's staging rows alias the tile the next iteration stages into
@@ -416,15 +370,12 @@ static hipError_t vpair_launch_tt(const VPairParams& p, hipStream_t stream) {
     }
     const int per_cu = std::max(1, std::min((int)(160 * 1024 / lds), (CC == 128 && TT == 128 && WT == 1) ? 3 : 2));
     const long long max_tiles = (long long)p.B * ((p.T + TTe - 1) / TTe);
-    const int grid = (int)std::min<long long>((long long)std::max(1, cus - cu_reserve()) * per_cu, max_tiles);
+    const int grid = (int)std::min<long long>((long long)cus * per_cu, max_tiles);
     if (grid <= 0) return hipSuccess;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, q);
     return hipGetLastError();
 }
 
-#ifndef VP_TT96
-#define VP_TT96 1
-#endif
 // CUs of the current device (cached per device)
 static int vpair_cus() {
     static int cus_dev[64] = {};
@@ -442,30 +393,19 @@ template <int EL>
 static hipError_t vpair_launch_el(const VPairParams& p, int C, hipStream_t stream) {
     // small batches (B = 1: one sentence): the default tiles would leave most CUs without one and the launch takes as long as ONE tile
     // -> half-size tiles (more halo rows recomputed, twice the weight stream per row, but twice the CUs at work)
-    static const bool small_ok = [] { const char* e = ablate_env("DTTS_VP_SMALL"); return !e || atoi(e) != 0; }();
     auto tiles_of = [&](int tt) { return (long long)p.B * ((p.T + (tt - (p.K - 1)) - 1) / (tt - (p.K - 1))); };
     if (C == 256) {
-#ifdef VP_FORCE64    // experiment: 64-row tiles at C = 256 whatever the tile count
-        return vpair_launch_tt<256, 64, EL>(p, stream);
-#endif
-        if (small_ok && 2 * tiles_of(128) <= vpair_cus()) return vpair_launch_tt<256, 64, EL>(p, stream);
+        if (2 * tiles_of(128) <= vpair_cus()) return vpair_launch_tt<256, 64, EL>(p, stream);
         // 128-row tiles, or 96-row ones where only those leave room for TWO workgroups per CU (one workgroup = one wave per SIMD exposes
         // every latency of the memory phases: k = 7 with dilation 5, k = 11 with dilation 3)
         auto lds_of = [&](int tt) { return ((size_t)tt + (size_t)p.dil * (p.K - 1) + std::max(p.dil + 1, 4)) * (256 * 2 + 16) + (size_t)(3 * p.B + 2) * sizeof(int); };
-        if (2 * lds_of(128) > 160 * 1024 && 2 * lds_of(96) <= 160 * 1024 && VP_TT96) return vpair_launch_tt<256, 96, EL>(p, stream);
+        if (2 * lds_of(128) > 160 * 1024 && 2 * lds_of(96) <= 160 * 1024) return vpair_launch_tt<256, 96, EL>(p, stream);
         return vpair_launch_tt<256, 128, EL>(p, stream);
     }
     // 256-row tiles while two workgroups still fit a CU's 160 KB of LDS (all but k = 11 with dilation 5)
     const size_t rows256 = (size_t)256 + (size_t)p.dil * (p.K - 1) + std::max(p.dil + 1, 8);
     const bool big = (rows256 * (128 * 2 + 16) + (size_t)(3 * p.B + 2) * sizeof(int)) * 2 <= 160 * 1024;
-#ifdef VP_FORCE128   // experiment (small grids: long form, B = 1): 128-row tiles at C = 128 whatever the tile count
-    return vpair_launch_tt<128, 128, EL>(p, stream);
-#endif
-    if (small_ok && 2 * tiles_of(256) <= vpair_cus()) return vpair_launch_tt<128, 128, EL>(p, stream);
-#ifdef VP_NT2   // experiment: 2 x 2 waves, two co-tiles per wave
-    if (big) return vpair_launch_tt<128, 256, EL, false, 2>(p, stream);
-    return vpair_launch_tt<128, 192, EL, false, 2>(p, stream);
-#endif
+    if (2 * tiles_of(256) <= vpair_cus()) return vpair_launch_tt<128, 128, EL>(p, stream);
     if (big) return vpair_launch_tt<128, 256, EL>(p, stream);
     // k = 11 with dilation 5: 192-row tiles (two workgroups per CU, persistent) instead of 128-row ones (three, one tile each)
     return vpair_launch_tt<128, 192, EL>(p, stream);

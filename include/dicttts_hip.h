@@ -114,9 +114,9 @@ typedef struct dtts_config {
     int32_t vocoder_range_guard;      /* DTTS_VOC_F16: 1 = start with the fp16 range guard on (dtts_vocoder_range_guard) */
     int32_t debug_redzone;            /* testing aid: 1 = memory-safety mode — every workspace buffer and weight pack sits between 4 KiB red
                                          zones, workspaces are filled with 0xFF (NaN) before each forward; dtts_debug_check verifies the zones */
-    int32_t tune_flags;               /* A/B switches of tuning experiments (tools/ab_*.sh); 0 = the measured defaults.  The library never
+    int32_t tune_flags;               /* A/B switches of tuning experiments (tools/ab_libs.sh); 0 = the measured defaults.  The library never
                                          reads the process environment: arithmetic and layout follow this struct alone.
-                                         The RELEASE library honours exactly the bits that have a parity / bit-identity test behind them and
+                                         The library honours exactly the bits that have a parity / bit-identity test behind them and
                                          refuses every other one (dtts_create: DTTS_E_INVAL):
                                            8  (arithmetic) prior flow launch by launch on the exact-fp32 kernels
                                            9  (schedule)   all ResBlocks of a C <= 64 stage in one launch (less HBM traffic, not faster)
@@ -125,12 +125,8 @@ typedef struct dtts_config {
                                            14 (schedule)   512-row tiles for every k at C = 64
                                            15 (arithmetic) fp32 stream between the three iterations of the C >= 128, k >= 7 ResBlocks (round 5's
                                                            form; the default stores it as fp16: half the bytes, waveform error 5.3e-5 -> 6.7e-5)
-                                         Builds made with -DDTTS_ABLATE (`make ablate`, tools/ab_tune.sh) additionally carry the untested
-                                         experiments — 0 conv_post as its own kernel, 1 upsamplers without the zero-tap skip, 2 static tile
-                                         assignment, 3 no whole-ResBlock fusion at C >= 128, 4 per-launch timer events, 5 128-row tiles for the
-                                         narrow upsamplers, 6 raw (unprojected) dictionary table, 7 two-group phase-shifted ResBlock kernel
-                                         (rblock2.hip), 10 fp32 g_pre_net, 11 fp32 flow conditioning, 16 strided g_pre_net, 17 fp32 MFMA instead of the
-                                         three-piece bf16 products — OR the DTTS_TUNE environment variable in and honour a few schedule-only variables. */
+                                         Bits 0-7, 10, 11, 16, 17 were closed experiments of earlier rounds; their code is retired
+                                         (LABNOTES.md: retired switches) and the bits are refused like any other. */
 } dtts_config;
 
 /* Fill *cfg with the Biaobei Dict-TTS + HifiGAN defaults listed above. */

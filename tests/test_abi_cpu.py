@@ -43,16 +43,16 @@ def test_library_exports_exactly_the_header(lib):
 
 
 def test_release_library_refuses_untested_tune_bits(lib):
-    """a tune_flags bit without a parity / bit-identity test exists only in -DDTTS_ABLATE builds; the release library refuses
-    it loudly (argument validation: no device needed) instead of ignoring it.  The tested bits (8, 9, 12, 13, 14) pass this check."""
+    """the library honours only the tune_flags bits that have a parity / bit-identity test behind them and refuses every other
+    one loudly (argument validation: no device needed) instead of ignoring it.  The tested bits (8, 9, 12, 13, 14, 15) pass this check."""
     cfg = abi.default_config()
-    for bit in (0, 1, 2, 3, 4, 5, 6, 7, 10, 11, 16, 17):
+    for bit in (0, 1, 2, 3, 4, 5, 6, 7, 10, 11, 16, 17) + tuple(range(18, 31)):
         cfg.tune_flags = 1 << bit
         h = abi.C.c_void_p()
         assert lib.dtts_create(abi.C.byref(cfg), abi.C.byref(h)) == -22, bit
         assert b"tune_flags" in lib.dtts_last_error(None)
-    text = open(os.path.join(ROOT, "dict_tts_amd", "csrc", "tune_env.h")).read()
-    assert "TUNE_RELEASE_MASK = (1 << 8) | (1 << 9) | (1 << 12) | (1 << 13) | (1 << 14)" in text
+    text = open(os.path.join(ROOT, "dict_tts_amd", "csrc", "context.hip")).read()
+    assert "TUNE_RELEASE_MASK = (1 << 8) | (1 << 9) | (1 << 12) | (1 << 13) | (1 << 14) | (1 << 15);" in text
 
 
 def test_default_config_matches_reference_hparams(lib):

@@ -1668,7 +1668,7 @@ def test_memory_safety_other_kernel_families(voc_sd):
                                        (16384, "512-row tiles for every k of the C = 64 whole-ResBlock kernel (the default takes 640 rows at k >= 7)")])
 def test_optin_resblock_forms_are_bit_identical_to_the_default(voc_sd, voc_plain, flag, what):
     """round 4's measured-and-not-adopted ResBlock launch forms (dtts_config.tune_flags bits 9, 12, 14; LABNOTES round 4; the two-group kernel of
-    bit 7 lives in the ablation build only since round 5) compute the SAME bits
+    bit 7 was retired, LABNOTES: retired switches) compute the SAME bits
     as the default launches — 70 ragged utterances (several tiles per persistent workgroup, odd tile counts, empty rows) and a B = 24 batch
     large enough for the stage-fused form to engage — and stay clean under the memory-safety mode"""
     from dict_tts_amd import vocoder

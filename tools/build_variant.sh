@@ -5,8 +5,8 @@ set -e
 R=$(cd $(dirname $0)/.. && pwd); C=$R/dict_tts_amd/csrc; X=$R/build/x; mkdir -p $X
 NAME=$1; FLAGS=$2; shift 2
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-function -Wno-pass-failed"
-ALL="conv1d vconv rblock vpair flowstack ops context"
-[ -f $C/rblock2.o ] && grep -q rblock2 $C/Makefile && ALL="$ALL rblock2"
+ALL=$(sed -n 's/^SRCS *= *//p' $C/Makefile | sed 's/\.hip//g')   # the library's sources, as the Makefile lists them
+[ -n "$ALL" ] || { echo "no SRCS in $C/Makefile"; exit 1; }
 OBJS=""
 for s in $ALL; do
   if [[ " $* " == *" $s.hip "* ]]; then

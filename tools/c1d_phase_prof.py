@@ -4,7 +4,8 @@ kernel start / tile staged / contraction done / stores issued, for the four shap
 conv_2, O) — what `rocprofv3 --kernel-trace` cannot split.  Needs the stamped build of the library:
     make -C dict_tts_amd/csrc prof          # build/libdicttts_hip_prof.so (conv1d.hip with -DC1D_PROF=1)
     python tools/c1d_phase_prof.py
-(DTTS_C1D_KS=1|2|4 forces the contraction split for an A/B.)"""
+(The contraction split ks follows the grid, conv1d.hip: launch_short_policy; to stamp another split, set ks there in a variant build:
+tools/build_variant.sh c1dks "-DC1D_PROF=1" conv1d.hip.)"""
 import ctypes, os, sys, shutil
 R = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, R)

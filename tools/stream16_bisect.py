@@ -1,6 +1,5 @@
-"""Which hop of the 16-bit inter-iteration stream changes the waveform, and by how much?  Compares DTTS_VOC_F16 with the fp16 stream (tune 0) against the fp32
-stream (tune_flags bit 15) on the same mels; with the ablation library (LIB=dict_tts_amd/libdicttts_abl.so) DTTS_S16 masks single hops (bit 2 i: iteration 0 -> 1 of
-stage i, bit 2 i + 1: iteration 1 -> 2).  usage: [LIB=...] [DTTS_S16=mask] [B=2 T=48] python tools/stream16_bisect.py"""
+"""How much does the 16-bit inter-iteration stream change the waveform?  Compares DTTS_VOC_F16 with the fp16 stream (tune 0) against the fp32
+stream (tune_flags bit 15) on the same mels.  usage: [LIB=a variant build] [B=2 T=48] python tools/stream16_bisect.py"""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np, torch
@@ -19,4 +18,4 @@ for t in (32768, 0):
     w = v.forward_batch(mel, lens); torch.cuda.synchronize()
     out[t] = w.cpu().numpy().astype(np.float64)
 d = out[0] - out[32768]
-print(f"S16={os.environ.get('DTTS_S16')} B={B} T={T}: rms(ref) {np.sqrt((out[32768]**2).mean()):.4f} rms(diff) {np.sqrt((d**2).mean()):.3e} max {np.abs(d).max():.3e} finite {np.isfinite(out[0]).all()}")
+print(f"B={B} T={T}: rms(ref) {np.sqrt((out[32768]**2).mean()):.4f} rms(diff) {np.sqrt((d**2).mean()):.3e} max {np.abs(d).max():.3e} finite {np.isfinite(out[0]).all()}")
