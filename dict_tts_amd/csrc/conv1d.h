@@ -68,7 +68,7 @@ struct PackedConv {
     int dil = 1, stride = 1, pad = 0;
     int gate_H = 0;
     int poly_half = 0;        // polyphase form of a k = 2u, pad = u/2 transposed convolution: packed channels of the first half of the
-                              // phases have an all-zero LAST tap, those of the second half an all-zero FIRST tap (context.hip:pack_transposed)
+                              // phases have an all-zero LAST tap, those of the second half an all-zero FIRST tap (pack.hip:pack_transposed)
     double flops_per_row = 0; // algorithmic 2*MAC per output row (unpadded), for the roofline report
 };
 

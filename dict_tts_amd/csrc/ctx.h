@@ -1,0 +1,314 @@
+// Internal to libdicttts_hip.so (not installed): the context behind dtts_handle with its workspace arenas and timers, and what the host
+// units share: error reporting, weight access and packing (pack.hip), parameter blocks, the builders dtts_finalize_weights calls.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <cstdlib>
+#include <ctime>
+#include <functional>
+#include <unistd.h>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/dicttts_hip.h"
+#include "conv1d.h"
+#include "ops.h"
+#include "vconv.h"
+#include "rblock.h"
+#include "vpair.h"
+#include "rb2x.h"
+#include "flowstack.h"
+
+// dtts_config.tune_flags: the bits the library honours are listed at TUNE_RELEASE_MASK (context.hip)
+#define DTTS_TUNE(h, bit) (((h)->tune & (bit)) != 0)
+
+namespace dtts {
+
+struct HostTensor {
+    std::vector<float> f;
+    std::vector<int64_t> shape;
+    int64_t numel() const {
+        int64_t n = 1;
+        for (auto s : shape) n *= s;
+        return n;
+    }
+};
+
+// Memory-safety mode (dtts_config.debug_redzone, tests only): every workspace buffer sits between two RED ZONES of RZ bytes, the whole
+// arena is filled with 0xFF (= NaN as fp32 / fp16 / bf16, -1 as an integer) before each forward, so that
+//   * an out-of-range WRITE of a kernel damages a red zone (dtts_debug_check counts the bytes that are no longer 0xFF),
+//   * an out-of-range or stale READ that is actually consumed shows up as NaN in the outputs (buffers are never zero by luck).
+// Weight packs / tables (dev_alloc below) get the same red zones.  Off (the default): no red zones, no fills, no cost.
+constexpr size_t RZ = 4096;
+
+struct Arena {
+    char* base = nullptr;
+    size_t cap = 0, off = 0;
+    bool debug = false;
+    struct Buf { size_t start, bytes; };
+    std::vector<Buf> bufs;   // debug: the buffers handed out since the last reserve / rewind
+    static constexpr int DBG_BUFS = 1024;   // debug mode budgets red zones for this many buffers per forward (the largest forward hands out < 100)
+    hipError_t reserve(size_t n, hipStream_t s) {
+        off = 0;
+        bufs.clear();
+        if (debug) n += (size_t)DBG_BUFS * (RZ + 256);   // red zones + alignment of up to DBG_BUFS buffers (alloc fails beyond: see below)
+        if (n > cap) {
+            if (base) {
+                hipError_t e = hipDeviceSynchronize();
+                if (e != hipSuccess) return e;
+                (void)hipFree(base);
+                base = nullptr;
+                cap = 0;
+            }
+            n = n + n / 8 + (1 << 20);
+            hipError_t e = hipMalloc((void**)&base, n);
+            if (e != hipSuccess) return e;
+            cap = n;
+        }
+        if (debug) return hipMemsetAsync(base, 0xFF, cap, s);
+        return hipSuccess;
+    }
+    void rewind() {   // walk the same layout again (decode re-derives the buffers encode laid out)
+        off = 0;
+        bufs.clear();
+    }
+    template <class T>
+    T* alloc(size_t count) {
+        if (debug) off += RZ;
+        size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
+        if (off + bytes + (debug ? RZ : 0) > cap) return nullptr;
+        T* p = (T*)(base + off);
+        if (debug) bufs.push_back({off, count * sizeof(T)});
+        off += bytes;
+        return p;
+    }
+    void release() {
+        if (base) (void)hipFree(base);
+        base = nullptr;
+        cap = off = 0;
+        bufs.clear();
+    }
+};
+
+struct EncLayer {
+    PackedConv qkv, o, ffn1, ffn2;
+    float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr;
+};
+struct Encoder {
+    std::vector<EncLayer> l;
+    float *lg = nullptr, *lb = nullptr;
+};
+struct WNet {
+    PackedConv cond;
+    std::vector<PackedConv> in, rs;
+    int hidden = 0, layers = 0;
+};
+struct Flow {
+    PackedConv pre, post;
+    WNet wn;
+    int in_coff = 0, out_coff = 0;  // physical channel offsets of the logical x0 / x1 halves (flip parity)
+};
+
+struct TimerSlot {
+    bool enabled = false;
+    std::vector<hipEvent_t> pool;
+    size_t used = 0;
+    double ms_done = 0;
+    int64_t launches = 0;
+};
+
+} // namespace dtts
+
+struct dtts_ctx {
+    dtts_config cfg;
+    std::string err;
+    std::map<std::string, dtts::HostTensor> w;
+    std::vector<void*> allocs;
+    bool debug_rz = false;                                   // dtts_config.debug_redzone
+    int device = 0;                                          // the HIP device that was current at dtts_create: weights and workspaces live there
+    int n_cu = 256;                                          // its compute units
+    struct StaticBuf { char* p; size_t bytes; };
+    std::vector<StaticBuf> rz_static;                         // debug: weight packs / tables (user pointer, payload bytes) between red zones
+    bool acoustic_ready = false, vocoder_ready = false, fft_ready = false;
+    // ---- FFT block stack
+    std::vector<dtts::EncLayer> fft;
+    float *fft_g = nullptr, *fft_b = nullptr, *fft_alpha = nullptr;
+    dtts::Arena a_fft;
+    // ---- acoustic model
+    float *word_emb = nullptr, *pinyin_emb = nullptr;
+    dtts::Encoder sem, lin;
+    dtts::PackedConv s2_q, s2_kT, s2_k, s2_v, s2_o;   // s2_kT: k_transform applied transposed to the query (tensor API); s2_k: to the table rows at upload
+    std::vector<dtts::PackedConv> dur_conv;
+    std::vector<float*> dur_g, dur_b;
+    float *dur_w = nullptr, *dur_bias = nullptr;
+    dtts::PackedConv g_pre, g_pre_poly, dec_pre, dec_out;   // g_pre_poly: the strided g_pre_net as a 3-tap convolution over 4-frame groups (vconv), or empty
+    std::vector<dtts::Flow> flows;  // in execution (reversed) order
+    float* fs_w = nullptr;    // packed weights of the fused prior-flow kernel (flowstack.hip), or null = launch by launch
+    dtts::PackedConv fs_cond;       // cond_layer of ALL blocks as one 1x1 convolution (execution order)
+    dtts::WNet dec_wn;
+    // ---- vocoder
+    dtts::PackedConv conv_pre, conv_post;
+    std::vector<dtts::PackedConv> ups;
+    std::vector<std::vector<dtts::PackedConv>> rb1, rb2;  // [resblock][3]
+    std::vector<std::vector<dtts::PackedConv>> rbf1, rbf2;  // fused-ResBlock copies (taps zero padded), empty where unsupported
+    // ResBlock2 generators (two-dilation rows: resblock_dilation_sizes[j][2] == 0): rb1[i] = convs.{0,1} for the per-convolution path,
+    // rbf1[i] = the same, tap-padded, for the fused kernel (rb2x.hip); rb2 / rbf2 stay empty
+    bool resblock2 = false;
+    int hop = 1;
+    int tune = 0;
+    float *post_w = nullptr, *post_b = nullptr;   // conv_post as [taps][C] fp32 for the fused epilogue of the last ResBlock (rblock.hip), or null
+    // ---- workspaces and per-call state
+    dtts::Arena a_enc, a_dec, a_voc;
+    unsigned* amax_bits = nullptr;  // dtts_wav_to_int16 scratch
+    unsigned long long noise_counter = 0x5EEDull;   // device prior samples (z_p == NULL): one stream per call, offset by noise_seed
+    unsigned long long noise_seed = 0;              // per context (dtts_create: time, pid, device, instance; dtts_set_noise_seed overrides)
+    unsigned long long* ovf_dev = nullptr;          // fp16 range guard counter (DTTS_VOC_F16), device
+    bool guard_on = false;
+    // always-on overflow detector of the 16-bit vocoder modes: non-finite pre-tanh values counted by the conv_post epilogue (device), and the
+    // pinned host word every dtts_hifigan_forward copies it to behind its last kernel (dtts_vocoder_nonfinite reads it without a sync)
+    unsigned* bad_dev = nullptr;
+    volatile unsigned* bad_host = nullptr;
+    // static fp16 analysis of the ResBlock operands (build_vocoder): bound(M) <= wc_lin * M + wc_const for |mel| <= M (worst case, L1),
+    // est_lin * M + est_const = the propagated RMS (an ESTIMATE under independence); 0 / 0 when the mode has no fp16 operands
+    double wc_lin = 0, wc_const = 0, est_lin = 0, est_const = 0;
+    bool voc_span = false;                          // DTTS_TIMER_VOC_CONV: one event pair spans the whole kernel family of a forward (below)
+    int amax_cap = 0;
+    int B = 0, T_w = 0, L_k = 0, P = 0, T_mel = 0;
+    bool encoded = false;
+    float *weo = nullptr, *dur = nullptr, *pron_attn = nullptr, *dict_attn = nullptr, *context = nullptr, *x_mask = nullptr;
+    int64_t* m2w = nullptr;
+    int *mel_lens = nullptr, *lens = nullptr;
+    dtts::TimerSlot timers[DTTS_TIMER_COUNT];
+    // ---- resident dictionary table (dtts_dict_table_upload)
+    int t_entries = 0;
+    int *t_off = nullptr, *t_poff = nullptr, *t_pmmax = nullptr;
+    float *t_keys = nullptr, *t_values = nullptr, *t_key_map = nullptr;
+    int64_t *t_pinyin = nullptr, *t_pinyin_map = nullptr;
+    // ---- speaker conditioning (dtts_text2mel_speakers; modules/portaspeech/model.py:159-163, modules/dict_tts/model.py:44-45,94-96)
+    int spk_kind = 0;                        // 0 = no spk_embed_proj loaded, DTTS_SPK_EMBED (Linear 256 -> hidden), DTTS_SPK_ID (Embedding)
+    int spk_n = 0;                           // DTTS_SPK_ID: rows of the table (num_spk)
+    float *spk_w = nullptr, *spk_bias = nullptr;   // Linear: W^T [256][hidden] + bias [hidden]; Embedding: table [num_spk][hidden]
+    dtts::Arena a_spk;                             // the projected rows [B][hidden] + the id-check flag words, written by dtts_text2mel_speakers
+    float* spk_rows = nullptr;
+    unsigned long long* spk_flag = nullptr;
+    int spk_armed_B = 0;                     // > 0: the next encode adds spk_rows (and disarms)
+    unsigned spk_gen = 0, enc_spk_gen = 0;   // arming count; the one the last encode consumed
+    bool enc_spk = false;                    // the last encode was conditioned on spk_rows
+    // ---- FVAE posterior pass (dtts_text2mel_fetch(DTTS_OUT_POSTERIOR); modules/dict_tts/fvae_semantics.py:84-108), packed when the checkpoint carries
+    // fvae.encoder.*; otherwise post_missing names the first absent tensor and the call is refused.  A shape the pass does not support
+    // still loads for inference: post_unsupported says why, and the posterior call is refused with it
+    bool post_ready = false;
+    std::string post_missing, post_unsupported;
+    dtts::PackedConv post_pre;                     // encoder.pre_net.0: Conv1d(n_mel -> hidden, k = 8, s = 4, p = 2)
+    dtts::WNet post_wn;                            // encoder.wn (fvae_enc_n_layers layers, conditioned on g_sqz)
+    float *post_wt = nullptr, *post_bias = nullptr;   // encoder.out_proj as W^T [hidden][2 latent] + bias [2 latent]
+    std::vector<dtts::Flow> flows_fwd;             // the prior flow's couplings in EXECUTION order of the forward direction (+m, not -m)
+    float* fs_w_fwd = nullptr;               // the same blocks packed for the fused kernel's masked forward form (flowstack.hip: MASK), or null
+    dtts::PackedConv fs_cond_fwd;                  //   with their cond_layers as one 1x1 convolution in forward execution order
+    dtts::Arena a_post;
+};
+
+namespace dtts {
+
+// context.hip: records the message (h == null: for dtts_last_error(NULL)) and returns `code`
+int fail(dtts_ctx* h, int code, const char* fmt, ...);
+
+#define HIPCHK(expr)                                                                                       \
+    do {                                                                                                   \
+        hipError_t _e = (expr);                                                                            \
+        if (_e != hipSuccess) return fail(h, DTTS_E_HIP, "%s failed: %s", #expr, hipGetErrorString(_e));   \
+    } while (0)
+
+#define LAUNCH(expr)                                                                                          \
+    do {                                                                                                      \
+        hipError_t _e = (expr);                                                                               \
+        if (_e != hipSuccess) return fail(h, DTTS_E_HIP, "%s: %s", #expr, hipGetErrorString(_e));             \
+    } while (0)
+
+// ---- pack.hip: device allocations owned by the context, weight access, folding and packing
+void* dev_alloc(dtts_ctx* h, size_t bytes);
+void dev_free(dtts_ctx* h, void* user);
+
+template <class T>
+T* upload(dtts_ctx* h, const std::vector<T>& v) {
+    T* d = (T*)dev_alloc(h, v.size() * sizeof(T));
+    if (!d) return nullptr;
+    if (!v.empty() && hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    return d;
+}
+
+bool pack_conv(dtts_ctx* h, PackedConv& L, int engine, int C_out, int C_in, int K, const std::function<float(int, int, int)>& getw,
+               const std::vector<float>& bias, int dil, int stride, int pad, int gate_H = 0, double flops_per_row = -1);
+
+struct Need {
+    dtts_ctx* h;
+    std::string missing;
+    const HostTensor* get(const std::string& name) {
+        auto it = h->w.find(name);
+        if (it == h->w.end()) {
+            if (missing.empty()) missing = name;
+            return nullptr;
+        }
+        return &it->second;
+    }
+};
+
+const HostTensor* folded_weight(dtts_ctx* h, Need& need, const std::string& base);
+std::vector<float> bias_of(Need& need, const std::string& base);
+bool pack_plain(dtts_ctx* h, Need& need, PackedConv& L, int engine, const std::string& base, int dil, int stride, int pad,
+                bool with_bias = true, int gate_H = 0);
+bool pack_transposed(dtts_ctx* h, Need& need, PackedConv& L, int engine, const std::string& base, int u, int p);
+float* upload_named(dtts_ctx* h, Need& need, const std::string& name);
+
+// ---- pack.hip: parameter blocks of a packed convolution (conv1d: base_params / set_res; vconv: vparams / vparams_x3)
+ConvParams base_params(const float* x, int ldx, int B, int T_in, int T_out, float* y, int ldy);
+void set_res(ConvParams& p, int s, const float* res, int ld);
+VConvParams vparams(const PackedConv& L, const unsigned short* x, const int* lens, int B, int T);
+VConvParams vparams_x3(const PackedConv& L, const float* xf, int ld, float in_slope, const int* lens, int B, int T);
+
+// ---- one event pair around a span of launches (dtts_timer_*); nothing is recorded unless the timer is enabled
+struct Timed {
+    dtts_ctx* h;
+    int which;
+    hipStream_t s;
+    hipEvent_t e1 = nullptr;
+    Timed(dtts_ctx* h_, int which_, hipStream_t s_) : h(h_), which(which_), s(s_) {
+        TimerSlot& t = h->timers[which];
+        if (!t.enabled) return;
+        if (which == DTTS_TIMER_VOC_CONV && h->voc_span) {   // inside a family span: count the launch, record nothing
+            t.launches += 1;
+            return;
+        }
+        if (t.used + 2 > t.pool.size()) {
+            for (int i = 0; i < 256; ++i) {
+                hipEvent_t e;
+                if (hipEventCreate(&e) != hipSuccess) return;
+                t.pool.push_back(e);
+            }
+        }
+        hipEvent_t e0 = t.pool[t.used];
+        e1 = t.pool[t.used + 1];
+        t.used += 2;
+        t.launches += 1;
+        (void)hipEventRecord(e0, s);
+    }
+    void stop() {   // close the span now (the destructor closes it at scope exit otherwise)
+        if (e1) (void)hipEventRecord(e1, s);
+        e1 = nullptr;
+    }
+    ~Timed() { stop(); }
+};
+
+// ---- the builders behind dtts_finalize_weights (text2mel_build.hip, vocoder.hip, fft_blocks.hip)
+int build_acoustic(dtts_ctx* h);
+int build_vocoder(dtts_ctx* h);
+int build_fft(dtts_ctx* h);
+
+} // namespace dtts

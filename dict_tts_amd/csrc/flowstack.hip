@@ -10,7 +10,7 @@
 //     skip co-tiles of the same 32 channels), so the gate and the skip accumulator are wave-local; two barriers per layer;
 //   * contractions on v_mfma_f32_32x32x2_f32 (D[co][t]: A = weights, B = LDS rows); the K order is chosen so that a lane's four
 //     consecutive steps read four consecutive channels: one ds_read_b128 of the state and one 16 B weight fragment per co-tile
-//     feed 16 MFMAs.  Weights stream from L2 in fragment order (context.hip: flowstack_pack);
+//     feed 16 MFMAs.  Weights stream from L2 in fragment order (flowstack_pack below; text2mel_build.hip: flowstack_block);
 //   * the conditioning (cond_layer(g) of all blocks: one [B*T4, hidden] x [hidden, 2048] convolution, launched once before) enters as
 //     the accumulators' initial value together with the bias;
 //   * pre (8 -> 64) and post (64 -> 8) on the VALU; rows outside [0, T4) are forced to zero after every update = the

@@ -10,7 +10,7 @@
 //     block), every wave owns MT=4 row tiles, and weight fragments are prefetched through a register ring PF
 //     k-steps ahead, so L2 latency is covered by MFMA work instead of being exposed per k-step;
 //   * dual-output epilogue: fp32 residual stream + bf16 leaky_relu copy for the next convolution.
-// Same packed-weight format as conv1d.hip (context.hip:pack_conv), same contraction, same rounding points.
+// Same packed-weight format as conv1d.hip (pack.hip:pack_conv), same contraction, same rounding points.
 #include "vconv.h"
 #include "rb_common.h"
 
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256, X3 ? (MT <= 2 ? (NT == 2 ? 3 : (CK == 64 && WC
         tap_lo = second ? 1 : 0;
         tap_hi = second ? p.K : p.K - 1;
     }
-    // in_half (the strided g_pre_net as a 3-tap convolution over 4-row phase groups, context.hip: pack_gpre_poly): the first half of the
+    // in_half (the strided g_pre_net as a 3-tap convolution over 4-row phase groups, text2mel_build.hip: build_acoustic packs it as g_pre_poly): the first half of the
     // INPUT channels has an all-zero first tap, the second half an all-zero last tap — the tap range follows the chunk
     auto chunk_taps = [&](int ci0) {
         if (!p.in_half) return;

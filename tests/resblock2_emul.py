@@ -8,7 +8,7 @@ operand is the producer's bf16(leaky_relu(x)) copy, vconv.hip `pack2bf(lrelu(o, 
     registers"): NO 16-bit stream between the two convolutions in any mode, so tune bit 15 (`stream16`) changes nothing;
   * the operand of convolution m is act(x) taken from the CURRENT x (rb2x.hip: `write_act(xr)` before the loop and again after
     the first convolution — "leaky_relu of the UPDATED x");
-  * weights: one 16-bit pack per convolution (context.hip build_vocoder: pack_conv(..., eng_rb, ...) of convs.{0,1}).
+  * weights: one 16-bit pack per convolution (vocoder.hip build_vocoder: pack_conv(..., eng_rb, ...) of convs.{0,1}).
 
 ``defect`` plants a restatement error for the CPU test of the bounds: "halo" (the second convolution's outermost tap on each side sees
 zeros within one dilation step of a tile seam every `tile` rows: a halo short by d1 rows), "stale" (the second convolution fed
@@ -47,7 +47,7 @@ class Emulator2(Emulator):
     def resblock(self, i, j, x, operand_hook=None):
         k, dils = self.cfg["resblock_kernel_sizes"][j], self.cfg["resblock_dilation_sizes"][j]
         p = f"resblocks.{i * self.nk + j}"
-        w = [self._w(f"{p}.convs.{m}.weight", self.mode) for m in range(2)]      # context.hip pack_conv: f2h_host / f2bf_host
+        w = [self._w(f"{p}.convs.{m}.weight", self.mode) for m in range(2)]      # pack.hip pack_conv: f2h_host / f2bf_host
         b = [self.sd[f"{p}.convs.{m}.bias"] for m in range(2)]
         if self.defect == "rb1_order":
             xt = self._conv(self.act(x), w[0], b[0], k, dils[0])

@@ -1124,7 +1124,7 @@ def test_fp16_validity_is_decided_statically_and_checked_on_every_call(voc_sd, o
 
 
 def _fp16_worst_case_peak(fsd, cfg, M):
-    """numpy restatement of the static worst-case rule (context.hip: vocoder_fp16_analysis) evaluated DIRECTLY at |mel| <= M: the largest
+    """numpy restatement of the static worst-case rule (vocoder.hip: vocoder_fp16_analysis) evaluated DIRECTLY at |mel| <= M: the largest
     bound any fp16 ResBlock operand (leaky_relu(x) at the start of an iteration, leaky_relu(xt)) can reach, per-channel
     u_out[co] = |b[co]| + sum_ci u_in[ci] sum_k |w[co][ci][k]| (transposed convolutions: the largest output phase)."""
     g = lambda k: fsd[k].double().numpy()

@@ -6,7 +6,7 @@ restates).  The fp32 steps between those points (MFMA accumulation, bias, residu
 fused conv_post) are taken in float64: the GPU then differs from this emulator only by fp32 summation order and the rare
 16-bit rounding flips that order causes, far below the fp16 operand noise the oracle comparison has to allow for.
 
-Modes (``dtts_config.vocoder_precision``, dict_tts_amd/csrc/context.hip ``build_vocoder`` / ``hifigan_forward``):
+Modes (``dtts_config.vocoder_precision``, dict_tts_amd/csrc/vocoder.hip ``build_vocoder`` / ``hifigan_forward_fused`` / ``hifigan_forward_x3``):
   * ``"f16"``  (DTTS_VOC_F16): serial convolutions (conv_pre, the polyphase upsamplers, the unfused conv_post) on bf16
     hi / lo split operands with three products; ResBlock convolutions on single fp16 operands, leaky_relu applied in
     fp16 AFTER the conversion; the residual stream between the three iterations of the per-iteration kernel (vpair:
@@ -44,7 +44,7 @@ def _pad(k, d=1):
 class Emulator:
     def __init__(self, sd, cfg, mode="f16", stream16=True, h2=False, fused_post=None, rounding=True, dtype=torch.float64, hook=None):
         """sd: FOLDED state dict (oracle.hifigan_ref.fold_weight_norm), cfg: the generator config.  fused_post: None = as the library
-        decides it (the last stage at C = 32 with >= 2 ResBlock kernels: conv_post + tanh in the last rblock's epilogue, context.hip
+        decides it (the last stage at C = 32 with >= 2 ResBlock kernels: conv_post + tanh in the last rblock's epilogue, vocoder.hip
         `fusable`); False = conv_post on the serial-convolution path (the unfused bf16 testing mode, or any other last width)."""
         assert mode in ("f16", "bf16")
         self.cfg, self.mode, self.rounding, self.dtype, self.hook = cfg, mode, rounding, dtype, hook
@@ -56,7 +56,7 @@ class Emulator:
         if fused_post is None:
             fused_post = self.last_ch == 32 and self.nk >= 2
         self.fused_post = fused_post
-        # context.hip build_vocoder `h2`: ups.1 only, when its polyphase shape suits the H2 instantiation
+        # vocoder.hip build_vocoder `h2`: ups.1 only, when its polyphase shape suits the H2 instantiation
         self.h2_stage = None
         if h2 and mode == "f16" and nup >= 2:
             if (cfg["upsample_rates"][1] * (c0 >> 2)) % 256 == 0 and (c0 >> 1) % 128 == 0:
@@ -69,9 +69,9 @@ class Emulator:
         if key not in self._wcache:
             w = self.sd[name]
             if self.rounding and kind == "f16":
-                w = to_f16(w)            # context.hip pack_conv: ENG_F16 -> f2h_host(v)
+                w = to_f16(w)            # pack.hip pack_conv: ENG_F16 -> f2h_host(v)
             elif self.rounding and kind == "bf16":
-                w = to_bf16(w)           # context.hip pack_conv: ENG_BF16 -> f2bf_host(v)
+                w = to_bf16(w)           # pack.hip pack_conv: ENG_BF16 -> f2bf_host(v)
             self._wcache[key] = w
         return self._wcache[key]
 
@@ -83,8 +83,8 @@ class Emulator:
             return fn(a, w, b)
         if self.mode == "bf16":
             # bf16 mode: the operand is the bf16 copy of leaky_relu taken in fp32 by the producer's epilogue (vconv.hip:409-410 /
-            # rblock.hip:482 / vpair.hip:341 `pack2bf(lrelu(o, p.slope))`; conv_pre's input: context.hip f32_to_bf16_pad of the mel);
-            # weights a single bf16 pack (context.hip pack_conv ENG_BF16)
+            # rblock.hip:482 / vpair.hip:341 `pack2bf(lrelu(o, p.slope))`; conv_pre's input: vocoder.hip f32_to_bf16_pad of the mel);
+            # weights a single bf16 pack (pack.hip pack_conv ENG_BF16)
             return fn(to_bf16(a), self._w(name + ".weight", "bf16"), b)
         if h2:
             # vconv.hip:158-165 (H2): hh = fp16(med3(a, -65504, 65504)), lo = fp16(a - hh); weights a single fp16 pack;
@@ -93,7 +93,7 @@ class Emulator:
             al = to_f16(a - ah)
             wh = self._w(name + ".weight", "f16")
             return fn(al, wh, None) + fn(ah, wh, b)
-        # vconv.hip:168-175 (X3): hi = bf16(lrelu(a)), lo = bf16(a - hi); context.hip pack_conv ENG_BF16X3: whi = bf16(w),
+        # vconv.hip:168-175 (X3): hi = bf16(lrelu(a)), lo = bf16(a - hi); pack.hip pack_conv ENG_BF16X3: whi = bf16(w),
         # wlo = bf16(w - whi); vconv.hip:243-247: Wlo * Xhi + Whi * Xlo + Whi * Xhi (the lo * lo product is not taken)
         ah = to_bf16(a)
         al = to_bf16(a - ah)
@@ -121,7 +121,7 @@ class Emulator:
         return x if y is None else y
 
     def per_iteration(self, i):
-        """does stage i run its ResBlocks on the per-iteration kernel (vpair), for k != 3?  (context.hip build_vocoder: rblock covers
+        """does stage i run its ResBlocks on the per-iteration kernel (vpair), for k != 3?  (vocoder.hip build_vocoder: rblock covers
         C <= 64 every k and k = 3 at C = 128 / 256 (rblock.hip rblock_supported); everything else is vpair)"""
         return (self.cfg["upsample_initial_channel"] >> (i + 1)) >= 128
 
@@ -129,7 +129,7 @@ class Emulator:
     def resblock(self, i, j, x, operand_hook=None):
         """ResBlock1 (hifigan.py:51-58) of stage i, kernel j; the residual x in fp32 (rblock: accumulator registers) except on
         the vpair path, where iterations 0 and 1 store it as fp16 (vpair.hip:335-337 `p.y16`, read back as the next iteration's
-        residual at vpair.hip:323-326) unless tune bit 15 (context.hip `s16`).  operand_hook(m, which, a) may replace the 16-bit operand
+        residual at vpair.hip:323-326) unless tune bit 15 (vocoder.hip `s16`).  operand_hook(m, which, a) may replace the 16-bit operand
         of iteration m's convs1 (which = 1) / convs2 (which = 2)"""
         oh = operand_hook or (lambda m, which, a: a)
         k, dils = self.cfg["resblock_kernel_sizes"][j], self.cfg["resblock_dilation_sizes"][j]
@@ -152,7 +152,7 @@ class Emulator:
         mel = mel.to(self.dtype)
         with torch.no_grad():
             conv = lambda a, w, b: F.conv1d(a, w, b, padding=3)
-            # conv_pre: f16 mode reads the fp32 mel with in_slope 1 (context.hip vparams_x3(conv_pre, mel, ..., 1.f))
+            # conv_pre: f16 mode reads the fp32 mel with in_slope 1 (vocoder.hip vparams_x3(conv_pre, mel, ..., 1.f))
             x = self._serial(conv, mel, "conv_pre", 1.0)
             x = self._call_hook("conv_pre", x)
             stages["conv_pre"] = x
@@ -172,7 +172,7 @@ class Emulator:
                 # rblock.hip:466 lrelu(o / div, 0.01) in fp32 + rblock.hip:492-530 conv_post in exact fp32 (no 16-bit operand)
                 pre = F.conv1d(F.leaky_relu(x, 0.01), w, b, padding=3)
             else:
-                # vconv.hip post_tanh on the serial path: f16 mode split operands with in_slope 0.01 (context.hip vparams_x3(conv_post,
+                # vconv.hip post_tanh on the serial path: f16 mode split operands with in_slope 0.01 (vocoder.hip vparams_x3(conv_post,
                 # Sf, ch, 0.01f)); bf16 mode the bf16 copy Sa = bf16(lrelu(x, 0.01))
                 pre = self._serial(conv, x, "conv_post", 0.01)
             pre = self._call_hook("post", pre)
