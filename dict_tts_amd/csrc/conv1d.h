@@ -67,6 +67,7 @@ struct PackedConv {
     int C_in = 0, C_in_pad = 0, C_out = 0, C_out_pad = 0, K = 1, CK = 64;
     int dil = 1, stride = 1, pad = 0;
     int gate_H = 0;
+    int frag = 32;            // fragment order of w_hi (pack.hip: pack_conv): 32 = v_mfma_f32_32x32x16's A operand, 16 = v_mfma_f32_16x16x32's (vpair.hip only)
     int poly_half = 0;        // polyphase form of a k = 2u, pad = u/2 transposed convolution: packed channels of the first half of the
                               // phases have an all-zero LAST tap, those of the second half an all-zero FIRST tap (pack.hip:pack_transposed)
     double flops_per_row = 0; // algorithmic 2*MAC per output row (unpadded), for the roofline report

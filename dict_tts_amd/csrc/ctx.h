@@ -245,7 +245,7 @@ T* upload(dtts_ctx* h, const std::vector<T>& v) {
 }
 
 bool pack_conv(dtts_ctx* h, PackedConv& L, int engine, int C_out, int C_in, int K, const std::function<float(int, int, int)>& getw,
-               const std::vector<float>& bias, int dil, int stride, int pad, int gate_H = 0, double flops_per_row = -1);
+               const std::vector<float>& bias, int dil, int stride, int pad, int gate_H = 0, double flops_per_row = -1, int frag = 32);
 
 struct Need {
     dtts_ctx* h;
@@ -263,7 +263,7 @@ struct Need {
 const HostTensor* folded_weight(dtts_ctx* h, Need& need, const std::string& base);
 std::vector<float> bias_of(Need& need, const std::string& base);
 bool pack_plain(dtts_ctx* h, Need& need, PackedConv& L, int engine, const std::string& base, int dil, int stride, int pad,
-                bool with_bias = true, int gate_H = 0);
+                bool with_bias = true, int gate_H = 0, int frag = 32);
 bool pack_transposed(dtts_ctx* h, Need& need, PackedConv& L, int engine, const std::string& base, int u, int p);
 float* upload_named(dtts_ctx* h, Need& need, const std::string& name);
 

@@ -73,10 +73,16 @@ uint16_t f2h_host(float f) {
 // Pack one convolution into MFMA fragment order and upload it.  getw(co, ci, tap) addresses the LOGICAL
 // weight; bias is in logical channel order.  gate_H > 0: logical C_out = 2*gate_H, packed co-tiles
 // alternate (tanh[32j..32j+32), sigmoid[H+32j..H+32j+32)).
+// frag: the fragment order.  32 (every kernel but vpair.hip): the A operand of v_mfma_f32_32x32x16 — per (tap, kg-channel group, co-tile)
+// 64 lanes x kg / 2 elements, lane = 32 * half + co % 32, ci = kg * g + (kg / 2) * half + e.  16 (16-bit engines only; rb_common.h:
+// MfmaShape<16>): the A operand of v_mfma_f32_16x16x32 — per (tap, 32-channel group, co-tile, co half) 64 lanes x 8 elements,
+// lane = 16 * kq + co % 16, ci = 32 * g + 8 * kq + e.  Both orders have the same size, slack included.
 bool pack_conv(dtts_ctx* h, PackedConv& L, int engine, int C_out, int C_in, int K,
                const std::function<float(int, int, int)>& getw, const std::vector<float>& bias, int dil, int stride,
-               int pad, int gate_H, double flops_per_row) {
+               int pad, int gate_H, double flops_per_row, int frag) {
+    if (frag != 32 && (frag != 16 || engine == ENG_F32 || engine == ENG_BF16X3)) return false;
     L.engine = engine;
+    L.frag = frag;
     L.C_in = C_in;
     L.C_out = C_out;
     L.K = K;
@@ -87,6 +93,7 @@ bool pack_conv(dtts_ctx* h, PackedConv& L, int engine, int C_out, int C_in, int 
     L.CK = (C_in <= 32) ? 32 : 64;
     L.C_in_pad = (C_in + L.CK - 1) / L.CK * L.CK;
     L.C_out_pad = (C_out + 31) / 32 * 32;
+    if (frag == 16 && L.C_in_pad % 32) return false;   // whole 32-channel k-steps
     L.flops_per_row = flops_per_row >= 0 ? flops_per_row : 2.0 * C_out * C_in * K;
     const int KG = engine == ENG_F32 ? 8 : 16, NCT = L.C_out_pad / 32;
     // + zero k-steps of slack behind the last tap: the kernels prefetch weight fragments past the end instead of clamping.  vconv walks
@@ -108,6 +115,11 @@ bool pack_conv(dtts_ctx* h, PackedConv& L, int engine, int C_out, int C_in, int 
             const int ct = pco / 32, col = pco % 32;
             for (int tap = 0; tap < K; ++tap)
                 for (int ci = 0; ci < C_in; ++ci) {
+                    if (frag == 16) {   // (kg = 16, C_in_pad % 32 == 0)
+                        const int g = ci / 32, kq = ci % 32 / 8, e = ci % 8;
+                        put((((((size_t)tap * (L.C_in_pad / 32) + g) * NCT + ct) * 2 + col / 16) * 64 + kq * 16 + col % 16) * 8 + e, getw(co, ci, tap));
+                        continue;
+                    }
                     const int g = ci / kg, within = ci % kg, half = within / E, e = within % E;
                     put(((((size_t)tap * NG + g) * NCT + ct) * 64 + half * 32 + col) * E + e, getw(co, ci, tap));
                 }
@@ -188,7 +200,7 @@ std::vector<float> bias_of(Need& need, const std::string& base) {
 
 // ordinary Conv1d weight [C_out][C_in][K]
 bool pack_plain(dtts_ctx* h, Need& need, PackedConv& L, int engine, const std::string& base, int dil, int stride, int pad,
-                bool with_bias, int gate_H) {
+                bool with_bias, int gate_H, int frag) {
     const HostTensor* w = folded_weight(h, need, base);
     if (!w) return false;
     const int C_out = (int)w->shape[0], C_in = (int)w->shape[1], K = w->shape.size() > 2 ? (int)w->shape[2] : 1;
@@ -197,7 +209,7 @@ bool pack_plain(dtts_ctx* h, Need& need, PackedConv& L, int engine, const std::s
     const float* p = w->f.data();
     return pack_conv(h, L, engine, C_out, C_in, K,
                      [=](int co, int ci, int tap) { return p[((size_t)co * C_in + ci) * K + tap]; }, bias, dil, stride,
-                     pad, gate_H);
+                     pad, gate_H, -1, frag);
 }
 
 // ConvTranspose1d weight [C_in][C_out][k], stride u, padding p -> polyphase Conv1d with u*C_out channels

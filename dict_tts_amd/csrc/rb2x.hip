@@ -205,7 +205,7 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
             f32x16 unused[NT];
             rb2_contract<EL, MT, NT, NKG, PITCH, 4, false>(xr, ring, act, xlane - ((p.K - 1) / 2) * d * PITCH, wq, S, d * PITCH, unused);
         } else
-            rb_contract<EL, MT, NT, NKG, PITCH, false, 1>(xr, ring, act, xlane - ((p.K - 1) / 2) * d * PITCH, wq, S, d * PITCH, kg_stride);
+            rb_contract<EL, MT, NT, NKG, PITCH, false, 1>(xr, ring, act, xlane - ((p.K - 1) / 2) * d * PITCH, wq, S, d * PITCH);
         if (it == 0) rb_preload<NT>(ring, p.w[1] + wlane, kg_stride);   // the second convolution's first weights fly during barrier + rewrite
         if (p.tile_ctr && it == 1 && tid == 0) pre[3 * p.B + 1] = G + (int)claim;   // the claimed tile, for everyone (read behind the barrier)
         __syncthreads();               // every wave is done reading the operand tile

@@ -115,24 +115,88 @@ __device__ __forceinline__ f32x16 mfma16(const uint4& a, const uint4& b, const f
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
+// ---- MFMA shape of a contraction.  A block of 32 output channels x 32 time rows x 32 input channels is either two
+// v_mfma_f32_32x32x16 (MfmaShape<32>: the default, every kernel but vpair.hip) or four v_mfma_f32_16x16x32 (MfmaShape<16>: 2 channel halves x
+// 2 row halves) — the same MFMA cycles, the same number of 16-byte operand fragments per lane, 16 fp32 accumulators per lane either way.
+// An accumulator QUAD qi (0..3) is four consecutive output channels of one time row in both shapes, so act4, the 8-byte LDS rewrite and
+// the 16-byte fp32 accesses keep their form; which (row, channel) a quad is comes from row() / chan().  The weights are the A operand
+// (its row = output channel), the activations the B operand (its column = time row):
+//   32: A/B lane l <-> row/column l & 31, k = 8 (l >> 5) + j;  D: column l & 31, row (reg & 3) + 8 (reg >> 2) + 4 (l >> 5)
+//   16: A/B lane l <-> row/column l & 15, k = 8 (l >> 4) + j;  D: column l & 15, row 4 (l >> 4) + reg
+// A pack in the shape's fragment order (pack.hip: pack_conv, `frag`) goes with it.
+template <int M>
+struct MfmaShape;
+
+template <>
+struct MfmaShape<32> {
+    static constexpr int FRAG = 32;   // pack_conv's fragment order
+    static constexpr int CI = 16;     // input channels per k-step
+    static constexpr int KB = 32;     // bytes of a k-step within an activation row
+    static constexpr int WF = 1;      // weight fragments per 32-channel co-tile and k-step
+    static constexpr int XF = 1;      // activation fragments per 32-row tile and k-step
+    static constexpr int XROWS = 32;  // rows between two activation fragments of a row tile
+    static constexpr int RD = 4;      // depth of the weight ring in k-steps (fragments RD - 1 steps = 48 input channels ahead)
+    static constexpr int QB = 1;      // accumulator quads that share their four channels (= their bias): quads QB * b ... QB * b + QB - 1
+    typedef f32x16 acc_t;
+    static __device__ __forceinline__ int row(int lane, int qi) { return lane & 31; }                   // row within the 32-row tile
+    static __device__ __forceinline__ int chan(int lane, int qi) { return 8 * qi + 4 * (lane >> 5); }   // first channel within the co-tile
+    static __device__ __forceinline__ int xoff(int lane, int pitch) { return (lane & 31) * pitch + (lane >> 5) * 16; }   // activation fragment of a lane: LDS byte offset
+    static __device__ __forceinline__ f32x4 quad(const acc_t& a, int qi) { return f32x4{a[4 * qi], a[4 * qi + 1], a[4 * qi + 2], a[4 * qi + 3]}; }
+    static __device__ __forceinline__ void set_quad(acc_t& a, int qi, const f32x4& v) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) a[4 * qi + e] = v[e];
+    }
+    template <int EL>
+    static __device__ __forceinline__ void mma(acc_t& d, const uint4* w, const uint4* const (&x)[XF], const acc_t& c) {
+        d = mfma16<EL>(w[0], *x[0], c);
+    }
+};
+
+template <>
+struct MfmaShape<16> {
+    static constexpr int FRAG = 16;
+    static constexpr int CI = 32;
+    static constexpr int KB = 64;
+    static constexpr int WF = 2;      // the two 16-channel halves of a co-tile
+    static constexpr int XF = 2;      // the two 16-row halves of a row tile
+    static constexpr int XROWS = 16;
+    static constexpr int QB = 2;      // (the two row halves)
+    static constexpr int RD = 2;      // fragments one k-step = 32 input channels ahead, in the registers of the 32x32x16 ring (4 x 16 channels)
+    struct acc_t {
+        f32x4 q[4];                   // quad 2 ch + rh: channel half ch, row half rh
+    };
+    static __device__ __forceinline__ int row(int lane, int qi) { return 16 * (qi & 1) + (lane & 15); }
+    static __device__ __forceinline__ int chan(int lane, int qi) { return 16 * (qi >> 1) + 4 * (lane >> 4); }
+    static __device__ __forceinline__ int xoff(int lane, int pitch) { return (lane & 15) * pitch + (lane >> 4) * 16; }
+    static __device__ __forceinline__ f32x4 quad(const acc_t& a, int qi) { return a.q[qi]; }
+    static __device__ __forceinline__ void set_quad(acc_t& a, int qi, const f32x4& v) { a.q[qi] = v; }
+    template <int EL>
+    static __device__ __forceinline__ void mma(acc_t& d, const uint4* w, const uint4* const (&x)[XF], const acc_t& c) {
+#pragma unroll
+        for (int ch = 0; ch < 2; ++ch)
+#pragma unroll
+            for (int rh = 0; rh < 2; ++rh) {
+                if constexpr (EL == EL_F16)
+                    d.q[2 * ch + rh] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w[ch]), __builtin_bit_cast(f16x8, *x[rh]), c.q[2 * ch + rh], 0, 0, 0);
+                else
+                    d.q[2 * ch + rh] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w[ch]), __builtin_bit_cast(bf16x8, *x[rh]), c.q[2 * ch + rh], 0, 0, 0);
+            }
+    }
+};
+
 constexpr int RB_GUARD = 40;  // zero rows on both sides of the LDS tile (>= max pad 25 + one padded tap + one prefetched tap, dilation 5)
 
-// acc += W * act, all taps; act is the LDS tile (bf16, pitch PITCH), weights in fragment order [step][co-tile][lane]
-// first PF = 3 weight fragments of a convolution (issued early: before the barriers / activation writes that precede it)
-template <int NT>
-__device__ __forceinline__ void rb_preload(uint4 (&ring)[4][NT], const uint4* w, int kg_stride) {
+// acc += W * act, all taps; act is the LDS tile (bf16, pitch PITCH), weights in fragment order [step][co-tile][lane] ([step][co-tile][half][lane], MfmaShape<16>)
+// first RD - 1 weight fragment sets of a convolution (issued early: before the barriers / activation writes that precede it)
+template <int NTW, int RD>
+__device__ __forceinline__ void rb_preload(uint4 (&ring)[RD][NTW], const uint4* w, int kg_stride) {
 #pragma unroll
-    for (int s = 0; s < 3; ++s)
+    for (int s = 0; s < RD - 1; ++s)
 #pragma unroll
-        for (int n = 0; n < NT; ++n) ring[s][n] = w[(size_t)s * kg_stride + n * 64];
+        for (int n = 0; n < NTW; ++n) ring[s][n] = w[(size_t)s * kg_stride + n * 64];
 }
 
-// acc += W * act over all taps.  Steps are processed 4 at a time (= TU taps); inside a group every LDS / global
-// offset is a compile-time immediate off two VGPR bases that advance once per group, so the loop body is MFMAs,
-// ds_read_b128, global_load_dwordx4 and ~4 address instructions.  Weight fragments run 3 steps ahead (register ring),
-// activation fragments 1 step ahead.  The packed weights carry >= 4 zero steps of slack, the LDS tile >= one extra tap
-// of guard rows, so the prefetches past the last step need no clamping.
-// One group of 4 k-steps of the contraction (see rb_contract).  CINIT: the very first MFMA of every accumulator tile
+// One group of 4 k-steps of the contraction (see rb_contract; a k-step is SH::CI input channels of one tap).  CINIT: the very first MFMA of every accumulator tile
 // takes its C operand from cinit[n] (the bias pattern of this lane's 16 channel slots, identical for every row tile), so
 // the accumulators need no initialisation pass at all.
 // MH > 1: the wave owns MH * MT row tiles, processed as MH passes of MT tiles per weight fragment (pass h covers rows
@@ -142,42 +206,61 @@ __device__ __forceinline__ void rb_preload(uint4 (&ring)[4][NT], const uint4* w,
 // burst at the top of a step (a double buffer), row tile m's next fragment is read right behind the MFMAs that consumed the current one and lands while the other
 // row tiles' MFMAs run: eight waves' bursts no longer queue on the CU's LDS pipe in front of the matrix pipe (-1.5 ... -5.9 % per kernel), MT * 4 registers less.
 // The scheduling barriers around the read keep it where it is written (+0.4 % without them).  (The line "(NT == 1 here)" below: the read follows the LAST co-tile's MFMA.)
-template <int EL, int MT, int NT, int NKG, int PITCH, bool CINIT, int MH = 1>
-__device__ __forceinline__ void rb_group(f32x16 (&acc)[MH * MT][NT], const f32x16 (&cinit)[NT], uint4 (&ring)[4][NT], uint4 (&xa)[MT],
-                                         const char* act, const uint4* wpf, int xb, int dilP, int g) {
+// NKG: k-steps per tap (C / SH::CI).
+template <int EL, int MT, int NT, int NKG, int PITCH, bool CINIT, int MH = 1, class SH = MfmaShape<32>>
+__device__ __forceinline__ void rb_group(typename SH::acc_t (&acc)[MH * MT][NT], const typename SH::acc_t (&cinit)[NT], uint4 (&ring)[SH::RD][NT * SH::WF],
+                                         uint4 (&xa)[MT], const char* act, const uint4* wpf, int xb, int dilP, int g) {
     constexpr int GPT = (NKG >= 4) ? NKG / 4 : 1;     // groups per tap
-    constexpr int KGS = (NKG / 2) * 64;               // uint4 elements between consecutive steps (= NCT * 64, NCT = NKG / 2)
+    constexpr int KGS = NKG * SH::CI * 2 * SH::WF;    // uint4 elements between consecutive steps (= NCT * 64 per fragment of a co-tile, NCT = C / 32)
     constexpr int HSTRIDE = MT * 32 * PITCH;          // LDS bytes between two passes
+    constexpr int RD = SH::RD, WF = SH::WF, KB = SH::KB;
+    static_assert(4 % RD == 0, "a group of 4 steps is whole turns of the ring");
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
 #pragma unroll
         for (int h = 0; h < MH; ++h) {
             if (h == 0) {
 #pragma unroll
-                for (int n = 0; n < NT; ++n) ring[(u + 3) & 3][n] = wpf[u * KGS + n * 64];
+                for (int n = 0; n < NT * WF; ++n) ring[(u + RD - 1) % RD][n] = wpf[u * KGS + n * 64];
             }
-            int off;   // activation fragments of the next (step, pass)
+            // The activation fragments of a (step, pass) are NP = MT * XF positions p = XF * m + f (row tile m, fragment f), consumed in this order;
+            // MT of them are live at a time, position p in register set p % MT, and the one MT positions ahead is read behind the MFMAs that
+            // consumed position p: from this (step, pass) at `cur` (XF = 2, p < MT), or from the next at `off`.
+            constexpr int NP = MT * SH::XF;
+            int cur = 0;   // this (step, pass)
+            if constexpr (SH::XF > 1) {
+                if constexpr (NKG >= 4) cur = xb + ((g * 4 + u) % NKG) * KB + h * HSTRIDE;
+                else cur = xb + (u / NKG) * dilP + (u % NKG) * KB + h * HSTRIDE;
+            }
+            int off;   // the next (step, pass)
             if (h + 1 < MH) {
                 // same step, next pass
-                if constexpr (NKG >= 4) off = xb + ((g * 4 + u) % NKG) * 32 + (h + 1) * HSTRIDE;
-                else off = xb + (u / NKG) * dilP + (u % NKG) * 32 + (h + 1) * HSTRIDE;
+                if constexpr (NKG >= 4) off = xb + ((g * 4 + u) % NKG) * KB + (h + 1) * HSTRIDE;
+                else off = xb + (u / NKG) * dilP + (u % NKG) * KB + (h + 1) * HSTRIDE;
             } else if constexpr (NKG >= 4) {
                 const int kgn = (g * 4 + u + 1);            // k-group index within the tap (may be NKG: next tap)
-                off = (u == 3 && g == GPT - 1) ? xb + dilP : xb + (kgn % NKG) * 32;
+                off = (u == 3 && g == GPT - 1) ? xb + dilP : xb + (kgn % NKG) * KB;
             } else {
                 const int un = u + 1;                        // step within the group of TU taps
-                off = xb + (un / NKG) * dilP + (un % NKG) * 32;
+                off = xb + (un / NKG) * dilP + (un % NKG) * KB;
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int m = 0; m < MT; ++m)
 #pragma unroll
                 for (int n = 0; n < NT; ++n) {
-                    if (CINIT && u == 0) acc[h * MT + m][n] = mfma16<EL>(ring[u][n], xa[m], cinit[n]);
-                    else acc[h * MT + m][n] = mfma16<EL>(ring[u][n], xa[m], acc[h * MT + m][n]);
-                    if (n == NT - 1) {   // row tile m's fragment of the next step, behind the MFMAs that read the current one (NT == 1 here)
+                    const uint4* xf[SH::XF];
+#pragma unroll
+                    for (int f = 0; f < SH::XF; ++f) xf[f] = &xa[(m * SH::XF + f) % MT];
+                    if (CINIT && u == 0) SH::template mma<EL>(acc[h * MT + m][n], &ring[u % RD][n * WF], xf, cinit[n]);
+                    else SH::template mma<EL>(acc[h * MT + m][n], &ring[u % RD][n * WF], xf, acc[h * MT + m][n]);
+                    if (n == NT - 1) {   // the fragments MT positions ahead, behind the MFMAs that read row tile m's (NT == 1 here)
                         __builtin_amdgcn_sched_barrier(0);
-                        xa[m] = *(const uint4*)(act + off + m * 32 * PITCH);
+#pragma unroll
+                        for (int f = 0; f < SH::XF; ++f) {
+                            const int p = m * SH::XF + f, pn = (p + MT) % NP;
+                            xa[p % MT] = *(const uint4*)(act + (p + MT < NP ? cur : off) + (pn / SH::XF * 32 + pn % SH::XF * SH::XROWS) * PITCH);
+                        }
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
@@ -186,27 +269,36 @@ __device__ __forceinline__ void rb_group(f32x16 (&acc)[MH * MT][NT], const f32x1
     }
 }
 
-// acc (+)= W * act over all taps.  Steps are processed 4 at a time (= TU taps); inside a group every LDS / global
-// offset is a compile-time immediate off two bases that advance once per group, so the loop body is MFMAs,
-// ds_read_b128, global_load_dwordx4 and ~4 address instructions.  Weight fragments run 3 steps ahead (register ring),
-// activation fragments 1 step ahead.  The packed weights carry >= 4 zero steps of slack, the LDS tile >= one extra tap
-// of guard rows, so the prefetches past the last step need no clamping.  CINIT: acc = cinit + W * act (acc not read).
-template <int EL, int MT, int NT, int NKG, int PITCH, bool CINIT = false, int MH = 1>
-__device__ __forceinline__ void rb_contract(f32x16 (&acc)[MH * MT][NT], uint4 (&ring)[4][NT], const char* act, int xrow0, const uint4* w,
-                                            int S, int dilP, int kg_stride_unused, const f32x16 (*cinit)[NT] = nullptr) {
+// acc (+)= W * act over all taps.  k-steps (SH::CI input channels of one tap: 16 or 32) are processed 4 at a time (a group =
+// TU taps, or 1 / GPT of a tap); inside a group every LDS / global offset is a compile-time immediate off two bases that advance once
+// per group, so the loop body is MFMAs, ds_read_b128, global_load_dwordx4 and ~4 address instructions.  CINIT: acc = cinit + W * act
+// (acc not read).  What the prefetches read past the end, and why neither needs a clamp:
+//   weights: fragments run RD - 1 steps ahead, so the last group loads RD - 1 steps behind step S - 1: 3 x 16 channels (MfmaShape<32>) or
+//     1 x 32 channels (MfmaShape<16>), i.e. at most three 16-channel steps of every co-tile.  pack_conv appends C_in_pad / 16 + 8 >= 10
+//     zero 16-channel steps to every pack, in either fragment order (the two orders have the same size per 32 channels);
+//   activations: MT fragment positions ahead, i.e. at most the first k-group of the tap BEHIND the last one (row offset K * dil from the
+//     wave's first row, the same 32 rows per row tile in both shapes, bytes 0 .. SH::KB - 1 <= 63 of a row): one spare tap of rows, which
+//     vpair's launcher allots (TT + dil (K - 1) + max(dil + 1, .) rows for c1, TT + K + 1 for c2) and rblock's RB_GUARD covers.
+template <int EL, int MT, int NT, int NKG, int PITCH, bool CINIT = false, int MH = 1, class SH = MfmaShape<32>>
+__device__ __forceinline__ void rb_contract(typename SH::acc_t (&acc)[MH * MT][NT], uint4 (&ring)[SH::RD][NT * SH::WF], const char* act, int xrow0,
+                                            const uint4* w, int S, int dilP, const typename SH::acc_t (*cinit)[NT] = nullptr) {
+    typedef typename SH::acc_t acc_t;
     constexpr int TU = (NKG >= 4) ? 1 : 4 / NKG;      // taps per group of 4 steps
     constexpr int GPT = (NKG >= 4) ? NKG / 4 : 1;     // groups per tap
-    constexpr int KGS = (NKG / 2) * 64;
-    uint4 xa[MT];
+    constexpr int KGS = NKG * SH::CI * 2 * SH::WF;
+    uint4 xa[MT];   // the first MT fragment positions of step 0 (rb_group)
 #pragma unroll
-    for (int m = 0; m < MT; ++m) xa[m] = *(const uint4*)(act + xrow0 + m * 32 * PITCH);
-    const uint4* wpf = w + 3 * KGS;                   // prefetch pointer, 3 steps ahead
+    for (int p = 0; p < MT; ++p) xa[p] = *(const uint4*)(act + xrow0 + (p / SH::XF * 32 + p % SH::XF * SH::XROWS) * PITCH);
+    const uint4* wpf = w + (SH::RD - 1) * KGS;        // prefetch pointer, RD - 1 steps ahead
     int xb = xrow0;                                   // LDS byte offset of (tap of this group, kg 0)
     int g = 0;
     int s0 = 0;
     if constexpr (CINIT) {
-        if (S > 0) {
-            rb_group<EL, MT, NT, NKG, PITCH, true, MH>(acc, *cinit, ring, xa, act, wpf, xb, dilP, 0);
+        // (MfmaShape<16> has no S == 0 arm: the arm's copies of 4 * MH * MT * NT accumulator quads at the join cost the new shape 4 - 10
+        // registers.  Its only caller, vpair_launch, refuses K < 3 (vpair_supported), so S = K * NKG >= 3 there, and vpair_kernel returns
+        // before staging anything if it is ever entered with K < 1.  MfmaShape<32> keeps the arm, see below)
+        if (SH::FRAG == 16 || S > 0) {
+            rb_group<EL, MT, NT, NKG, PITCH, true, MH, SH>(acc, *cinit, ring, xa, act, wpf, xb, dilP, 0);
             s0 = 4;
             wpf += 4 * KGS;
             if constexpr (NKG >= 4) {
@@ -225,8 +317,8 @@ __device__ __forceinline__ void rb_contract(f32x16 (&acc)[MH * MT][NT], uint4 (&
         }
     }
     for (; s0 < S; s0 += 4) {
-        const f32x16(&dummy)[NT] = *(const f32x16(*)[NT])acc[0];
-        rb_group<EL, MT, NT, NKG, PITCH, false, MH>(acc, dummy, ring, xa, act, wpf, xb, dilP, g);
+        const acc_t(&dummy)[NT] = *(const acc_t(*)[NT])acc[0];
+        rb_group<EL, MT, NT, NKG, PITCH, false, MH, SH>(acc, dummy, ring, xa, act, wpf, xb, dilP, g);
         wpf += 4 * KGS;
         if constexpr (NKG >= 4) {
             if (++g == GPT) {

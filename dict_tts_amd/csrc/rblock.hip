@@ -316,9 +316,9 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
             // S > 0 always, which the compiler cannot know.  The two tests on S and the S == 0 arm (acc = cinit, by way of rb_contract) stay: without them,
             // or with the arm written out, hipcc allocates the C = 32 kernels' registers differently (LABNOTES: retired switches)
             if (S) rb2_contract<EL, MT, NT, NKG, PITCH, 4, true>(acc, ring, act, xlane - ((Kr - 1) / 2) * d * PITCH, R.w1[it] + wlane, S, d * PITCH, cinit);
-            else rb_contract<EL, MT, NT, NKG, PITCH, true, 1>(acc, ring, act, 0, R.w1[it] + wlane, 0, 0, kg_stride, &cinit);
+            else rb_contract<EL, MT, NT, NKG, PITCH, true, 1>(acc, ring, act, 0, R.w1[it] + wlane, 0, 0, &cinit);
         } else
-            rb_contract<EL, MT, NT, NKG, PITCH, true, 1>(acc, ring, act, xlane - ((Kr - 1) / 2) * d * PITCH, R.w1[it] + wlane, S, d * PITCH, kg_stride, &cinit);
+            rb_contract<EL, MT, NT, NKG, PITCH, true, 1>(acc, ring, act, xlane - ((Kr - 1) / 2) * d * PITCH, R.w1[it] + wlane, S, d * PITCH, &cinit);
         rb_preload<NT>(ring, R.w2[it] + wlane, kg_stride);   // next conv's first weights fly during barrier + write
         RB_T(2);
         if constexpr (!TB) __syncthreads();   // every wave is done reading A (TB: xt has its own buffer, last read before the previous barrier)
@@ -340,7 +340,7 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
         if constexpr (REAL_STEPS) {
             if (S) rb2_contract<EL, MT, NT, NKG, PITCH, 4, false>(xr, ring, act2, xlane - ((Kr - 1) / 2) * PITCH, R.w2[it] + wlane, S, PITCH, cinit);
         } else
-            rb_contract<EL, MT, NT, NKG, PITCH, false, 1>(xr, ring, act2, xlane - ((Kr - 1) / 2) * PITCH, R.w2[it] + wlane, S, PITCH, kg_stride);
+            rb_contract<EL, MT, NT, NKG, PITCH, false, 1>(xr, ring, act2, xlane - ((Kr - 1) / 2) * PITCH, R.w2[it] + wlane, S, PITCH);
         if (it < 2) rb_preload<NT>(ring, R.w1[it + 1] + wlane, kg_stride);
         if (PS && p.tile_ctr && last_rb && it == 2 && tid == 0) pre[3 * p.B + 1] = G + (int)claim;   // the claimed tile, for everyone (read behind the barrier)
         RB_T(6);

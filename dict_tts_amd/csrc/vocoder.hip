@@ -145,6 +145,19 @@ bool pack_rb_fused(dtts_ctx* h, Need& need, PackedConv& L, int eng, const std::s
     return ok;
 }
 
+// Does the fused forward run this ResBlock1 (ch channels, kernel size k, dilations d[0..2], operand engine eng_rb) iteration by iteration on
+// vpair.hip?  THE predicate: build_vocoder packs the block's convolutions in vpair's fragment order exactly where it holds, rb_path sends the
+// block to vpair exactly where it holds, and the per-convolution path refuses a pack in another order than its own.
+// what vpair_kernel<ch> assumes of a pack it walks: ch x ch x k, nothing padded, in its fragment order
+bool vpair_pack_fits(const PackedConv& L, int ch, int k) {
+    return L.C_in == ch && L.C_out == ch && L.C_in_pad == ch && L.C_out_pad == ch && L.K == k && L.frag == vpair_mfma_shape(ch);
+}
+bool vpair_runs(const dtts_config& c, bool resblock2, int eng_rb, int ch, int k, int d0, int d1, int d2) {
+    const bool fuse = c.vocoder_precision == DTTS_VOC_F16 || !c.vocoder_unfused;   // (as in hifigan_forward_fused)
+    return fuse && !resblock2 && eng_rb != ENG_BF16X3 && !rblock_supported(ch, k) && vpair_supported(ch, k, d0) && vpair_supported(ch, k, d1) &&
+           vpair_supported(ch, k, d2);
+}
+
 } // namespace
 
 namespace dtts {
@@ -192,13 +205,27 @@ int build_vocoder(dtts_ctx* h) {
     const bool rb2x = h->resblock2;
     for (int i = 0; ok && i < c.n_upsamples * nk; ++i) {   // ResBlock1: convs1 (dilated) / convs2; ResBlock2: convs.{0,1}, both dilated
         const int j = i % nk, k = c.resblock_kernel_sizes[j], n = rb2x ? 2 : 3;
+        const int ch = c.upsample_initial_channel >> (i / nk + 1);
         const std::string r = v + "resblocks." + std::to_string(i);
+        // Each pack in the fragment order of the kernel that consumes it in THIS context (a context never uses both orders of a layer):
+        // vpair's where the ResBlock runs on vpair.hip, the common order for vconv (vocoder_unfused, the per-convolution fallback) and
+        // conv1d (DTTS_VOC_BF16X3).
+        const int* dl = c.resblock_dilation_sizes[j];
+        const bool vp = vpair_runs(c, rb2x, eng_rb, ch, k, dl[0], dl[1], dl[2]);
+        const int frag = vp ? vpair_mfma_shape(ch) : 32;
         h->rb1[i].resize(n);
         if (!rb2x) h->rb2[i].resize(3);
         for (int mth = 0; ok && mth < n; ++mth) {
             const int d = c.resblock_dilation_sizes[j][mth];
-            ok = ok && pack_plain(h, need, h->rb1[i][mth], eng_rb, r + (rb2x ? ".convs." : ".convs1.") + std::to_string(mth), d, 1, (k * d - d) / 2);
-            if (!rb2x) ok = ok && pack_plain(h, need, h->rb2[i][mth], eng_rb, r + ".convs2." + std::to_string(mth), 1, 1, (k - 1) / 2);
+            ok = ok && pack_plain(h, need, h->rb1[i][mth], eng_rb, r + (rb2x ? ".convs." : ".convs1.") + std::to_string(mth), d, 1, (k * d - d) / 2, true, 0, frag);
+            if (!rb2x) ok = ok && pack_plain(h, need, h->rb2[i][mth], eng_rb, r + ".convs2." + std::to_string(mth), 1, 1, (k - 1) / 2, true, 0, frag);
+            // vpair walks a pack with the strides of ch x ch x k: the checkpoint's tensors must have the shape the configuration states
+            if (ok && vp && !vpair_pack_fits(h->rb1[i][mth], ch, k))
+                return fail(h, DTTS_E_INVAL, "%s%d: weight shape [%d, %d, %d] is not the configured [%d, %d, %d]", (r + ".convs1.").c_str(), mth, h->rb1[i][mth].C_out,
+                            h->rb1[i][mth].C_in, h->rb1[i][mth].K, ch, ch, k);
+            if (ok && vp && !vpair_pack_fits(h->rb2[i][mth], ch, k))
+                return fail(h, DTTS_E_INVAL, "%s%d: weight shape [%d, %d, %d] is not the configured [%d, %d, %d]", (r + ".convs2.").c_str(), mth, h->rb2[i][mth].C_out,
+                            h->rb2[i][mth].C_in, h->rb2[i][mth].K, ch, ch, k);
         }
     }
     // fused ResBlock kernel (bf16 mode, narrow stages): the same weights with the tap axis zero padded so that the
@@ -224,9 +251,8 @@ int build_vocoder(dtts_ctx* h) {
         const int j = i % nk, k = c.resblock_kernel_sizes[j];
         const int ch = c.upsample_initial_channel >> (i / nk + 1);
         if (!rblock_supported(ch, k)) {
-            bool vp = h->rb1[i][0].C_in_pad == ch;
-            for (int mth = 0; mth < 3; ++mth) vp = vp && vpair_supported(ch, k, c.resblock_dilation_sizes[j][mth]);
-            if (eng_rb == ENG_F16 && !vp)
+            const int* dl = c.resblock_dilation_sizes[j];
+            if (eng_rb == ENG_F16 && !vpair_runs(c, rb2x, eng_rb, ch, k, dl[0], dl[1], dl[2]))
                 return fail(h, DTTS_E_INVAL, "DTTS_VOC_F16 needs ResBlock widths 32/64/128/256 and odd kernels 3..11 (resblock %d: %d channels, k=%d); use DTTS_VOC_BF16X3", i, ch, k);
             continue;
         }
@@ -339,7 +365,7 @@ RbPath rb_path(const dtts_ctx* h, bool fuse, int ch, size_t rb) {
     if (fuse && !h->rbf1[rb].empty()) return RB_WHOLE;
     if (h->resblock2) return RB_CONVS;
     const auto& c1 = h->rb1[rb];
-    return fuse && vpair_supported(ch, c1[0].K, c1[0].dil) && vpair_supported(ch, c1[2].K, c1[2].dil) && c1[0].C_in_pad == ch ? RB_VPAIR : RB_CONVS;
+    return fuse && vpair_runs(h->cfg, false, c1[0].engine, ch, c1[0].K, c1[0].dil, c1[1].dil, c1[2].dil) ? RB_VPAIR : RB_CONVS;
 }
 
 // Which stages run ALL their ResBlocks in one launch (rblock.hip; OPT-IN, tune bit 9 — measured: HBM traffic -0.36 MB / mel frame, vocoder
@@ -491,6 +517,9 @@ struct VocRun {
     int vpair(int j) {
         const auto& c1 = h->rb1[(size_t)i * nk + j];
         const auto& c2 = h->rb2[(size_t)i * nk + j];
+        for (int mth = 0; mth < 3; ++mth)   // (build_vocoder packed and checked them where vpair_runs holds)
+            if (!vpair_pack_fits(c1[mth], ch, c1[0].K) || !vpair_pack_fits(c2[mth], ch, c1[0].K))
+                return fail(h, DTTS_E_STATE, "resblock %d is not packed for vpair<%d>", i * nk + j, ch);
         const float* xin = Xf;
         for (int mth = 0; mth < 3; ++mth) {
             VPairParams vp;
@@ -537,6 +566,7 @@ struct VocRun {
     int convs(int j) {
         if (exact) return fail(h, DTTS_E_STATE, "DTTS_VOC_F16: resblock %d has no fused kernel", i * nk + j);   // build_vocoder rejects such configs
         const auto& c1 = h->rb1[(size_t)i * nk + j];
+        if (c1[0].frag != 32) return fail(h, DTTS_E_STATE, "resblock %d is packed for vpair, not for the per-convolution kernels", i * nk + j);   // (vpair_runs decides both)
         const int n = h->resblock2 ? 2 : 3;
         for (int mth = 0; mth < n; ++mth) {
             const bf* xa = mth == 0 ? Xa : Ra;

@@ -22,6 +22,8 @@ namespace dtts {
 // C = 256 (NT = 2 co-tiles per wave): the stage-1 ResBlocks; 128-row tiles only.
 // WT = 2 (C = 128; no launch configuration selects it: 1.3 / 4 % slower, LABNOTES (K)): the four waves as 2 (time) x 2 (output channels), two co-tiles per wave — every activation fragment read from LDS feeds two
 // MFMAs instead of one (half the ds_read_b128 traffic; twice the weight fragments through the texture path, as at C = 256).
+// Both contractions run on the MFMA shape of vpair.h: vpair_mfma_shape (rb_common.h: MfmaShape): all row / channel arithmetic below goes through its helpers
+// (row / chan of an accumulator quad, a lane's activation-fragment offset), and w1 / w2 arrive in its fragment order.
 // X16 (round 6; EL_F16 only): the INPUT stream x is fp16 — iterations 1 and 2 of a ResBlock, whose predecessor stored its result with
 // p.y16.  fp16(x) is exactly what the fp32 stream's staging computed as the convolution operand, so c1's operands keep their bits; what
 // changes is the residual add (x16 + xt instead of x32 + xt).  The staging loads 8 channels per thread (half the bytes, half the
@@ -31,11 +33,14 @@ template <int C, int TT, int EL, bool GUARD, int WT = 1, bool X16 = false>
 __global__ __launch_bounds__(256, (C == 128 && TT == 128 && WT == 1) ? 3 : 2) void vpair_kernel(const VPairParams p) {
     static_assert(!X16 || EL == EL_F16, "the 16-bit stream is fp16");
     const int mode = p.mode;
+    if (p.K < 1) return;   // (uniform; vpair_launch refuses K < 3: the contractions assume at least one k-step, rb_common.h rb_contract)
     constexpr bool PS = !(C == 128 && TT == 128 && WT == 1);   // persistent workgroups (below); not the 3-per-CU configuration, which loses 9 % with them
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int WC = 4 / WT, TW = TT / WT;     // waves over the output channels; rows of a time-wave
     constexpr int MT = (TW == 192 || TW == 96) ? 3 : (TW == 64 ? 2 : 4), NT = C / (32 * WC), MH = TW / (32 * MT), MTT = MT * MH;   // TW = 192: two passes of 3 row tiles
-    constexpr int PITCH = C * 2 + 16, NKG = C / 16, NCT = C / 32;
+    typedef MfmaShape<vpair_mfma_shape(C)> SH;   // MFMA shape of both contractions; the packs come in its fragment order (vpair.h)
+    typedef typename SH::acc_t acc_t;
+    constexpr int PITCH = C * 2 + 16, NKG = C / SH::CI, NCT = C / 32, KGS = NCT * SH::WF * 64;   // KGS: uint4 elements of a k-step's weights
     constexpr int EP = C * 4 + 16, F4 = C / 4;
     static_assert(NCT == WC * NT && (NT == 1 || MH == 1) && WT * WC == 4, "4 waves: WT over time x WC over the output channels");
     const int tid0 = threadIdx.x;
@@ -91,9 +96,9 @@ __global__ __launch_bounds__(256, (C == 128 && TT == 128 && WT == 1) ? 3 : 2) vo
     const long long brow = (long long)b * p.T;
 
     int n_ovf = 0;
-    uint4 ring[4][NT];
-    const size_t wlane = (size_t)wc * NT * 64 + lane;   // the wave's first co-tile
-    rb_preload<NT>(ring, p.w1 + wlane, NCT * 64);   // c1's first weights fly while the tile is staged
+    uint4 ring[SH::RD][NT * SH::WF];
+    const size_t wlane = (size_t)wc * NT * SH::WF * 64 + lane;   // the wave's first co-tile
+    rb_preload(ring, p.w1 + wlane, KGS);   // c1's first weights fly while the tile is staged
 
     // ---- stage bf16(leaky_relu(x)) for rows [t0 - h2 - h1, t0 - h2 + TT + h1) ; zero outside the utterance.
     // Buffer loads over the utterance [0, len) x C: an out-of-range row (t < 0 wraps to a huge unsigned offset,
@@ -164,50 +169,49 @@ __global__ __launch_bounds__(256, (C == 128 && TT == 128 && WT == 1) ? 3 : 2) vo
             }
         }
     }
-    // this lane's bias quads (channel of accumulator slot 4q+e of co-tile n: (wc * NT + n) * 32 + 8q + 4 (lane >> 5) + e)
-    f32x4 bb[NT][4];
+    // this lane's bias quads (channel of element e of accumulator quad q of co-tile n: (wc * NT + n) * 32 + SH::chan(lane, q) + e)
+    constexpr int NBQ = 4 / SH::QB;   // distinct bias quads of a co-tile: quad q takes bb[.][q / SH::QB]
+    f32x4 bb[NT][NBQ];
 #pragma unroll
     for (int n = 0; n < NT; ++n)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) bb[n][q] = *(const f32x4*)(p.b1 + (wc * NT + n) * 32 + 8 * q + 4 * (lane >> 5));
+        for (int q = 0; q < NBQ; ++q) bb[n][q] = *(const f32x4*)(p.b1 + (wc * NT + n) * 32 + SH::chan(lane, q * SH::QB));
     __syncthreads();
 
     // ---- c1: xt rows r = 0..127  <->  global t0 - h2 + r ; reads staged rows r + tap * d
-    f32x16 acc[MTT][NT];
-    f32x16 cinit[NT];   // bias pattern of this lane's 16 channel slots: the C operand of every tile's first MFMA
+    acc_t acc[MTT][NT];
+    acc_t cinit[NT];   // bias pattern of this lane's 16 channel slots: the C operand of every tile's first MFMA
 #pragma unroll
     for (int n = 0; n < NT; ++n)
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) cinit[n][4 * q + e] = bb[n][q][e];
+        for (int q = 0; q < 4; ++q) SH::set_quad(cinit[n], q, bb[n][q / SH::QB]);
     auto load_b2 = [&]() {
 #pragma unroll
         for (int n = 0; n < NT; ++n)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) bb[n][q] = *(const f32x4*)(p.b2 + (wc * NT + n) * 32 + 8 * q + 4 * (lane >> 5));
+            for (int q = 0; q < NBQ; ++q) bb[n][q] = *(const f32x4*)(p.b2 + (wc * NT + n) * 32 + SH::chan(lane, q * SH::QB));
     };
     if (NT == 1) load_b2();   // lands while c1 runs; at C = 256 its 32 registers do not fit beside c1's (spills): fetched after c1 there
-    const int xlane = (wt * TW + (lane & 31)) * PITCH + (lane >> 5) * 16;
-    rb_contract<EL, MT, NT, NKG, PITCH, true, MH>(acc, ring, smem, xlane, p.w1 + wlane, S, p.dil * PITCH, 0, &cinit);
+    const int xlane = wt * TW * PITCH + SH::xoff(lane, PITCH);
+    rb_contract<EL, MT, NT, NKG, PITCH, true, MH, SH>(acc, ring, smem, xlane, p.w1 + wlane, S, p.dil * PITCH, &cinit);
     if (NT != 1) load_b2();
-    rb_preload<NT>(ring, p.w2 + wlane, NCT * 64);
+    rb_preload(ring, p.w2 + wlane, KGS);
     __syncthreads();   // every wave is done reading the x tile
     // ---- bf16(leaky_relu(xt)) overwrites it (rows 0..127), zero outside the utterance
 #pragma unroll
     for (int m = 0; m < MTT; ++m) {
-        const int r = wt * TW + m * 32 + (lane & 31);
-        const int t = t0 - h2 + r;
-        const bool inb = t >= 0 && t < len;
 #pragma unroll
         for (int n = 0; n < NT; ++n)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const f32x4 v4 = {acc[m][n][4 * q], acc[m][n][4 * q + 1], acc[m][n][4 * q + 2], acc[m][n][4 * q + 3]};
+                const int r = wt * TW + m * 32 + SH::row(lane, q);
+                const int t = t0 - h2 + r;
+                const bool inb = t >= 0 && t < len;
+                const f32x4 v4 = SH::quad(acc[m][n], q);
                 uint2 pk = act4<EL>(v4, 0.1f);
                 if constexpr (GUARD) n_ovf += (inb && r >= h2 && r < h2 + TTe) ? ovf4(v4, 0.1f) : 0;
                 if (!inb) pk = make_uint2(0, 0);
-                *(uint2*)(smem + r * PITCH + ((wc * NT + n) * 32 + 8 * q + 4 * (lane >> 5)) * 2) = pk;
+                *(uint2*)(smem + r * PITCH + ((wc * NT + n) * 32 + SH::chan(lane, q)) * 2) = pk;
             }
     }
     __syncthreads();
@@ -215,10 +219,8 @@ __global__ __launch_bounds__(256, (C == 128 && TT == 128 && WT == 1) ? 3 : 2) vo
 #pragma unroll
     for (int n = 0; n < NT; ++n)
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) cinit[n][4 * q + e] = bb[n][q][e];
-    rb_contract<EL, MT, NT, NKG, PITCH, true, MH>(acc, ring, smem, xlane, p.w2 + wlane, S, PITCH, 0, &cinit);
+        for (int q = 0; q < 4; ++q) SH::set_quad(cinit[n], q, bb[n][q / SH::QB]);
+    rb_contract<EL, MT, NT, NKG, PITCH, true, MH, SH>(acc, ring, smem, xlane, p.w2 + wlane, S, PITCH, &cinit);
     __syncthreads();   // the xt tile is dead: the staging buffer of the epilogue aliases it
 
     if constexpr (GUARD) {
@@ -258,9 +260,10 @@ __global__ __launch_bounds__(256, (C == 128 && TT == 128 && WT == 1) ? 3 : 2) vo
         }
     };
     auto fetch_s = [&](int m, u32x4 (&so)[PER]) {
-        if (mode < 2) return;
+        // (mode 1 never reads them; defined here all the same: left undefined, the register allocator keeps a value for them alive from the top of
+        // the tile through both contractions — 16 / 32 registers, spilled in the largest instantiations)
 #pragma unroll
-        for (int u = 0; u < PER; ++u) so[u] = __builtin_amdgcn_raw_buffer_load_b128(rs_y, eoff(m, u), 0, VP_LD_AUX);
+        for (int u = 0; u < PER; ++u) so[u] = mode < 2 ? u32x4{0, 0, 0, 0} : __builtin_amdgcn_raw_buffer_load_b128(rs_y, eoff(m, u), 0, VP_LD_AUX);
     };
 #pragma unroll
     for (int m = 0; m < XD - 1; ++m) fetch_x(m, xin[m]);
@@ -272,12 +275,8 @@ __global__ __launch_bounds__(256, (C == 128 && TT == 128 && WT == 1) ? 3 : 2) vo
 #pragma unroll
         for (int n = 0; n < NT; ++n)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = acc[m][n][4 * q + e];
-                *(f32x4*)(smem + (wt * 32 + (lane & 31)) * EP + ((wc * NT + n) * 32 + 8 * q + 4 * (lane >> 5)) * 4) = v;
-            }
+            for (int q = 0; q < 4; ++q)
+                *(f32x4*)(smem + (wt * 32 + SH::row(lane, q)) * EP + ((wc * NT + n) * 32 + SH::chan(lane, q)) * 4) = SH::quad(acc[m][n], q);
         if (m + XD - 1 < MTT) fetch_x(m + XD - 1, xin[(m + XD - 1) % XD]);
         if (m + SD - 1 < MTT) fetch_s(m + SD - 1, sold[(m + SD - 1) % SD]);
         __syncthreads();
