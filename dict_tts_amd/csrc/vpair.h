@@ -31,7 +31,8 @@ struct VPairParams {
 // MFMA shape of vpair's contractions at width C (rb_common.h: MfmaShape): 16 = v_mfma_f32_16x16x32, 32 = v_mfma_f32_32x32x16.  ONE
 // shape per width, whatever the tile size: every launch configuration of a layer sums it in the same order (an utterance alone is
 // bit-identical to the same utterance inside a batch).  The packs of w1 / w2 are in this fragment order (pack.hip: pack_conv, `frag`).
-constexpr int vpair_mfma_shape(int C) { return C == 128 ? 16 : 32; }
+// Both widths run the 16x16x32 form (same MFMA cycles and operands as 32x32x16, fewer joules: LABNOTES "vpair<256> on v_mfma_f32_16x16x32").
+constexpr int vpair_mfma_shape(int C) { return (C == 128 || C == 256) ? 16 : 32; }
 
 bool vpair_supported(int C, int K, int dil);
 hipError_t vpair_launch(const VPairParams& p, int C, hipStream_t stream);

@@ -19,7 +19,7 @@ namespace dtts {
 
 // TT = 128: 3 workgroups per CU; TT = 256: every weight fragment feeds 8 MFMAs instead of 4 (half the weight stream
 // through the texture path, half the halo), 2 workgroups per CU when the LDS tile allows
-// C = 256 (NT = 2 co-tiles per wave): the stage-1 ResBlocks; 128-row tiles only.
+// C = 256 (NT = 2 co-tiles per wave): the stage-1 ResBlocks; 128-, 96- and 64-row tiles (vpair_launch_el; the census never takes the 128-row one: vpair_launch_tt).
 // WT = 2 (C = 128; no launch configuration selects it: 1.3 / 4 % slower, LABNOTES (K)): the four waves as 2 (time) x 2 (output channels), two co-tiles per wave — every activation fragment read from LDS feeds two
 // MFMAs instead of one (half the ds_read_b128 traffic; twice the weight fragments through the texture path, as at C = 256).
 // Both contractions run on the MFMA shape of vpair.h: vpair_mfma_shape (rb_common.h: MfmaShape): all row / channel arithmetic below goes through its helpers
@@ -324,6 +324,13 @@ static hipError_t vpair_launch_tt(const VPairParams& p, hipStream_t stream) {
     }
     if ((p.x16 && !X16) || (p.y16 && (EL != EL_F16 || p.mode != 1))) return hipErrorInvalidValue;
     if ((long long)p.T * CC * 4 >= (1LL << 31)) return hipErrorInvalidValue;   // 32-bit byte offsets inside an utterance's buffer resource
+    if constexpr (EL == EL_F16 && !GUARD) {
+        // the census (GUARD) instantiation of the same configuration.  C = 256: 96-row tiles where the release path takes 128-row ones — the
+        // guarded 128-row kernel does not fit 256 VGPRs on MfmaShape<16> (41 spilled) and is never instantiated.  The shape is fixed per
+        // width and the census counts over the rows each tile OUTPUTS (every in-utterance row once per launch), so neither an output bit
+        // nor the count depends on the tile size; a 96-row tile needs less LDS than the 128-row one, so whatever fits there fits here.
+        if (p.ovf) return vpair_launch_tt<CC, (CC == 256 && TT == 128) ? 96 : TT, EL, true, WT, X16>(p, stream);
+    }
     constexpr int PITCH = CC * 2 + 16;
     const int h1 = p.dil * (p.K - 1) / 2, h2 = (p.K - 1) / 2;
     const int TTe = TT - 2 * h2;
@@ -341,9 +348,6 @@ static hipError_t vpair_launch_tt(const VPairParams& p, hipStream_t stream) {
     constexpr bool PS = !(CC == 128 && TT == 128 && WT == 1);
     if (PS) lds += (size_t)(3 * p.B + 2) * sizeof(int);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if constexpr (EL == EL_F16 && !GUARD) {
-        if (p.ovf) return vpair_launch_tt<CC, TT, EL, true, WT, X16>(p, stream);
-    }
     auto kern = vpair_kernel<CC, TT, EL, GUARD, WT, X16>;
     // per device (hipFuncSetAttribute is per device; a process may hold contexts on several GPUs)
     static bool configured_dev[64] = {};
