@@ -129,6 +129,7 @@ int dtts_create(const dtts_config* cfg, dtts_handle* out) {
     (void)hipGetDevice(&h->device);
     if (hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || h->n_cu <= 0) h->n_cu = 256;
     h->debug_rz = cfg->debug_redzone != 0;
+    h->debug_misorder = cfg->debug_redzone == 2;
     h->a_fft.debug = h->a_enc.debug = h->a_dec.debug = h->a_voc.debug = h->a_spk.debug = h->a_post.debug = h->debug_rz;
     *out = h;
     return DTTS_OK;

@@ -171,6 +171,7 @@ struct dtts_ctx {
     unsigned long long noise_seed = 0;              // per context (dtts_create: time, pid, device, instance; dtts_set_noise_seed overrides)
     unsigned long long* ovf_dev = nullptr;          // fp16 range guard counter (DTTS_VOC_F16), device
     bool guard_on = false;
+    bool debug_misorder = false;                             // dtts_config.debug_redzone = 2: the whole-ResBlock launches declare the other fragment order (self-test)
     // always-on overflow detector of the 16-bit vocoder modes: non-finite pre-tanh values counted by the conv_post epilogue (device), and the
     // pinned host word every dtts_hifigan_forward copies it to behind its last kernel (dtts_vocoder_nonfinite reads it without a sync)
     unsigned* bad_dev = nullptr;

@@ -73,7 +73,7 @@ uint16_t f2h_host(float f) {
 // Pack one convolution into MFMA fragment order and upload it.  getw(co, ci, tap) addresses the LOGICAL
 // weight; bias is in logical channel order.  gate_H > 0: logical C_out = 2*gate_H, packed co-tiles
 // alternate (tanh[32j..32j+32), sigmoid[H+32j..H+32j+32)).
-// frag: the fragment order.  32 (every kernel but vpair.hip): the A operand of v_mfma_f32_32x32x16 — per (tap, kg-channel group, co-tile)
+// frag: the fragment order.  32 (every kernel but vpair.hip and rblock.hip at C = 64): the A operand of v_mfma_f32_32x32x16 — per (tap, kg-channel group, co-tile)
 // 64 lanes x kg / 2 elements, lane = 32 * half + co % 32, ci = kg * g + (kg / 2) * half + e.  16 (16-bit engines only; rb_common.h:
 // MfmaShape<16>): the A operand of v_mfma_f32_16x16x32 — per (tap, 32-channel group, co-tile, co half) 64 lanes x 8 elements,
 // lane = 16 * kq + co % 16, ci = 32 * g + 8 * kq + e.  Both orders have the same size, slack included.

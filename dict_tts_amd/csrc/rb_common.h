@@ -116,7 +116,7 @@ __device__ __forceinline__ f32x16 mfma16(const uint4& a, const uint4& b, const f
 }
 
 // ---- MFMA shape of a contraction.  A block of 32 output channels x 32 time rows x 32 input channels is either two
-// v_mfma_f32_32x32x16 (MfmaShape<32>: the default, every kernel but vpair.hip) or four v_mfma_f32_16x16x32 (MfmaShape<16>: 2 channel halves x
+// v_mfma_f32_32x32x16 (MfmaShape<32>: rb2x.hip, rblock.hip at C = 32 / 128 / 256) or four v_mfma_f32_16x16x32 (MfmaShape<16>: vpair.hip, rblock.hip at C = 64; 2 channel halves x
 // 2 row halves) — the same MFMA cycles, the same number of 16-byte operand fragments per lane, 16 fp32 accumulators per lane either way.
 // An accumulator QUAD qi (0..3) is four consecutive output channels of one time row in both shapes, so act4, the 8-byte LDS rewrite and
 // the 16-byte fp32 accesses keep their form; which (row, channel) a quad is comes from row() / chan().  The weights are the A operand
@@ -146,6 +146,12 @@ struct MfmaShape<32> {
 #pragma unroll
         for (int e = 0; e < 4; ++e) a[4 * qi + e] = v[e];
     }
+    // quad qi += v, element by element (as a vector sum hipcc forms packed adds on aligned register pairs and copies accumulators to get them:
+    // 15 registers more in rblock's kernels, spills in its 640-row one)
+    static __device__ __forceinline__ void add_quad(acc_t& a, int qi, const f32x4& v) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) a[4 * qi + e] += v[e];
+    }
     template <int EL>
     static __device__ __forceinline__ void mma(acc_t& d, const uint4* w, const uint4* const (&x)[XF], const acc_t& c) {
         d = mfma16<EL>(w[0], *x[0], c);
@@ -170,6 +176,10 @@ struct MfmaShape<16> {
     static __device__ __forceinline__ int xoff(int lane, int pitch) { return (lane & 15) * pitch + (lane >> 4) * 16; }
     static __device__ __forceinline__ f32x4 quad(const acc_t& a, int qi) { return a.q[qi]; }
     static __device__ __forceinline__ void set_quad(acc_t& a, int qi, const f32x4& v) { a.q[qi] = v; }
+    static __device__ __forceinline__ void add_quad(acc_t& a, int qi, const f32x4& v) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) a.q[qi][e] += v[e];
+    }
     template <int EL>
     static __device__ __forceinline__ void mma(acc_t& d, const uint4* w, const uint4* const (&x)[XF], const acc_t& c) {
 #pragma unroll
@@ -184,7 +194,14 @@ struct MfmaShape<16> {
     }
 };
 
-constexpr int RB_GUARD = 40;  // zero rows on both sides of the LDS tile (>= max pad 25 + one padded tap + one prefetched tap, dilation 5)
+// Zero rows on both sides of rblock's LDS tile.  Below the tile a contraction reaches (K - 1) / 2 * dil rows (25 at k = 11, dilation 5).  Above
+// it the LAST real tap reaches the same 25 rows, a zero tap of a pack padded to whole groups would reach dil rows more (30; no configuration
+// multiplies one today: 4 or more steps per tap, rb_contract's half group at two steps per tap, the real steps at C = 32), and the activation
+// fragment prefetched behind the last step is the first k-step of the tap behind that one: dil rows more (35), bytes 0 .. SH::KB - 1 <= 63 of
+// rows that exist.  The prefetch reaches no further
+// with MfmaShape<16> than with <32>: its two fragments are the two 16-row halves of the SAME 32-row tile (rb_group: row offsets 32 m + 16 f),
+// and 64 bytes instead of 32 stay inside a row (PITCH >= 80).  40 >= 35 covers both shapes.
+constexpr int RB_GUARD = 40;
 
 // acc += W * act, all taps; act is the LDS tile (bf16, pitch PITCH), weights in fragment order [step][co-tile][lane] ([step][co-tile][half][lane], MfmaShape<16>)
 // first RD - 1 weight fragment sets of a convolution (issued early: before the barriers / activation writes that precede it)
@@ -206,17 +223,18 @@ __device__ __forceinline__ void rb_preload(uint4 (&ring)[RD][NTW], const uint4* 
 // burst at the top of a step (a double buffer), row tile m's next fragment is read right behind the MFMAs that consumed the current one and lands while the other
 // row tiles' MFMAs run: eight waves' bursts no longer queue on the CU's LDS pipe in front of the matrix pipe (-1.5 ... -5.9 % per kernel), MT * 4 registers less.
 // The scheduling barriers around the read keep it where it is written (+0.4 % without them).  (The line "(NT == 1 here)" below: the read follows the LAST co-tile's MFMA.)
-// NKG: k-steps per tap (C / SH::CI).
-template <int EL, int MT, int NT, int NKG, int PITCH, bool CINIT, int MH = 1, class SH = MfmaShape<32>>
+// NKG: k-steps per tap (C / SH::CI).  NU: steps of this group: 4, or 2 for the half group that ends a contraction of 4 n + 2 steps (rb_contract: TAIL).
+template <int EL, int MT, int NT, int NKG, int PITCH, bool CINIT, int MH = 1, class SH = MfmaShape<32>, int NU = 4>
 __device__ __forceinline__ void rb_group(typename SH::acc_t (&acc)[MH * MT][NT], const typename SH::acc_t (&cinit)[NT], uint4 (&ring)[SH::RD][NT * SH::WF],
                                          uint4 (&xa)[MT], const char* act, const uint4* wpf, int xb, int dilP, int g) {
     constexpr int GPT = (NKG >= 4) ? NKG / 4 : 1;     // groups per tap
     constexpr int KGS = NKG * SH::CI * 2 * SH::WF;    // uint4 elements between consecutive steps (= NCT * 64 per fragment of a co-tile, NCT = C / 32)
     constexpr int HSTRIDE = MT * 32 * PITCH;          // LDS bytes between two passes
     constexpr int RD = SH::RD, WF = SH::WF, KB = SH::KB;
-    static_assert(4 % RD == 0, "a group of 4 steps is whole turns of the ring");
+    static_assert(NU % RD == 0, "a group is whole turns of the ring");
+    static_assert(NU == 4 || (NKG < 4 && NU % NKG == 0), "a short group is whole taps");
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
+    for (int u = 0; u < NU; ++u) {
 #pragma unroll
         for (int h = 0; h < MH; ++h) {
             if (h == 0) {
@@ -286,6 +304,11 @@ __device__ __forceinline__ void rb_contract(typename SH::acc_t (&acc)[MH * MT][N
     constexpr int TU = (NKG >= 4) ? 1 : 4 / NKG;      // taps per group of 4 steps
     constexpr int GPT = (NKG >= 4) ? NKG / 4 : 1;     // groups per tap
     constexpr int KGS = NKG * SH::CI * 2 * SH::WF;
+    // TAIL: two k-steps per tap (C = 64 on MfmaShape<16>) and an ODD number of taps, so S = 4 n + 2: whole groups, then one half group of 2
+    // steps = the last tap.  Nothing is padded: no zero tap is multiplied to round S up to whole groups (it would be 1 / K of the MFMAs more).
+    // The caller guarantees S % 4 == 2 (rblock_supported: odd kernel sizes only; the launcher refuses anything else).
+    constexpr bool TAIL = (NKG == 2 && SH::FRAG == 16);
+    const int SG = TAIL ? S - 2 : S;                  // steps in whole groups
     uint4 xa[MT];   // the first MT fragment positions of step 0 (rb_group)
 #pragma unroll
     for (int p = 0; p < MT; ++p) xa[p] = *(const uint4*)(act + xrow0 + (p / SH::XF * 32 + p % SH::XF * SH::XROWS) * PITCH);
@@ -316,7 +339,7 @@ __device__ __forceinline__ void rb_contract(typename SH::acc_t (&acc)[MH * MT][N
                 for (int n = 0; n < NT; ++n) acc[m][n] = (*cinit)[n];
         }
     }
-    for (; s0 < S; s0 += 4) {
+    for (; s0 < SG; s0 += 4) {
         const acc_t(&dummy)[NT] = *(const acc_t(*)[NT])acc[0];
         rb_group<EL, MT, NT, NKG, PITCH, false, MH, SH>(acc, dummy, ring, xa, act, wpf, xb, dilP, g);
         wpf += 4 * KGS;
@@ -328,6 +351,10 @@ __device__ __forceinline__ void rb_contract(typename SH::acc_t (&acc)[MH * MT][N
         } else {
             xb += TU * dilP;
         }
+    }
+    if constexpr (TAIL) {
+        const acc_t(&dummy)[NT] = *(const acc_t(*)[NT])acc[0];
+        rb_group<EL, MT, NT, NKG, PITCH, false, MH, SH, 2>(acc, dummy, ring, xa, act, wpf, xb, dilP, 0);
     }
 }
 

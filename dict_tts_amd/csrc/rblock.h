@@ -59,9 +59,20 @@ __host__ __device__ inline int rblock_halo(const RBlockParams& p) {
     return h;
 }
 
+// MFMA shape of rblock's contractions at width C (rb_common.h: MfmaShape): 16 = v_mfma_f32_16x16x32, 32 = v_mfma_f32_32x32x16.  ONE shape per
+// width, whatever the tile size and whether one ResBlock or the whole stage runs in a launch: every launch configuration of a layer sums it in
+// the same order (an utterance alone is bit-identical to the same utterance inside a batch).  The packs are in this fragment order.
+// C = 64 runs the 16x16x32 form: the same MFMA cycles, operands and bits as 32x32x16, fewer joules in kernels that sit at the board's power limit
+// (LABNOTES "rblock on the MFMA shape trait").  C = 128 / 256 (the k = 3 launches) are one line here, packs included: built, bit-identical and
+// faster on the vocoder benchmark, but not yet kept — their own launches' trace was not collected (same LABNOTES section).  C = 32 is not a
+// choice: its contraction (rb2_contract) is written for 32x32x16, and it is LDS-bound.
+constexpr int rblock_mfma_shape(int C) { return C == 64 ? 16 : 32; }
+
 bool rblock_supported(int C, int K);
 int rblock_padded_taps(int C, int K);
-hipError_t rblock_launch(const RBlockParams& p, int C, hipStream_t stream);
+// frag: the fragment order EVERY pack of the launch is in (pack.hip: pack_conv; 0 = mixed).  hipErrorInvalidValue, and nothing runs, unless it is
+// rblock_mfma_shape(C): a kernel walks a pack in its own order or not at all.
+hipError_t rblock_launch(const RBlockParams& p, int C, int frag, hipStream_t stream);
 // the launches with ALL ResBlocks of a stage (nrb > 1; tune bits 9 / 12), for a launch halo of `halo` rows (rblock_halo):
 // rows a fused launch with the fused conv_post needs in S (one private strip per tile), or 0 when the configuration does not fuse
 long long rblock_private_rows(int C, int halo, int B, int T);

@@ -1,4 +1,5 @@
 // Fused HifiGAN ResBlock1 (modules/hifigan/hifigan.py:27-58), 16-bit MFMA: every k at C = 64 / 32, k = 3 at C = 128 / 256.
+// The MFMA instruction is a per-width choice (rblock.h: rblock_mfma_shape; rb_common.h: MfmaShape): the kernel is written against the trait.
 //
 // Unfused, a ResBlock is six convolutions that each stream the whole activation through HBM; at C <= 64 their
 // arithmetic intensity (C*k/2 FLOP/B) is far below the MFMA/HBM ridge, i.e. the vocoder's last two stages (36 % of
@@ -6,7 +7,7 @@
 //   * the fp32 residual stream x lives in REGISTERS in MFMA accumulator layout (D[co][t]),
 //   * the bf16 leaky_relu copy that feeds the next convolution lives in ONE LDS buffer (A and the intermediate
 //     xt time-share it: conv reads -> barrier -> overwrite -> barrier),
-//   * weights stream from L2 through a 4-deep register ring (22..90 KB per conv, shared by every workgroup),
+//   * weights stream from L2 through a register ring of SH::RD k-steps (22..90 KB per conv, shared by every workgroup),
 //   * the tile carries a halo of 6*(k-1) rows per side (sum of the six receptive half-widths at dilations (1, 3, 5); more
 //     for larger dilations: rblock_halo) that is recomputed;
 //     rows outside the utterance are forced to zero after every activation = the reference's zero padding.
@@ -40,14 +41,18 @@ extern "C" __attribute__((visibility("default"))) int dtts_debug_rb_stamps(unsig
 
 // TB (two LDS activation buffers; no launch configuration selects it: slower, LABNOTES (O)): leaky_relu(x) and leaky_relu(xt) live in SEPARATE buffers, so the rewrite after a
 // contraction needs no write-after-read barrier (nobody reads the buffer it writes): two workgroup barriers per iteration instead of four.
-template <int C, int MT, int NT, int WT, int WC, int EL, int PS, bool GUARD, bool TB = false>
+// SH: the MFMA shape of every contraction of the kernel (rb_common.h MfmaShape; rblock.h rblock_mfma_shape picks it per width): all row / channel
+// arithmetic of the accumulator layout goes through its helpers, and the packs arrive in its fragment order.
+template <int C, int MT, int NT, int WT, int WC, int EL, int PS, bool GUARD, bool TB = false, class SH = MfmaShape<32>>
 __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void rblock_kernel(const RBlockParams p) {
     static_assert(WC * NT * 32 == C, "channel tiling must cover C");
+    static_assert(!TB || SH::FRAG == 32, "the two-buffer form was only ever built on 32x32x16");
+    typedef typename SH::acc_t acc_t;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int THREADS = 64 * WT * WC;
     constexpr int W = 32 * MT * WT;
     constexpr int PITCH = C * 2 + 16;
-    constexpr int NKG = C / 16;
+    constexpr int NKG = C / SH::CI;
     // (the contractions keep ONE activation-fragment set, rb_common.h: with a double buffer the 640-row C = 64 instantiation sat at 256 VGPRs with 13 of
     // them spilled; the single set takes 249 and spills nothing.  LABNOTES round 5 (Y))
     constexpr int EP = C * 4 + 16;                 // fp32 staging row
@@ -114,19 +119,19 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
         while (pre[bb + 1] <= jj) ++bb;
         bb = __builtin_amdgcn_readfirstlane(bb);
     };
-    // the residual stream of a tile, fp32, straight into accumulator layout (lane & 31 = row, 4 consecutive channels per 16 B access).
+    // the residual stream of a tile, fp32, straight into accumulator layout (quad q of a lane = 4 consecutive channels of row SH::row(lane, q): one
+    // 16 B access.  An access of the wave covers 32 rows x 32 contiguous bytes on MfmaShape<32>, 16 rows x 64 on MfmaShape<16>).
     // Buffer loads over the utterance [0, len) x C return zeros for rows outside it (t < 0 wraps to a huge unsigned offset) = the zero padding.
-    auto load_x = [&](f32x16 (&d)[NT], int m, int bb, int base, int ln) {   // 32-row slab m of this wave
+    // (row / chan are a lane part plus a quad part in both shapes: the quad part is an immediate offset of the access)
+    auto load_x = [&](acc_t (&d)[NT], int m, int bb, int base, int ln) {   // 32-row slab m of this wave
         const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + (long long)bb * p.T * C), 0, ln * C * 4, 0x00020000);
-        const int o0 = ((base + wt * MT * 32 + (lane & 31)) * C + wc * NT * 32 + 4 * (lane >> 5)) * 4;
+        const int o0 = ((base + wt * MT * 32 + SH::row(lane, 0)) * C + wc * NT * 32 + SH::chan(lane, 0)) * 4;
 #pragma unroll
         for (int n = 0; n < NT; ++n)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, o0 + (m * 32 * C + n * 32 + 8 * q) * 4, 0, RB_X_AUX);
-                const f32x4 f = __builtin_bit_cast(f32x4, v);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) d[n][4 * q + e] = f[e];
+                const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, o0 + (m * 32 * C + n * 32 + SH::row(0, q) * C + SH::chan(0, q)) * 4, 0, RB_X_AUX);
+                SH::set_quad(d[n], q, __builtin_bit_cast(f32x4, v));
             }
     };
     // (readfirstlane: a length in a VGPR would put every buffer resource below in VGPRs: a waterfall loop around each buffer access)
@@ -144,7 +149,7 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
         t0 = blockIdx.x * TTo - (p.wav ? PH : 0);
         if (t0 + (p.wav ? PH : 0) >= len) return;
     }
-    f32x16 xr[MT][NT];
+    acc_t xr[MT][NT];
     if constexpr (PS) {
 #pragma unroll
         for (int m = 0; m < MT; ++m) load_x(xr[m], m, b, t0 - H, len);
@@ -168,15 +173,12 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
 #pragma unroll
             for (int n = 0; n < NT; ++n)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const f32x4 v = *(const f32x4*)(stage + (wt * 32 + (lane & 31)) * EP + ((wc * NT + n) * 32 + 8 * q + 4 * (lane >> 5)) * 4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) xr[m][n][4 * q + e] = v[e];
-                }
+                for (int q = 0; q < 4; ++q)
+                    SH::set_quad(xr[m][n], q, *(const f32x4*)(stage + (wt * 32 + SH::row(lane, q)) * EP + ((wc * NT + n) * 32 + SH::chan(lane, q)) * 4));
         }
     }
 
-    const int kg_stride = (C / 32) * 64;
+    const int kg_stride = (C / 32) * SH::WF * 64;   // uint4 elements of a k-step's weights
     // work items of a workgroup: (tile, ResBlock r) — r runs over the launch's p.nrb ResBlocks on the SAME tile before the next tile
     int r = 0;
 
@@ -195,15 +197,17 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
         wt = wave % WT, wc = wave / WT;
         c4 = tid % F4, r0 = tid / F4;
     }
-    const int xlane = (RB_GUARD + wt * MT * 32 + (lane & 31)) * PITCH + (lane >> 5) * 16;
-    const size_t wlane = (size_t)(wc * NT) * 64 + lane;
+    const int xlane = (RB_GUARD + wt * MT * 32 + SH::row(lane, 0)) * PITCH + SH::chan(lane, 0) * 4;
+    const size_t wlane = (size_t)(wc * NT) * SH::WF * 64 + lane;
     if constexpr (PS) r = __builtin_amdgcn_readfirstlane(r);
     else r = 0;                                      // (one tile per workgroup: one ResBlock per launch)
     const RBlockParams::Set& R = p.rb[PS ? r : 0];
     const int Kr = R.K;                              // this ResBlock's kernel size (the tile's halo follows the launch's largest)
     // C = 32 (two k-groups per tap): the packs' zero padding to a multiple of four steps would be 25 / 12.5 / 8 % of the MFMAs at k = 3 / 7 / 11:
     // those configurations run the real steps only (rb2_contract, uniform exit at tap boundaries)
-    constexpr bool REAL_STEPS = (NKG < 4);
+    constexpr bool REAL_STEPS = (C == 32);
+    static_assert(!REAL_STEPS || SH::FRAG == 32, "rb2_contract is written for 32x32x16");
+    static_assert(REAL_STEPS || NKG >= 4 || (NKG == 2 && SH::FRAG == 16), "whole groups of four k-steps, or rb_contract's half group");
     const int S = (REAL_STEPS ? Kr : R.Kp) * NKG;   // k-steps (packed taps are zero padded so that Kp * NKG % 4 == 0)
     const bool last_rb = !PS || r + 1 == p.nrb;
     // what the epilogue does with the stage sum: one ResBlock per launch: p.mode; all of the stage's: write, accumulate.., finish
@@ -247,69 +251,80 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
                                   : __builtin_amdgcn_make_buffer_rsrc((void*)(p.S + brow * C), 0, len * C * 4, 0x00020000);
 
     // bf16(leaky_relu(v + bias, 0.1)) of this wave's tiles -> LDS activation buffer, zero outside the utterance.
-    // bias: this lane's 4 channel quads per co-tile, loaded into registers BEFORE the contraction it follows.
-    auto load_bias = [&](f32x4 (&bb)[NT][4], const float* bias) {
+    // bias: this lane's distinct channel quads per co-tile (accumulator quad q takes bb[.][q / SH::QB]: on MfmaShape<16> the two row halves
+    // share their channels), loaded into registers BEFORE the contraction it follows.
+    constexpr int NBQ = 4 / SH::QB;
+    auto load_bias = [&](f32x4 (&bb)[NT][NBQ], const float* bias) {
 #pragma unroll
         for (int n = 0; n < NT; ++n)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) bb[n][q] = *(const f32x4*)(bias + (wc * NT + n) * 32 + 8 * q + 4 * (lane >> 5));
+            for (int q = 0; q < NBQ; ++q) bb[n][q] = *(const f32x4*)(bias + (wc * NT + n) * 32 + SH::chan(lane, q * SH::QB));
     };
     const bool all_inb = base_t >= 0 && base_t + W <= len;   // block-uniform: no row of the tile needs masking
     int n_ovf = 0;
     // MASKED = false: a tile wholly inside its utterance (block-uniform, most tiles) — no row needs the zero select: 2 of the ~11 VALU
     // instructions per four values less, in the phase that is VALU-bound (LABNOTES round 4 (C))
-    auto write_act_impl = [&](char* dst, const f32x16 (&v)[MT][NT], auto masked_tag) {
+    auto write_act_impl = [&](char* dst, const acc_t (&v)[MT][NT], auto masked_tag) {
         constexpr bool MASKED = decltype(masked_tag)::value;
+        // (MfmaShape<16>: the lane index passes through an opaque move at every rewrite.  A lane has two rows per slab there, and hipcc otherwise keeps
+        // the 2 MT rows' masks and LDS addresses — the same in all six rewrites of a tile — alive through the contractions: spills at MT = 5)
+        int ln = lane;
+        if constexpr (SH::FRAG == 16) asm volatile("" : "+v"(ln));
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
-            const int row = (wt * MT + m) * 32 + (lane & 31);
-            const int t = base_t + row;
-            const bool inb = !MASKED || (t >= 0 && t < len);
-            // range guard: only the rows this tile OUTPUTS are counted.  Every in-utterance row is an output row of exactly one tile
-            // and carries the exact activation there at each of the six stages, so the count is a census; halo rows (recomputed,
-            // increasingly inexact towards the tile edge, their results discarded) are another tile's output rows.
-            const bool counted = inb && row >= H && row < H + TT;
+            // the row of a quad: one per lane on MfmaShape<32>, one per row half (SH::QB quads) on MfmaShape<16>
+            int row[SH::QB];
+            bool inb[SH::QB], counted[SH::QB];
+#pragma unroll
+            for (int rh = 0; rh < SH::QB; ++rh) {
+                row[rh] = (wt * MT + m) * 32 + SH::row(ln, rh);
+                const int t = base_t + row[rh];
+                inb[rh] = !MASKED || (t >= 0 && t < len);
+                // range guard: only the rows this tile OUTPUTS are counted.  Every in-utterance row is an output row of exactly one tile
+                // and carries the exact activation there at each of the six stages, so the count is a census; halo rows (recomputed,
+                // increasingly inexact towards the tile edge, their results discarded) are another tile's output rows.
+                counted[rh] = inb[rh] && row[rh] >= H && row[rh] < H + TT;
+            }
 #pragma unroll
             for (int n = 0; n < NT; ++n)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const int co = (wc * NT + n) * 32 + 8 * q + 4 * (lane >> 5);
-                    f32x4 v4 = {v[m][n][4 * q], v[m][n][4 * q + 1], v[m][n][4 * q + 2], v[m][n][4 * q + 3]};
+                    constexpr int QBM = SH::QB - 1;   // (quad q's row half: q % SH::QB)
+                    const int co = (wc * NT + n) * 32 + SH::chan(ln, q);
+                    const f32x4 v4 = SH::quad(v[m][n], q);
                     uint2 pk = act4<EL>(v4, 0.1f);
-                    if constexpr (GUARD) n_ovf += counted ? ovf4(v4, 0.1f) : 0;
+                    if constexpr (GUARD) n_ovf += counted[q & QBM] ? ovf4(v4, 0.1f) : 0;
                     if constexpr (MASKED) {
-                        if (!inb) pk = make_uint2(0, 0);
+                        if (!inb[q & QBM]) pk = make_uint2(0, 0);
                     }
-                    *(uint2*)(dst + (RB_GUARD + row) * PITCH + co * 2) = pk;
+                    *(uint2*)(dst + (RB_GUARD + row[q & QBM]) * PITCH + co * 2) = pk;
                 }
         }
     };
-    auto write_act = [&](char* dst, const f32x16 (&v)[MT][NT]) {
+    auto write_act = [&](char* dst, const acc_t (&v)[MT][NT]) {
         if (all_inb) write_act_impl(dst, v, std::false_type{});
         else write_act_impl(dst, v, std::true_type{});
     };
 
-    uint4 ring[4][NT];
-    f32x4 bb[NT][4];   // one live bias set
+    uint4 ring[SH::RD][NT * SH::WF];
+    f32x4 bb[NT][NBQ];   // one live bias set
     RB_T(10);                                            // (tile bookkeeping, and — the first tile — the wait for x)
-    rb_preload<NT>(ring, R.w1[0] + wlane, kg_stride);   // in flight during the first activation write
+    rb_preload(ring, R.w1[0] + wlane, kg_stride);       // in flight during the first activation write
     load_bias(bb, R.b1[0]);
     write_act(act, xr);
     RB_T(0);
     __syncthreads();
     RB_T(1);
 
-    f32x16 acc[MT][NT];
+    acc_t acc[MT][NT];
 #pragma unroll 1
     for (int it = 0; it < 3; ++it) {
         // conv1: the first MFMA of every tile takes the bias pattern as its C operand (no accumulator init pass)
-        f32x16 cinit[NT];
+        acc_t cinit[NT];
 #pragma unroll
         for (int n = 0; n < NT; ++n)
 #pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) cinit[n][4 * q + e] = bb[n][q][e];
+            for (int q = 0; q < 4; ++q) SH::set_quad(cinit[n], q, bb[n][q / SH::QB]);
         load_bias(bb, R.b2[it]);       // lands while conv1 runs
         const int d = R.dil[it];
         if constexpr (REAL_STEPS) {
@@ -318,8 +333,8 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
             if (S) rb2_contract<EL, MT, NT, NKG, PITCH, 4, true>(acc, ring, act, xlane - ((Kr - 1) / 2) * d * PITCH, R.w1[it] + wlane, S, d * PITCH, cinit);
             else rb_contract<EL, MT, NT, NKG, PITCH, true, 1>(acc, ring, act, 0, R.w1[it] + wlane, 0, 0, &cinit);
         } else
-            rb_contract<EL, MT, NT, NKG, PITCH, true, 1>(acc, ring, act, xlane - ((Kr - 1) / 2) * d * PITCH, R.w1[it] + wlane, S, d * PITCH, &cinit);
-        rb_preload<NT>(ring, R.w2[it] + wlane, kg_stride);   // next conv's first weights fly during barrier + write
+            rb_contract<EL, MT, NT, NKG, PITCH, true, 1, SH>(acc, ring, act, xlane - ((Kr - 1) / 2) * d * PITCH, R.w1[it] + wlane, S, d * PITCH, &cinit);
+        rb_preload(ring, R.w2[it] + wlane, kg_stride);   // next conv's first weights fly during barrier + write
         RB_T(2);
         if constexpr (!TB) __syncthreads();   // every wave is done reading A (TB: xt has its own buffer, last read before the previous barrier)
         RB_T(3);
@@ -333,15 +348,13 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
 #pragma unroll
             for (int n = 0; n < NT; ++n)
 #pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) xr[m][n][4 * q + e] += bb[n][q][e];
+                for (int q = 0; q < 4; ++q) SH::add_quad(xr[m][n], q, bb[n][q / SH::QB]);
         if (it < 2) load_bias(bb, R.b1[it + 1]);
         if constexpr (REAL_STEPS) {
             if (S) rb2_contract<EL, MT, NT, NKG, PITCH, 4, false>(xr, ring, act2, xlane - ((Kr - 1) / 2) * PITCH, R.w2[it] + wlane, S, PITCH, cinit);
         } else
-            rb_contract<EL, MT, NT, NKG, PITCH, false, 1>(xr, ring, act2, xlane - ((Kr - 1) / 2) * PITCH, R.w2[it] + wlane, S, PITCH);
-        if (it < 2) rb_preload<NT>(ring, R.w1[it + 1] + wlane, kg_stride);
+            rb_contract<EL, MT, NT, NKG, PITCH, false, 1, SH>(xr, ring, act2, xlane - ((Kr - 1) / 2) * PITCH, R.w2[it] + wlane, S, PITCH);
+        if (it < 2) rb_preload(ring, R.w1[it + 1] + wlane, kg_stride);
         if (PS && p.tile_ctr && last_rb && it == 2 && tid == 0) pre[3 * p.B + 1] = G + (int)claim;   // the claimed tile, for everyone (read behind the barrier)
         RB_T(6);
         if (!TB || it == 2) __syncthreads();   // every wave is done reading xt (TB: A is rewritten, not xt; the barrier stays in front of the epilogue)
@@ -408,12 +421,7 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
 #pragma unroll
         for (int n = 0; n < NT; ++n)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = xr[m][n][4 * q + e];
-                *(f32x4*)(stg + (lane & 31) * EP + (n * 32 + 8 * q + 4 * (lane >> 5)) * 4) = v;
-            }
+            for (int q = 0; q < 4; ++q) *(f32x4*)(stg + SH::row(lane, q) * EP + (n * 32 + SH::chan(lane, q)) * 4) = SH::quad(xr[m][n], q);
         // slab m of the residual registers is free: the NEXT tile's slab m starts its trip into them (no second register set, and
         // the loads are younger than the stage sum fetched above, so nothing below waits for them)
         if (has_next) load_x(xr[m], m, bn, t0n - H, lenn);
@@ -569,7 +577,11 @@ static size_t rb_table_bytes(int B) { return (size_t)(3 * B + 2) * sizeof(int); 
 // hipErrorOutOfMemory: the configuration's LDS (with the tile table of p.B utterances) exceeds 160 KB — the caller picks another one
 template <int C, int MT, int NT, int WT, int WC, int EL, int PS, bool GUARD = false, bool TB = false>
 static hipError_t rb_launch_cfg(const RBlockParams& p, hipStream_t stream) {
+    typedef MfmaShape<rblock_mfma_shape(C)> SH;   // one shape per width, whatever the tile size (rblock.h)
     constexpr int W = 32 * MT * WT;
+    // two k-steps per tap end on rb_contract's half group: odd kernel sizes only, and the taps the pack was padded to
+    for (int j = 0; j < p.nrb; ++j)
+        if (!(p.rb[j].K & 1) || p.rb[j].Kp != rblock_padded_taps(C, p.rb[j].K)) return hipErrorInvalidValue;
     const int H = rblock_halo(p), TT = W - 2 * H;
     if (TT < 32) return hipErrorInvalidValue;
     if ((long long)p.T * C * 4 >= (1LL << 31)) return hipErrorInvalidValue;   // 32-bit byte offsets inside an utterance's buffer resource
@@ -580,10 +592,14 @@ static hipError_t rb_launch_cfg(const RBlockParams& p, hipStream_t stream) {
     q.pre_off = (int)lds;
     if (PS) lds += rb_table_bytes(p.B);
     if (lds > 160 * 1024) return hipErrorOutOfMemory;
-    if constexpr (EL == EL_F16 && !GUARD) {
+    // (the 640-row C = 64 tile has no guarded form: with the census's counters it does not fit the register file on MfmaShape<16> — 6 registers
+    // spilled — and rb_launch_el sends a census launch to the 512-row tile instead)
+    constexpr bool HAS_GUARD = !(C == 64 && MT == 5);
+    if constexpr (EL == EL_F16 && !GUARD && HAS_GUARD) {
         if (p.ovf) return rb_launch_cfg<C, MT, NT, WT, WC, EL, PS, true, TB>(p, stream);
     }
-    auto kern = rblock_kernel<C, MT, NT, WT, WC, EL, PS, GUARD, TB>;
+    if (EL == EL_F16 && !HAS_GUARD && p.ovf) return hipErrorInvalidValue;
+    auto kern = rblock_kernel<C, MT, NT, WT, WC, EL, PS, GUARD, TB, SH>;
     // per device (hipFuncSetAttribute is per device; a process may hold contexts on several GPUs)
     static bool configured_dev[64] = {};
     int cur_dev = 0;
@@ -641,8 +657,14 @@ long long rblock_private_rows(int C, int halo, int B, int T) {
     return (long long)B * ((T + TTo - 1) / TTo) * TT;
 }
 
+// Taps of a pack (zero padded behind the real ones) such that the k-steps the kernel walks are whole groups of four.  Steps per tap: C / 16 on
+// MfmaShape<32>, C / 32 on MfmaShape<16>.  Two steps per tap on MfmaShape<16> (C = 64) pad nothing: K is odd (rblock_supported), K - 1 taps
+// are whole groups and rb_contract ends on a half group of two steps — one ring turn of RD = 2 — instead of multiplying a zero tap.
+// (C = 32: the kernel runs the real steps, rb2_contract; the padding only keeps its prefetches inside the pack.)
 int rblock_padded_taps(int C, int K) {
-    const int nkg = C / 16;
+    const int sh = rblock_mfma_shape(C);
+    const int nkg = C / (sh == 16 ? 32 : 16);
+    if (sh == 16 && nkg == 2) return K;
     int kp = K;
     while ((kp * nkg) % 4) ++kp;
     return kp;
@@ -688,8 +710,10 @@ static hipError_t rb_launch_el(const RBlockParams& p, int C, hipStream_t stream)
     if (C == 256 && few(128)) return rb_launch_cfg<256, 2, 1, 1, 8, EL, 1>(p, stream);   // 64-row tile
     if (C == 32) return rb_launch_cfg<32, 4, 1, 4, 1, EL, 0>(p, stream);      // 512-row tile, 4 waves over time
     // C = 64, k >= 7: 640-row tiles (MT = 5; the halo 12 (k - 1) is 11 / 19 % of the tile instead of 14 / 23 %: -4.8 % at k = 11, nothing at k = 3
-    // where 13 spilled registers cost what the halo gives); tune bit 14: 512-row tiles for every k (round 3)
-    if (C == 64 && p.K >= 7 && !p.small_tile) RB_TRY((rb_launch_cfg<64, 5, 1, 4, 2, EL, 1>(p, stream)));
+    // where 13 spilled registers cost what the halo gives); tune bit 14: 512-row tiles for every k (round 3).  The range-guard census (p.ovf, fp16
+    // operands) takes the 512-row tile as well: its 640-row kernel would spill.  One MFMA shape per width, so the bits — and the count, a census
+    // of output rows — do not depend on the tile size.
+    if (C == 64 && p.K >= 7 && !p.small_tile && !(EL == EL_F16 && p.ovf)) RB_TRY((rb_launch_cfg<64, 5, 1, 4, 2, EL, 1>(p, stream)));
     if (C == 64) RB_TRY((rb_launch_cfg<64, 4, 1, 4, 2, EL, 1>(p, stream)));    // 512-row tile, 8 waves (4 time x 2 channel)
     if (C == 64) return rb_launch_cfg<64, 4, 1, 2, 2, EL, 1>(p, stream);       // (the tile table of a very large batch) 256-row tile
     if (C == 128) RB_TRY((rb_launch_cfg<128, 4, 1, 2, 4, EL, 1>(p, stream)));  // 256-row tile, 8 waves (2 time x 4 channel)
@@ -700,7 +724,9 @@ static hipError_t rb_launch_el(const RBlockParams& p, int C, hipStream_t stream)
     return hipErrorInvalidValue;
 }
 
-hipError_t rblock_launch(const RBlockParams& p, int C, hipStream_t stream) {
+hipError_t rblock_launch(const RBlockParams& p, int C, int frag, hipStream_t stream) {
+    if (C != 32 && C != 64 && C != 128 && C != 256) return hipErrorInvalidValue;
+    if (frag != rblock_mfma_shape(C)) return hipErrorInvalidValue;   // (every configuration of a width runs MfmaShape<rblock_mfma_shape(C)>: rb_launch_cfg)
     return p.el == EL_F16 ? rb_launch_el<EL_F16>(p, C, stream) : rb_launch_el<EL_BF16>(p, C, stream);
 }
 

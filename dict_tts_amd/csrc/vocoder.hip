@@ -132,15 +132,19 @@ bool vocoder_fp16_analysis(dtts_ctx* h, Need& need) {
 }
 
 // One convolution of a whole-ResBlock kernel (rblock.hip, rb2x.hip): the weights of `base` with the tap axis zero padded so that the number of
-// k-steps is a multiple of the register ring depth; K stays the real kernel size.  false: a tensor is missing or the upload failed
-bool pack_rb_fused(dtts_ctx* h, Need& need, PackedConv& L, int eng, const std::string& base, int ch, int k, int dil) {
+// k-steps is whole groups of the contraction loop (rblock_padded_taps); K stays the real kernel size.  frag: the fragment order of the kernel
+// that walks the pack (rblock.hip: rblock_mfma_shape(ch); rb2x.hip: 32).  false: a tensor is missing or the upload failed.
+// Slack: the weight ring runs RD - 1 k-steps ahead — three 16-channel steps (MfmaShape<32>) or one 32-channel step (MfmaShape<16>, RD = 2)
+// behind the last tap, in either order less than the one zero tap appended here (>= 2 steps of 32 channels at ch >= 64) on top of pack_conv's own
+// slack: the prefetch never clamps.
+bool pack_rb_fused(dtts_ctx* h, Need& need, PackedConv& L, int eng, const std::string& base, int ch, int k, int dil, int frag) {
     const HostTensor* w = folded_weight(h, need, base);
     std::vector<float> bias = bias_of(need, base);
     if (!w || bias.empty()) return false;
     const float* pw = w->f.data();
     const int slack = ch >= 64 ? 1 : 2;   // >= 4 zero k-steps behind the last tap: the weight prefetch never clamps
     const bool ok = pack_conv(h, L, eng, ch, ch, rblock_padded_taps(ch, k) + slack,
-                              [=](int co, int ci, int tap) { return tap < k ? pw[((size_t)co * ch + ci) * k + tap] : 0.f; }, bias, dil, 1, 0);
+                              [=](int co, int ci, int tap) { return tap < k ? pw[((size_t)co * ch + ci) * k + tap] : 0.f; }, bias, dil, 1, 0, 0, -1, frag);
     L.K = k;
     return ok;
 }
@@ -245,7 +249,7 @@ int build_vocoder(dtts_ctx* h) {
         h->rbf1[i].resize(2);
         for (int mth = 0; ok && mth < 2; ++mth)
             ok = pack_rb_fused(h, need, h->rbf1[i][mth], eng_rb, v + "resblocks." + std::to_string(i) + ".convs." + std::to_string(mth), ch, k,
-                               c.resblock_dilation_sizes[j][mth]);
+                               c.resblock_dilation_sizes[j][mth], 32);
     }
     for (int i = 0; ok && !rb2x && eng_rb != ENG_BF16X3 && i < c.n_upsamples * nk; ++i) {
         const int j = i % nk, k = c.resblock_kernel_sizes[j];
@@ -260,8 +264,8 @@ int build_vocoder(dtts_ctx* h) {
         h->rbf2[i].resize(3);
         const std::string r = v + "resblocks." + std::to_string(i);
         for (int mth = 0; ok && mth < 3; ++mth) {
-            ok = pack_rb_fused(h, need, h->rbf1[i][mth], eng_rb, r + ".convs1." + std::to_string(mth), ch, k, c.resblock_dilation_sizes[j][mth]);
-            ok = ok && pack_rb_fused(h, need, h->rbf2[i][mth], eng_rb, r + ".convs2." + std::to_string(mth), ch, k, 1);
+            ok = pack_rb_fused(h, need, h->rbf1[i][mth], eng_rb, r + ".convs1." + std::to_string(mth), ch, k, c.resblock_dilation_sizes[j][mth], rblock_mfma_shape(ch));
+            ok = ok && pack_rb_fused(h, need, h->rbf2[i][mth], eng_rb, r + ".convs2." + std::to_string(mth), ch, k, 1, rblock_mfma_shape(ch));
         }
     }
     ok = ok && pack_plain(h, need, h->conv_post, eng, v + "conv_post", 1, 1, 3);
@@ -473,12 +477,17 @@ struct VocRun {
         whole_rb_params(rp, j, j_last);
         rp.nrb = j_last - j + 1;
         rp.last_mode = j_last == nk - 1 ? 2 : 1;
+        int frag = 0;
         for (int jj = j; jj <= j_last; ++jj) {
             RBlockParams::Set& st = rp.rb[jj - j];
             const auto& g1 = h->rbf1[(size_t)i * nk + jj];
             const auto& g2 = h->rbf2[(size_t)i * nk + jj];
             st.K = g1[0].K;
             st.Kp = rblock_padded_taps(ch, g1[0].K);
+            // the order the launch's packs are in; a mixed set is in no kernel's order (0), and rblock_launch refuses whatever is not its kernel's
+            if (jj == j) frag = g1[0].frag;
+            for (int mth = 0; mth < 3; ++mth)
+                if (g1[mth].frag != frag || g2[mth].frag != frag) frag = 0;
             for (int mth = 0; mth < 3; ++mth) {
                 st.w1[mth] = (const uint4*)g1[mth].w_hi;
                 st.w2[mth] = (const uint4*)g2[mth].w_hi;
@@ -491,8 +500,9 @@ struct VocRun {
         // a fused stage with the fused conv_post: one private strip of S per tile (the tiles overlap)
         if (rp.wav && fuse_n == nk) rp.s_private = (int)std::min<size_t>(s_cap_bytes, (size_t)INT_MAX);
         rp.small_tile = DTTS_TUNE(h, 16384) ? 1 : 0;
+        if (h->debug_misorder) frag = frag == 16 ? 32 : 16;   // (self-test of the launcher's refusal: dtts_config.debug_redzone = 2)
         Timed tm(h, TV, s);
-        LAUNCH(rblock_launch(rp, ch, s));
+        LAUNCH(rblock_launch(rp, ch, frag, s));
         return DTTS_OK;
     }
 

@@ -168,5 +168,6 @@ def fill_abi_config(cfg, hp=None, voc=None, n_phone=None, vocoder_precision=None
     # A/B switches of tuning experiments (include/dicttts_hip.h: dtts_config.tune_flags; 0 = the measured defaults).  An explicit
     # key of the hparams / vocoder config, never the process environment.
     cfg.tune_flags = int((hp or {}).get("dtts_tune_flags", 0)) | int((voc or {}).get("dtts_tune_flags", 0))
-    cfg.debug_redzone = 1 if ((hp or {}).get("dtts_debug_redzone") or (voc or {}).get("dtts_debug_redzone")) else 0
+    rz = (hp or {}).get("dtts_debug_redzone") or (voc or {}).get("dtts_debug_redzone")
+    cfg.debug_redzone = (2 if rz is not True and rz == 2 else 1) if rz else 0   # (2: + the launcher's pack-order self-test, include/dicttts_hip.h)
     return cfg

@@ -113,7 +113,10 @@ typedef struct dtts_config {
     int32_t decoder_fp32;             /* 1 = FVAE decoder WaveNet on exact fp32 MFMA (round 1); 0 (default) = bf16 hi/lo split operands */
     int32_t vocoder_range_guard;      /* DTTS_VOC_F16: 1 = start with the fp16 range guard on (dtts_vocoder_range_guard) */
     int32_t debug_redzone;            /* testing aid: 1 = memory-safety mode — every workspace buffer and weight pack sits between 4 KiB red
-                                         zones, workspaces are filled with 0xFF (NaN) before each forward; dtts_debug_check verifies the zones */
+                                         zones, workspaces are filled with 0xFF (NaN) before each forward; dtts_debug_check verifies the zones.
+                                         2 = the same, and (self-test of the whole-ResBlock launcher) every such launch of dtts_hifigan_forward declares
+                                         its weight packs to be in the OTHER MFMA fragment order than they are in: the launcher must refuse them, the
+                                         forward fails with DTTS_E_HIP before that kernel runs */
     int32_t tune_flags;               /* A/B switches of tuning experiments (tools/ab_libs.sh); 0 = the measured defaults.  The library never
                                          reads the process environment: arithmetic and layout follow this struct alone.
                                          The library honours exactly the bits that have a parity / bit-identity test behind them and
