@@ -24,6 +24,7 @@
 #include "rblock.h"
 #include "vpair.h"
 #include "rb2x.h"
+#include "rbn.h"
 #include "flowstack.h"
 
 // dtts_config.tune_flags: the bits the library honours are listed at TUNE_RELEASE_MASK (context.hip)

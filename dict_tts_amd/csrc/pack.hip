@@ -77,10 +77,15 @@ uint16_t f2h_host(float f) {
 // 64 lanes x kg / 2 elements, lane = 32 * half + co % 32, ci = kg * g + (kg / 2) * half + e.  16 (16-bit engines only; rb_common.h:
 // MfmaShape<16>): the A operand of v_mfma_f32_16x16x32 — per (tap, 32-channel group, co-tile, co half) 64 lanes x 8 elements,
 // lane = 16 * kq + co % 16, ci = 32 * g + 8 * kq + e.  Both orders have the same size, slack included.
+// RBN_FRAG (rbn.h; 16-bit engines, C_in = C_out = 16 or 8, K whole k-steps of 32 / C taps): the A operand of v_mfma_f32_16x16x32 with the taps folded
+// into the contraction index — per k-step 64 lanes x 8 elements, lane = 16 * kq + co, k = 8 * kq + e = (tap % (32 / C)) * C + ci; no slack (rbn.hip
+// copies exactly the pack to LDS).
 bool pack_conv(dtts_ctx* h, PackedConv& L, int engine, int C_out, int C_in, int K,
                const std::function<float(int, int, int)>& getw, const std::vector<float>& bias, int dil, int stride,
                int pad, int gate_H, double flops_per_row, int frag) {
-    if (frag != 32 && (frag != 16 || engine == ENG_F32 || engine == ENG_BF16X3)) return false;
+    const bool folded = frag == RBN_FRAG;
+    if (folded && (C_in != C_out || (C_in != 16 && C_in != 8) || K % rbn_taps_per_step(C_in) || gate_H)) return false;
+    if (frag != 32 && ((frag != 16 && !folded) || engine == ENG_F32 || engine == ENG_BF16X3)) return false;
     L.engine = engine;
     L.frag = frag;
     L.C_in = C_in;
@@ -100,7 +105,8 @@ bool pack_conv(dtts_ctx* h, PackedConv& L, int engine, int C_out, int C_in, int 
     // one C_in CHUNK at a time and, at the end of a chunk's last tap, its running pointer wraps to "next tap, same chunk" = up to a whole
     // tap's k-groups (NG) beyond the end for the last chunk (found in round 3: the 192 -> 2048 conditioning convolution read one
     // 64 KB step past the old 8-step slack — a GPU page fault whenever the allocation ended on a mapped-region boundary)
-    const size_t n = (size_t)K * L.C_in_pad * L.C_out_pad + (size_t)(L.C_in_pad / 16 + 8) * 16 * L.C_out_pad;
+    const size_t n = folded ? (size_t)(K / rbn_taps_per_step(C_in)) * 512
+                            : (size_t)K * L.C_in_pad * L.C_out_pad + (size_t)(L.C_in_pad / 16 + 8) * 16 * L.C_out_pad;
     // put(fragment index, logical weight) for every weight, with k-groups of kg input channels
     auto each_weight = [&](int kg, auto&& put) {
         const int E = kg / 2, NG = L.C_in_pad / kg;
@@ -115,6 +121,11 @@ bool pack_conv(dtts_ctx* h, PackedConv& L, int engine, int C_out, int C_in, int 
             const int ct = pco / 32, col = pco % 32;
             for (int tap = 0; tap < K; ++tap)
                 for (int ci = 0; ci < C_in; ++ci) {
+                    if (folded) {
+                        const int tps = rbn_taps_per_step(C_in), k = (tap % tps) * C_in + ci;
+                        put((((size_t)(tap / tps) * 64 + k / 8 * 16 + co) * 8) + k % 8, getw(co, ci, tap));
+                        continue;
+                    }
                     if (frag == 16) {   // (kg = 16, C_in_pad % 32 == 0)
                         const int g = ci / 32, kq = ci % 32 / 8, e = ci % 8;
                         put((((((size_t)tap * (L.C_in_pad / 32) + g) * NCT + ct) * 2 + col / 16) * 64 + kq * 16 + col % 16) * 8 + e, getw(co, ci, tap));

@@ -6,7 +6,7 @@
 namespace dtts {
 
 struct VConvParams {
-    const unsigned short* x;  // bf16 [B][T][ldx], already activated; ldx = C_in_pad (multiple of 8)
+    const unsigned short* x;  // bf16 [B][T][ldx], already activated; ldx = C_in_pad, or C_in (a multiple of 8) where the rows are narrower: channels >= C_in are read as zeros
     int ldx;
     const float* xf;          // waveform-exact mode (x == null): fp32 [B][T][ldx] NOT activated; leaky_relu(in_slope) + hi/lo split while staging
     float in_slope;           //   slope of that leaky_relu (1 = identity)

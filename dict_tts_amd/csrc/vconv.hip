@@ -171,7 +171,8 @@ __global__ __launch_bounds__(256, X3 ? (MT <= 2 ? (NT == 2 ? 3 : (CK == 64 && WC
                     const int r = idx / PIECES, c = idx % PIECES;
                     const int t = in0 + r;
                     v[u] = make_uint4(0, 0, 0, 0);
-                    if (idx < total && t >= 0 && t < len) v[u] = *(const uint4*)(xb + (long long)t * p.ldx + ci0 + c * 8);
+                    // (channels at and behind C_in are zero: rows narrower than C_in_pad — ldx = C_in = 16 / 8 — are not read past their end)
+                    if (idx < total && t >= 0 && t < len && ci0 + c * 8 < p.C_in) v[u] = *(const uint4*)(xb + (long long)t * p.ldx + ci0 + c * 8);
                 }
 #pragma unroll
                 for (int u = 0; u < U; ++u) {

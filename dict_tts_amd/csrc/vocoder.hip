@@ -133,7 +133,8 @@ bool vocoder_fp16_analysis(dtts_ctx* h, Need& need) {
 
 // One convolution of a whole-ResBlock kernel (rblock.hip, rb2x.hip): the weights of `base` with the tap axis zero padded so that the number of
 // k-steps is whole groups of the contraction loop (rblock_padded_taps); K stays the real kernel size.  frag: the fragment order of the kernel
-// that walks the pack (rblock.hip: rblock_mfma_shape(ch); rb2x.hip: 32).  false: a tensor is missing or the upload failed.
+// that walks the pack (rblock.hip: rblock_mfma_shape(ch); rb2x.hip: 32; rbn.hip: RBN_FRAG, whole k-steps of 32 / ch taps and no slack — its kernel
+// copies exactly the pack).  false: a tensor is missing or the upload failed.
 // Slack: the weight ring runs RD - 1 k-steps ahead — three 16-channel steps (MfmaShape<32>) or one 32-channel step (MfmaShape<16>, RD = 2)
 // behind the last tap, in either order less than the one zero tap appended here (>= 2 steps of 32 channels at ch >= 64) on top of pack_conv's own
 // slack: the prefetch never clamps.
@@ -143,7 +144,7 @@ bool pack_rb_fused(dtts_ctx* h, Need& need, PackedConv& L, int eng, const std::s
     if (!w || bias.empty()) return false;
     const float* pw = w->f.data();
     const int slack = ch >= 64 ? 1 : 2;   // >= 4 zero k-steps behind the last tap: the weight prefetch never clamps
-    const bool ok = pack_conv(h, L, eng, ch, ch, rblock_padded_taps(ch, k) + slack,
+    const bool ok = pack_conv(h, L, eng, ch, ch, frag == RBN_FRAG ? rbn_padded_taps(ch, k) : rblock_padded_taps(ch, k) + slack,
                               [=](int co, int ci, int tap) { return tap < k ? pw[((size_t)co * ch + ci) * k + tap] : 0.f; }, bias, dil, 1, 0, 0, -1, frag);
     L.K = k;
     return ok;
@@ -254,32 +255,35 @@ int build_vocoder(dtts_ctx* h) {
     for (int i = 0; ok && !rb2x && eng_rb != ENG_BF16X3 && i < c.n_upsamples * nk; ++i) {
         const int j = i % nk, k = c.resblock_kernel_sizes[j];
         const int ch = c.upsample_initial_channel >> (i / nk + 1);
-        if (!rblock_supported(ch, k)) {
-            const int* dl = c.resblock_dilation_sizes[j];
+        const int* dl = c.resblock_dilation_sizes[j];
+        // the narrow stages (C = 16 / 8: the V2 generators) have their own whole-ResBlock kernel (rbn.hip); nk = 1: no stage sum to fold the block into
+        const bool narrow = nk >= 2 && rbn_supported(ch, k, dl[0], dl[1], dl[2]) && h->rb1[i][0].C_in == ch && h->rb1[i][0].C_out == ch;
+        if (!rblock_supported(ch, k) && !narrow) {
             if (eng_rb == ENG_F16 && !vpair_runs(c, rb2x, eng_rb, ch, k, dl[0], dl[1], dl[2]))
-                return fail(h, DTTS_E_INVAL, "DTTS_VOC_F16 needs ResBlock widths 32/64/128/256 and odd kernels 3..11 (resblock %d: %d channels, k=%d); use DTTS_VOC_BF16X3", i, ch, k);
+                return fail(h, DTTS_E_INVAL, "DTTS_VOC_F16 needs ResBlock widths 8/16/32/64/128/256 and odd kernels 3..11 (resblock %d: %d channels, k=%d); use DTTS_VOC_BF16X3", i, ch, k);
             continue;
         }
         h->rbf1[i].resize(3);
         h->rbf2[i].resize(3);
         const std::string r = v + "resblocks." + std::to_string(i);
+        const int ffrag = narrow ? RBN_FRAG : rblock_mfma_shape(ch);
         for (int mth = 0; ok && mth < 3; ++mth) {
-            ok = pack_rb_fused(h, need, h->rbf1[i][mth], eng_rb, r + ".convs1." + std::to_string(mth), ch, k, c.resblock_dilation_sizes[j][mth], rblock_mfma_shape(ch));
-            ok = ok && pack_rb_fused(h, need, h->rbf2[i][mth], eng_rb, r + ".convs2." + std::to_string(mth), ch, k, 1, rblock_mfma_shape(ch));
+            ok = pack_rb_fused(h, need, h->rbf1[i][mth], eng_rb, r + ".convs1." + std::to_string(mth), ch, k, c.resblock_dilation_sizes[j][mth], ffrag);
+            ok = ok && pack_rb_fused(h, need, h->rbf2[i][mth], eng_rb, r + ".convs2." + std::to_string(mth), ch, k, 1, ffrag);
         }
     }
     ok = ok && pack_plain(h, need, h->conv_post, eng, v + "conv_post", 1, 1, 3);
-    {   // conv_post (C -> 1, k = 7) + tanh fused into the last stage's last ResBlock kernel when that stage runs on rblock at C = 32
+    {   // conv_post (C -> 1, k = 7) + tanh fused into the last stage's last ResBlock kernel when that stage runs on rblock at C = 32 or on rbn (C = 16 / 8)
         const int last_ch = c.upsample_initial_channel >> c.n_upsamples;
         const HostTensor* w = ok ? folded_weight(h, need, v + "conv_post") : nullptr;
         const std::vector<float> b = ok ? bias_of(need, v + "conv_post") : std::vector<float>();
-        bool fusable = ok && eng_rb != ENG_BF16X3 && last_ch == 32 && w && w->shape.size() == 3 && w->shape[0] == 1 && w->shape[1] == 32 &&
-                       w->shape[2] == 7 && b.size() == 1 && nk >= 2;
+        bool fusable = ok && eng_rb != ENG_BF16X3 && (last_ch == 32 || (!rb2x && (last_ch == 16 || last_ch == 8))) && w && w->shape.size() == 3 && w->shape[0] == 1 &&
+                       w->shape[1] == last_ch && w->shape[2] == 7 && b.size() == 1 && nk >= 2;
         for (int j = 0; fusable && j < nk; ++j) fusable = !h->rbf1[(size_t)(c.n_upsamples - 1) * nk + j].empty();
         if (fusable) {
-            std::vector<float> wt((size_t)7 * 32);
-            for (int ci = 0; ci < 32; ++ci)
-                for (int k = 0; k < 7; ++k) wt[(size_t)k * 32 + ci] = w->f[(size_t)ci * 7 + k];
+            std::vector<float> wt((size_t)7 * last_ch);
+            for (int ci = 0; ci < last_ch; ++ci)
+                for (int k = 0; k < 7; ++k) wt[(size_t)k * last_ch + ci] = w->f[(size_t)ci * 7 + k];
             h->post_w = upload(h, wt);
             h->post_b = upload(h, b);
             ok = h->post_w && h->post_b;
@@ -364,7 +368,7 @@ void scale_lens(const dtts_config& c, const int32_t* lens, int* lensS, int B, in
 // consumes (written by the producer's epilogue; bf16 mode, per-convolution path only).
 
 // how ResBlock rb (= stage * n_resblock_kernels + j) of a C = ch stage runs.  fuse = false: per-convolution kernels everywhere
-enum RbPath { RB_WHOLE, RB_VPAIR, RB_CONVS };   // rblock.hip / rb2x.hip; vpair.hip (ResBlock1 only); vconv, convolution by convolution
+enum RbPath { RB_WHOLE, RB_VPAIR, RB_CONVS };   // rblock.hip / rbn.hip / rb2x.hip; vpair.hip (ResBlock1 only); vconv, convolution by convolution
 RbPath rb_path(const dtts_ctx* h, bool fuse, int ch, size_t rb) {
     if (fuse && !h->rbf1[rb].empty()) return RB_WHOLE;
     if (h->resblock2) return RB_CONVS;
@@ -506,6 +510,29 @@ struct VocRun {
         return DTTS_OK;
     }
 
+    // whole ResBlock1 of a narrow stage (C = 16 / 8) in one kernel (rbn.hip); tune bits 9 / 12 / 14 / 15 have no meaning here
+    int rbn(int j) {
+        const auto& g1 = h->rbf1[(size_t)i * nk + j];
+        const auto& g2 = h->rbf2[(size_t)i * nk + j];
+        RBnParams rp;
+        whole_rb_params(rp, j, j);
+        rp.K = g1[0].K;
+        rp.Kp = rbn_padded_taps(ch, g1[0].K);
+        int frag = g1[0].frag;   // the order the launch's packs are in; a mixed set is in no kernel's order (0)
+        for (int mth = 0; mth < 3; ++mth) {
+            if (g1[mth].frag != frag || g2[mth].frag != frag) frag = 0;
+            rp.w1[mth] = (const uint4*)g1[mth].w_hi;
+            rp.w2[mth] = (const uint4*)g2[mth].w_hi;
+            rp.b1[mth] = g1[mth].bias;
+            rp.b2[mth] = g2[mth].bias;
+            rp.dil[mth] = g1[mth].dil;
+        }
+        if (h->debug_misorder) frag = 16;   // (self-test of the launcher's refusal: dtts_config.debug_redzone = 2)
+        Timed tm(h, TV, s);
+        LAUNCH(rbn_launch(rp, ch, frag, s));
+        return DTTS_OK;
+    }
+
     // whole ResBlock2 in one kernel (rb2x.hip); tune bits 9 / 12 / 15 have no meaning here
     int rb2x(int j) {
         const auto& fv = h->rbf1[(size_t)i * nk + j];
@@ -582,6 +609,7 @@ struct VocRun {
             const bf* xa = mth == 0 ? Xa : Ra;
             if (!h->resblock2) {   // only leaky_relu(xt) in bf16 is ever consumed
                 VConvParams p = vparams(c1[mth], xa, lout, B, Tcur);
+                p.ldx = ch;    // (the activations are [T][ch]; below 32 channels the pack's C_in_pad is wider than the rows)
                 p.ya = Ta;
                 p.ldya = ch;
                 p.slope = 0.1f;
@@ -590,6 +618,7 @@ struct VocRun {
                 xa = Ta;
             }
             VConvParams p = vparams(h->resblock2 ? c1[mth] : h->rb2[(size_t)i * nk + j][mth], xa, lout, B, Tcur);
+            p.ldx = ch;
             p.res = mth == 0 ? Xf : Rf;
             p.ldres = ch;
             if (mth < n - 1) {
@@ -696,6 +725,7 @@ int hifigan_forward_fused(dtts_ctx* h, const float* mel, const int32_t* lens, in
         for (int j = 0; j < nk; ++j) need_xa = need_xa || rb_path(h, fuse, ch, (size_t)i * nk + j) == RB_CONVS;
         {   // ups[i] (polyphase): Sa [B,Tin,2ch] -> Xf / Xa [B,Tin,u*ch] == [B,Tin*u,ch]
             VConvParams p = exact ? vparams_x3(h->ups[i], Sf, 2 * ch, 0.1f, lin, B, Tin) : vparams(h->ups[i], Sa, lin, B, Tin);
+            if (!exact) p.ldx = 2 * ch;   // Sa is [T][2 ch] (= C_in_pad except below 32 channels)
             p.small_tiles = exact;   // narrow split-operand upsamplers: 64-row tiles, 4 workgroups / CU (-0.15 ms same-box)
             p.yf = Xf;
             p.ldyf = u * ch;
@@ -712,7 +742,8 @@ int hifigan_forward_fused(dtts_ctx* h, const float* mel, const int32_t* lens, in
         r.last_stage = i == nup - 1;
         for (int j = 0; j < nk; ++j) {
             const RbPath path = rb_path(h, fuse, ch, (size_t)i * nk + j);
-            const int rc = path == RB_WHOLE ? (h->resblock2 ? r.rb2x(j) : r.rblock(j, plan.fuse_n[i]))
+            const bool narrow = path == RB_WHOLE && !h->resblock2 && h->rbf1[(size_t)i * nk + j][0].frag == RBN_FRAG;
+            const int rc = path == RB_WHOLE ? (h->resblock2 ? r.rb2x(j) : (narrow ? r.rbn(j) : r.rblock(j, plan.fuse_n[i])))
                                             : (path == RB_VPAIR ? r.vpair(j) : r.convs(j));
             if (rc) return rc;
         }
@@ -721,6 +752,7 @@ int hifigan_forward_fused(dtts_ctx* h, const float* mel, const int32_t* lens, in
         const int Tcur = (int)g.rows[nup], ch = g.ch[nup];
         VConvParams p = exact ? vparams_x3(h->conv_post, Sf, ch, 0.01f, lensS + (size_t)nup * B, B, Tcur)
                               : vparams(h->conv_post, Sa, lensS + (size_t)nup * B, B, Tcur);
+        if (!exact) p.ldx = ch;
         p.yf = wav;
         p.ldyf = 1;
         p.post_tanh = 1;

@@ -101,6 +101,13 @@ HIFIGAN_V3 = {
     "resblock_dilation_sizes": [[1, 2], [2, 6], [3, 12]],
 }
 
+# the small "V2" generator of the original HifiGAN release (config_v2.json): ResBlock1, upsample_initial_channel 128 (widths 64 / 32 / 16 / 8)
+HIFIGAN_V2 = {
+    "resblock": "1", "upsample_rates": [8, 8, 2, 2], "upsample_kernel_sizes": [16, 16, 4, 4],
+    "upsample_initial_channel": 128, "resblock_kernel_sizes": [3, 7, 11],
+    "resblock_dilation_sizes": [[1, 3, 5], [1, 3, 5], [1, 3, 5]],
+}
+
 HIFIGAN_DEFAULTS = {
     "resblock": "1", "upsample_rates": [8, 8, 2, 2], "upsample_kernel_sizes": [16, 16, 4, 4],
     "upsample_initial_channel": 512, "resblock_kernel_sizes": [3, 7, 11],

@@ -218,6 +218,14 @@ def hifigan_config_v3():
             "resblock_dilation_sizes": [[1, 2], [2, 6], [3, 12]]}
 
 
+def hifigan_config_v2():
+    """the small "V2" generator of the original HifiGAN release (config_v2.json): ResBlock1 like V1 with
+    ``upsample_initial_channel`` 128, i.e. stage widths 64 / 32 / 16 / 8 (hop 256)"""
+    return {"resblock": "1", "upsample_rates": [8, 8, 2, 2], "upsample_kernel_sizes": [16, 16, 4, 4],
+            "upsample_initial_channel": 128, "resblock_kernel_sizes": [3, 7, 11],
+            "resblock_dilation_sizes": [[1, 3, 5], [1, 3, 5], [1, 3, 5]]}
+
+
 def hifigan_state_dict(seed=1234, weight_norm=True, cfg=None):
     """numpy state dict of ``HifiGanGenerator`` (``state_dict.model_gen``), weight-norm form by default."""
     cfg = cfg or hifigan_config()

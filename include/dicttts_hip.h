@@ -101,9 +101,14 @@ typedef struct dtts_config {
      * 3..11 and every pair (d0, d1) whose halo (K - 1) / 2 * (d0 + d1) leaves at least 32 output rows in a tile of 512 / 512 / 256 /
      * 128 rows within the LDS (dict_tts_amd/csrc/rb2x.h: rb2x_supported); other shapes run convolution by convolution in
      * DTTS_VOC_BF16 and DTTS_VOC_BF16X3 and are refused by dtts_finalize_weights in DTTS_VOC_F16.  tune_flags bits 9 / 12 / 14 / 15
-     * concern ResBlock1 kernels only and do not change a ResBlock2 result. */
+     * concern ResBlock1 kernels only and do not change a ResBlock2 result.  A ResBlock1 runs as one fused launch at widths 32 / 64
+     * (every odd kernel 3..11) and 128 / 256 (k = 3; other kernels per iteration), and at the narrow widths 16 / 8 of the V2 generators
+     * (upsample_initial_channel 128) for odd kernels 3..11 and every dilation triple whose halo (K - 1) / 2 * (d0 + d1 + d2 + 3)
+     * leaves at least 32 output rows in a 256-row tile under the fused conv_post (dict_tts_amd/csrc/rbn.h: rbn_supported); a last
+     * stage of 32, 16 or 8 channels gets conv_post + tanh in its last ResBlock's launch.  tune_flags bits 9 / 12 / 14 / 15 do not
+     * change a result at the narrow widths. */
     int32_t resblock_dilation_sizes[4][3]; /* (1,3,5) x3 */
-    int32_t vocoder_precision;        /* DTTS_VOC_F16 (default) | DTTS_VOC_BF16 | DTTS_VOC_BF16X3 */
+    int32_t vocoder_precision;        /* DTTS_VOC_F16 (default) | DTTS_VOC_BF16 | DTTS_VOC_BF16X3; DTTS_VOC_F16 needs ResBlock widths 8 / 16 / 32 / 64 / 128 / 256 */
     /* FFT block stack (FFTBlocks, modules/fastspeech/tts_modules.py:458-493); width = hidden_size, heads = num_heads */
     int32_t fft_layers;               /* dec_layers 4                          egs/egs_bases/tts/base.yaml:68 */
     int32_t fft_kernel_size;          /* dec_ffn_kernel_size 9                 base.yaml:72                   */

@@ -98,6 +98,7 @@ def main():
     ap.add_argument("ckpt_dir", nargs="?", help="vocoder checkpoint directory (vocoders/hifigan.py:16-52 discovery rule)")
     ap.add_argument("--synthetic", action="store_true", help="the repo's seeded synthetic generator instead of a checkpoint")
     ap.add_argument("--v3", action="store_true", help="(with --synthetic) the V3 ResBlock2 generator (synth.hifigan_config_v3)")
+    ap.add_argument("--v2", action="store_true", help="(with --synthetic) the small V2 generator (synth.hifigan_config_v2)")
     ap.add_argument("--scale-resblocks", type=float, default=1.0, help="(with --synthetic) multiply every ResBlock weight_g: moves the checkpoint across the margin")
     ap.add_argument("--mels", type=int, default=16, help="synthetic mels to run when no --mel-npy is given")
     ap.add_argument("--frames", type=int, default=200)
@@ -108,7 +109,7 @@ def main():
         sys.exit("validate_checkpoint.py needs a ROCm GPU (the HIP path has no CPU fallback)")
     T_ = lambda x: torch.from_numpy(np.ascontiguousarray(x))
     if a.synthetic:
-        cfg = synth.hifigan_config_v3() if a.v3 else synth.hifigan_config()
+        cfg = synth.hifigan_config_v3() if a.v3 else (synth.hifigan_config_v2() if a.v2 else synth.hifigan_config())
         sd = {k: T_(v) for k, v in synth.hifigan_state_dict(1234, cfg=cfg).items()}
         if a.scale_resblocks != 1.0:
             sd = {k: (v * a.scale_resblocks if k.startswith("resblocks.") and k.endswith("weight_g") else v) for k, v in sd.items()}

@@ -17,7 +17,8 @@ ap.add_argument("--B", type=int, default=60)
 ap.add_argument("--T", type=int, default=740)
 ap.add_argument("--iters", type=int, default=5)
 ap.add_argument("--precision", default="f16")
-ap.add_argument("--config", choices=["default", "v3"], default="default", help="the Biaobei ResBlock1 generator, or the V3 ResBlock2 one (synth.hifigan_config_v3)")
+ap.add_argument("--config", choices=["default", "v2", "v3"], default="default",
+                help="the Biaobei ResBlock1 generator, the small V2 one (synth.hifigan_config_v2) or the V3 ResBlock2 one (synth.hifigan_config_v3)")
 ap.add_argument("--unfused", action="store_true", help="(bf16) one vconv launch per convolution")
 ap.add_argument("--uniform", action="store_true", help="every utterance T frames long (tile-count experiments)")
 ap.add_argument("--tune", type=int, default=0, help="dtts_config.tune_flags (A/B switches, include/dicttts_hip.h)")
@@ -26,7 +27,7 @@ a = ap.parse_args()
 if a.lib:
     abi.load_library(os.path.abspath(a.lib))
 T_ = lambda x: torch.from_numpy(np.ascontiguousarray(x))
-gen_cfg = synth.hifigan_config_v3() if a.config == "v3" else synth.hifigan_config()
+gen_cfg = {"v3": synth.hifigan_config_v3, "v2": synth.hifigan_config_v2}.get(a.config, synth.hifigan_config)()
 
 
 def flop_per_frame(cfg):
