@@ -15,8 +15,10 @@ DTTS_F32, DTTS_I64 = 0, 1
 VOC_BF16, VOC_BF16X3, VOC_F16 = 0, 1, 2
 VOC_PRECISIONS = {"f16": VOC_F16, "bf16": VOC_BF16, "bf16x3": VOC_BF16X3}
 PART_ACOUSTIC, PART_VOCODER, PART_FFT = 1, 2, 4
+PART_MELSPEC = 8    # the log-mel front end: "melspec.mel_basis" + "melspec.window"; rebuilt by every finalize that names it
 OUT_PRON_ATTN, OUT_DUR, OUT_MEL2WORD, OUT_DICT_ATTN, OUT_WORD_ENCODER_OUT, OUT_X_MASK, OUT_CONTEXT, OUT_MEL_LENS = range(1, 9)
 OUT_POSTERIOR = 9   # not a copy: the posterior pass, dst = a PosteriorArgs block (include/dicttts_hip.h)
+OUT_MELSPEC = 10     # not a copy, needs no encode: wav -> log-mel, dst = a MelspecArgs block
 SPK_EMBED, SPK_ID = 1, 2   # dtts_text2mel_speakers kinds: fp32 [B,256] (use_spk_embed) / int64 [B] (use_spk_id)
 TIMER_VOC_CONV, TIMER_S2PA = 1, 2
 TIMER_STAGE_ENCODER, TIMER_STAGE_DICT_ENCODER, TIMER_STAGE_FVAE, TIMER_STAGE_HIFIGAN = 3, 4, 5, 6   # the reference's profile_infer names
@@ -34,6 +36,12 @@ class PosteriorArgs(C.Structure):
     _fields_ = [("size", C.c_int32), ("mel_ld", C.c_int32), ("eps_ld", C.c_int32), ("mel_cap", C.c_int32),
                 ("tgt_mels_dev", C.c_void_p), ("eps_dev", C.c_void_p), ("mel_out_dev", C.c_void_p), ("m_q_dev", C.c_void_p),
                 ("logs_q_dev", C.c_void_p), ("z_p_dev", C.c_void_p), ("kl_dev", C.c_void_p)]
+
+
+class MelspecArgs(C.Structure):
+    """dtts_melspec_args (include/dicttts_hip.h): the argument block of dtts_text2mel_fetch(DTTS_OUT_MELSPEC)"""
+    _fields_ = [("size", C.c_int32), ("hop", C.c_int32), ("B", C.c_int32), ("wav_ld", C.c_int32), ("mel_cap", C.c_int32), ("eps", C.c_float),
+                ("wav_dev", C.c_void_p), ("wav_lens_dev", C.c_void_p), ("mel_dev", C.c_void_p), ("mel_lens_dev", C.c_void_p), ("lin_dev", C.c_void_p)]
 
 
 class DttsConfig(C.Structure):
@@ -211,6 +219,13 @@ class Context:
         (device pointers; eps / m_q / logs_q / z_p / kl may be None)"""
         a = PosteriorArgs(C.sizeof(PosteriorArgs), int(mel_ld), int(eps_ld), int(mel_cap), tgt_mels, eps, mel_out, m_q, logs_q, z_p, kl)
         self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_POSTERIOR, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_POSTERIOR)")
+
+    def melspec(self, wav, wav_lens, B, wav_ld, hop, mel, mel_cap, mel_lens, stream, eps=1e-6, lin=None):
+        """log-mel spectrograms of B waveforms in one launch (dtts_text2mel_fetch(DTTS_OUT_MELSPEC); needs PART_MELSPEC finalised, no encode):
+        device pointers wav f32 [B, wav_ld], wav_lens i32 [B] or None, mel f32 [B, mel_cap, n_mels] out, mel_lens i32 [B] out or None,
+        lin f32 like mel or None: the mel values before the floor and the logarithm"""
+        a = MelspecArgs(C.sizeof(MelspecArgs), int(hop), int(B), int(wav_ld), int(mel_cap), float(eps), wav, wav_lens or None, mel, mel_lens or None, lin or None)
+        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_MELSPEC, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_MELSPEC)")
 
     def fetch(self, what, dst, stream):
         self._chk(self.lib.dtts_text2mel_fetch(self.h, what, dst, stream), "dtts_text2mel_fetch")

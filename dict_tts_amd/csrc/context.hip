@@ -176,13 +176,16 @@ int dtts_finalize_weights(dtts_handle h, int parts) {
     if ((parts & DTTS_PART_ACOUSTIC) && !h->acoustic_ready) rc = build_acoustic(h);
     if (rc == DTTS_OK && (parts & DTTS_PART_VOCODER) && !h->vocoder_ready) rc = build_vocoder(h);
     if (rc == DTTS_OK && (parts & DTTS_PART_FFT) && !h->fft_ready) rc = build_fft(h);
+    const bool ms = rc == DTTS_OK && (parts & DTTS_PART_MELSPEC);   // every call rebuilds this plan from the tensors loaded last
+    if (ms) rc = build_melspec(h);
     if (rc == DTTS_OK) {
         // host copies are no longer needed for finished parts
         for (auto it = h->w.begin(); it != h->w.end();) {
             const bool a = it->first.rfind("model.", 0) == 0 && h->acoustic_ready;
             const bool v = it->first.rfind("vocoder.", 0) == 0 && h->vocoder_ready;
             const bool f = it->first.rfind("fft.", 0) == 0 && h->fft_ready;
-            it = (a || v || f) ? h->w.erase(it) : std::next(it);
+            const bool m = it->first.rfind("melspec.", 0) == 0 && ms;
+            it = (a || v || f || m) ? h->w.erase(it) : std::next(it);
         }
     }
     return rc;

@@ -26,6 +26,7 @@
 #include "rb2x.h"
 #include "rbn.h"
 #include "flowstack.h"
+#include "melspec.h"
 
 // dtts_config.tune_flags: the bits the library honours are listed at TUNE_RELEASE_MASK (context.hip)
 #define DTTS_TUNE(h, bit) (((h)->tune & (bit)) != 0)
@@ -215,6 +216,11 @@ struct dtts_ctx {
     float* fs_w_fwd = nullptr;               // the same blocks packed for the fused kernel's masked forward form (flowstack.hip: MASK), or null
     dtts::PackedConv fs_cond_fwd;                  //   with their cond_layers as one 1x1 convolution in forward execution order
     dtts::Arena a_post;
+    // ---- log-mel front end (dtts_text2mel_fetch(DTTS_OUT_MELSPEC); melspec.hip): the plan of the last dtts_finalize_weights(DTTS_PART_MELSPEC)
+    bool melspec_ready = false;
+    int ms_n_fft = 0, ms_n_mels = 0, ms_win = 0, ms_sg_lo = 0, ms_sg_hi = 0;
+    float *ms_basis = nullptr, *ms_melpack = nullptr;   // windowed DFT basis and mel basis in fragment order
+    int ms_skew_hop = 0, ms_skew = 8;                   // the slab skew chosen for the hop of the last call
 };
 
 namespace dtts {
@@ -308,9 +314,11 @@ struct Timed {
     ~Timed() { stop(); }
 };
 
-// ---- the builders behind dtts_finalize_weights (text2mel_build.hip, vocoder.hip, fft_blocks.hip)
+// ---- the builders behind dtts_finalize_weights (text2mel_build.hip, vocoder.hip, fft_blocks.hip, melspec.hip)
 int build_acoustic(dtts_ctx* h);
 int build_vocoder(dtts_ctx* h);
 int build_fft(dtts_ctx* h);
+int build_melspec(dtts_ctx* h);   // melspec.hip
+int melspec_forward(dtts_ctx* h, const dtts_melspec_args* a, hipStream_t stream);
 
 } // namespace dtts

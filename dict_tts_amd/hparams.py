@@ -90,7 +90,8 @@ BIAOBEI_DEFAULTS = {
     "fvae_dec_n_layers": 4, "fvae_enc_n_layers": 8, "prior_glow_hidden": 64, "glow_kernel_size": 3,
     "prior_glow_n_blocks": 4, "dur_predictor_layers": 3, "dur_predictor_kernel": 5, "frames_multiple": 4,
     "language": "zh", "use_post_glow": False, "use_prior_glow": True, "dur_scale": "log", "dur_level": "word",
-    "audio_sample_rate": 22050, "hop_size": 256, "use_spk_embed": False, "use_spk_id": False, "num_spk": 1,
+    "audio_sample_rate": 22050, "hop_size": 256, "fft_size": 1024, "win_size": 1024, "fmin": 80, "fmax": 7600,   # egs/egs_bases/tts/base.yaml:49-54
+    "loud_norm": False, "min_level_db": -100, "use_spk_embed": False, "use_spk_id": False, "num_spk": 1,
     "vocoder": "dict_tts_amd.vocoder.HifiGAN", "vocoder_ckpt": "", "use_word_input": True, "use_dict": True,
 }
 

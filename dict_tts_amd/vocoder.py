@@ -19,6 +19,7 @@ from . import hparams as hparams_mod
 from .hparams import HIFIGAN_DEFAULTS, fill_abi_config, load_config_chain
 
 VOCODERS = {}
+_MELSPEC_CACHE = {}   # HifiGAN.wav2spec: one MelSpectrogram (with a context of its own) per front-end configuration
 
 
 def register_vocoder(cls):
@@ -154,6 +155,57 @@ class HifiGAN:
         """vocoders/hifigan.py:54-62; one utterance, numpy in / numpy out"""
         c = torch.as_tensor(np.asarray(mel), dtype=torch.float32).unsqueeze(0).to(self.device)
         return self.forward_batch(c, check=True).view(-1).cpu().numpy()
+
+    @staticmethod
+    def wav2spec(wav_fn, return_linear=False):
+        """vocoders/base_vocoder.py:36-53 (process_utterance with vocoder='pwg'; loud_norm and trim_long_sil are not implemented) on the
+        device: wav_fn = a float waveform array, or the path of a 16-bit / float PCM wav at hparams['audio_sample_rate'] (nothing here
+        resamples) -> (wav padded to T * hop_size samples, log10-mel [T, n_mels]) as host numpy, the reference's return convention
+        (data_gen/tts/data_gen_utils.py:138-140)."""
+        if return_linear:
+            raise NotImplementedError("wav2spec(return_linear=True): the linear-spectrogram branch of process_utterance "
+                                      "(data_gen/tts/data_gen_utils.py:144-147) is not implemented on the HIP path")
+        from . import melspec
+        hp = {**hparams_mod.BIAOBEI_DEFAULTS, **hparams_mod.hparams}
+        if hp.get("loud_norm"):
+            raise NotImplementedError("wav2spec: loud_norm=True (pyloudnorm normalisation) is not implemented on the HIP path")
+        if isinstance(wav_fn, (str, os.PathLike)):
+            wav = melspec.read_wav(wav_fn, int(hp["audio_sample_rate"]))
+        else:
+            wav = np.asarray(wav_fn, dtype=np.float32).reshape(-1)
+        key = tuple(hp[k] for k in ("fft_size", "hop_size", "win_size", "audio_num_mel_bins", "fmin", "fmax", "audio_sample_rate"))
+        ms = _MELSPEC_CACHE.get(key)
+        if ms is None:
+            ms = _MELSPEC_CACHE[key] = melspec.MelSpectrogram(hp)
+        mel, _ = ms(wav)
+        mel = mel[0].cpu().numpy()
+        out = np.zeros(mel.shape[0] * ms.hop, np.float32)   # librosa_pad_lr(wav, fft_size, hop_size, 1): zeros up to the next multiple of hop
+        out[:len(wav)] = wav
+        return out, mel
+
+    def mel_roundtrip(self, mels, lens=None):
+        """mel(spec2wav(mel)) against mel without leaving the device — what the reference's vocoder validation reports, and a check of every
+        waveform of a batch that needs no oracle waveform.  mels [B, T, n_mels] float32 cuda tensor, lens [B] valid frames or None
+        -> [B] float32 cuda tensor: the mean |delta log10-mel| over the first lens[b] frames of each utterance.  (The vocoder's T * hop
+        samples give T + 1 frames, as in the reference's binariser; frame T has no counterpart and is left out.)"""
+        from . import melspec
+        ms = getattr(self, "_melspec", None)
+        if ms is None:
+            hp = {**hparams_mod.BIAOBEI_DEFAULTS, **hparams_mod.hparams}
+            if int(hp["hop_size"]) != self.hop:
+                raise abi.DttsError(f"mel_roundtrip: hop_size={hp['hop_size']} of the hparams, but the generator upsamples by {self.hop}")
+            ms = self._melspec = melspec.MelSpectrogram(hp, ctx=self.ctx)
+        B, T, n_mels = mels.shape
+        if n_mels != ms.n_mels:
+            raise abi.DttsError(f"mel_roundtrip: mels of {n_mels} bins, audio_num_mel_bins={ms.n_mels}")
+        if lens is None:
+            lens = torch.full((B,), T, dtype=torch.int32, device=mels.device)
+        lens = lens.to(device=mels.device, dtype=torch.int32)
+        wav = self.forward_batch(mels, lens)
+        back, _ = ms(wav, lens * self.hop)
+        valid = (torch.arange(T, device=mels.device)[None, :] < lens[:, None]).to(torch.float32)
+        diff = (back[:, :T] - mels).abs().mean(dim=2) * valid
+        return diff.sum(dim=1) / lens.clamp(min=1).to(torch.float32)
 
     def overflowed(self):
         """True when a forward since the last call of this method (or construction) delivered non-finite pre-tanh samples, i.e. an fp16

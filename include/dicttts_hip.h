@@ -161,6 +161,12 @@ DTTS_API int dtts_load_weight(dtts_handle h, const char* name, const void* host_
 #define DTTS_PART_ACOUSTIC 1
 #define DTTS_PART_VOCODER 2
 #define DTTS_PART_FFT 4 /* an FFTBlocks state dict loaded under "fft.<key>"  */
+/* The log-mel front end (DTTS_OUT_MELSPEC below): "melspec.mel_basis" [n_mels][n_fft / 2 + 1] (librosa.filters.mel as
+ * data_gen/tts/data_gen_utils.py:128-130 calls it) and "melspec.window" [win_length] (the periodic Hann window); n_fft, n_mels and win_length
+ * follow from the shapes.  Supported: n_fft 512 / 1024 / 2048, 1 <= win_length <= n_fft, 1 <= n_mels <= 128, else DTTS_E_INVAL naming the
+ * value.  Unlike the other parts this one is rebuilt by EVERY call that names it, from the tensors loaded last: finalising again with
+ * other tensors replaces the plan (the old packs stay allocated until dtts_destroy: a launch in flight may still read them). */
+#define DTTS_PART_MELSPEC 8
 /* Fold, repack into MFMA fragment order and upload.  Fails with DTTS_E_NOENT naming the first missing tensor. */
 DTTS_API int dtts_finalize_weights(dtts_handle h, int parts);
 
@@ -296,6 +302,29 @@ typedef struct dtts_posterior_args {
     float* z_p_dev;               /* or NULL */
     float* kl_dev;                /* or NULL */
 } dtts_posterior_args;
+/*
+ * DTTS_OUT_MELSPEC: not a copy either, and needs NO encode — the vocoder's other direction, BaseVocoder.wav2spec (vocoders/base_vocoder.py:36-53
+ * -> process_utterance, data_gen/tts/data_gen_utils.py:122-134, vocoder='pwg', no loudness normalisation, no trimming) for a batch, in one
+ * launch on `stream`, no host synchronisation: dst = (dtts_melspec_args*), args->size = sizeof(*args).  Per utterance b of len_b =
+ * wav_lens_dev[b] samples (clamped to [0, wav_ld]; NULL = wav_ld): n_fft / 2 zeros on both sides (librosa center=True, pad_mode='constant'),
+ * T_b = 1 + len_b / hop frames of n_fft samples, the window of dtts_finalize_weights(DTTS_PART_MELSPEC) centred in the frame, |rfft|, the mel
+ * basis, log10(max(eps, .)).  wav_dev f32 [B][wav_ld]; mel_dev f32 [B][mel_cap][n_mels], rows >= T_b of utterance b are left untouched;
+ * mel_lens_dev i32 [B] receives T_b (or NULL); lin_dev (or NULL) receives the same rows before the floor and the logarithm.  The contraction is exact fp32 products, summed in fp32 over eight samples at a time and in fp64 across those, against a windowed DFT basis
+ * computed in fp64; every utterance's result is bit-identical alone and inside any batch.  DTTS_E_STATE without a finalised plan;
+ * DTTS_E_INVAL (naming the value) for a wrong size, a hop outside 1 .. n_fft, B <= 0, mel_cap < 1 + wav_ld / hop, or eps <= 0.
+ */
+#define DTTS_OUT_MELSPEC 10
+typedef struct dtts_melspec_args {
+    int32_t size;                 /* sizeof(dtts_melspec_args) */
+    int32_t hop;                  /* hop_size: any integer in 1 .. n_fft */
+    int32_t B, wav_ld, mel_cap;
+    float eps;                    /* the floor under the logarithm (the reference: 1e-6) */
+    const float* wav_dev;
+    const int32_t* wav_lens_dev;  /* or NULL */
+    float* mel_dev;
+    int32_t* mel_lens_dev;        /* or NULL */
+    float* lin_dev;               /* or NULL: f32 [B][mel_cap][n_mels], the mel values BEFORE max(eps, .) and the logarithm (accuracy tests) */
+} dtts_melspec_args;
 DTTS_API int dtts_text2mel_fetch(dtts_handle h, int what, void* dst_dev, dtts_stream stream);
 
 /*

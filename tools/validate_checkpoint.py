@@ -8,6 +8,7 @@ command on a machine that has the checkpoint and a GPU:
 
     python tools/validate_checkpoint.py /path/to/vocoder_ckpt_dir            # config.yaml + model_ckpt_steps_*.ckpt, or config.json + generator_v1
     python tools/validate_checkpoint.py /path/to/dir --mel-npy a.npy b.npy   # real mels [T,80] instead of synthetic ones
+    python tools/validate_checkpoint.py /path/to/dir --wavs DIR              # mels made on the device from the recordings DIR/*.wav (HifiGAN.wav2spec)
     python tools/validate_checkpoint.py --synthetic                           # the repo's seeded generator (what CI can run)
 
 It prints, in this order:
@@ -20,6 +21,8 @@ It prints, in this order:
      detector's count (dtts_vocoder_nonfinite);
   4. the waveform gate of BASELINE.json (RMS(gpu - ref) <= 1e-4, |RMS(gpu) - RMS(ref)| <= 1e-4) of fp16 and of bf16x3 against the oracle on
      the first --gate mels;
+  4b. the mel round trip mel(spec2wav(mel)) against mel per utterance (HifiGAN.mel_roundtrip: mean |delta log10-mel|), the figure the
+     reference's vocoder validation reports.  It means something for a trained checkpoint only: a synthetic generator does not invert mels;
   5. the verdict: the mode HifiGAN(precision=None) runs this checkpoint in, and whether that mode met the gate.
 Exit code 0 = the mode AUTO chose meets the gate with a clean guard; 1 otherwise.
 """
@@ -103,6 +106,7 @@ def main():
     ap.add_argument("--mels", type=int, default=16, help="synthetic mels to run when no --mel-npy is given")
     ap.add_argument("--frames", type=int, default=200)
     ap.add_argument("--mel-npy", nargs="*", default=[], help="real mels, each [T,80] float32 (.npy)")
+    ap.add_argument("--wavs", help="directory of recordings (*.wav at audio_sample_rate): the mels are made from them on the device (HifiGAN.wav2spec)")
     ap.add_argument("--gate", type=int, default=3, help="mels compared with the CPU oracle (fp32 torch; ~1 s per 100 frames)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -120,7 +124,14 @@ def main():
     else:
         ap.error("give a checkpoint directory or --synthetic")
     full_cfg = {**vocoder.HIFIGAN_DEFAULTS, **(cfg or {})}
-    mels = [np.load(f).astype(np.float32) for f in a.mel_npy] or [synth.random_mel(100 + i, a.frames, f"val{i}") for i in range(a.mels)]
+    wav_mels = []
+    if a.wavs:
+        import glob
+        files = sorted(glob.glob(os.path.join(a.wavs, "*.wav")))
+        if not files:
+            sys.exit(f"--wavs {a.wavs}: no *.wav files")
+        wav_mels = [vocoder.HifiGAN.wav2spec(fn)[1] for fn in files]
+    mels = wav_mels or [np.load(f).astype(np.float32) for f in a.mel_npy] or [synth.random_mel(100 + i, a.frames, f"val{i}") for i in range(a.mels)]
     print(f"checkpoint: {src}\n  upsample_rates {full_cfg['upsample_rates']}  initial channels {full_cfg['upsample_initial_channel']}  "
           f"resblock kernels {full_cfg['resblock_kernel_sizes']}\n  {len(mels)} mels, {sum(m.shape[0] for m in mels)} frames, "
           f"|mel| max {max(float(np.abs(m).max()) for m in mels):.2f}")
@@ -193,6 +204,10 @@ def main():
         ok = ok and worst[0] <= 1e-4 and worst[1] <= 1e-4
         gate[name] = ok
         print(f"   {name:7s} rms(diff) {worst[0]:.3e}  |drms| {worst[1]:.2e}  ->  {'PASS' if ok else 'FAIL'}")
+
+    print("\n4b. mel round trip mel(spec2wav(mel)) vs mel, mean |delta log10-mel| per utterance" + (" (synthetic weights: the value means nothing)" if a.synthetic else ""))
+    for i, m in enumerate(mels[:max(a.gate, 1)]):
+        print(f"   mel {i} ({m.shape[0]} frames): {float(auto.mel_roundtrip(T_(m[None]).cuda())[0]):.4f}")
 
     chosen = VOC_NAMES.get(auto.precision, str(auto.precision))
     chosen_key = "f16" if auto.precision == abi.VOC_F16 else "bf16x3"
