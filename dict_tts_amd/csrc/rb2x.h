@@ -54,7 +54,6 @@ __host__ __device__ inline size_t rb2x_lds_bytes(int C, int W, int time_waves, i
     const size_t ot = (size_t)(W - 2 * halo) * C * 4;
     return (ot > act ? ot : act) + (size_t)time_waves * 32 * (C * 4 + 16);
 }
-inline size_t rb2x_table_bytes(int B) { return (size_t)(3 * B + 2) * sizeof(int); }   // prefix sums [B + 1], counts [B], lengths [B], the claimed tile
 
 // (C, K, d0, d1) the fused kernel runs for EVERY batch size up to DTTS_MAX_VOCODER_BATCH: widths 32 / 64 / 128 / 256, odd K 3 .. 11,
 // dilations >= 1, and the `base` tile keeps at least 32 output rows (38 at C = 32, where the fused conv_post takes 6) with its LDS and

@@ -18,6 +18,7 @@
 #include "rb2x.h"
 #include "rblock.h"
 #include "rb_common.h"
+#include "rb_tiles.h"
 #include "../../include/dicttts_hip.h"
 
 #include <algorithm>
@@ -47,7 +48,7 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
     constexpr int PK = 7, PH = (PK - 1) / 2;
     const int TTo = p.wav ? TT - 2 * PH : TT;
 
-    int* pre = (int*)(smem + p.pre_off);
+    const RbTiles tiles{(int*)(smem + p.pre_off), p.B};
     // zero the guard bands (once; the fused conv_post's fp32 output tile aliases them: again after every tile there)
     auto zero_guard_bands = [&](int t) {
         for (int idx = t; idx < 2 * GR * (PITCH / 16); idx += THREADS) {
@@ -57,29 +58,14 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
         }
     };
     zero_guard_bands(tid);
-    // the valid tiles of the batch (ceil(len_b / TTo) per utterance) are numbered through; a table of the per-utterance counts' prefix sums lives in LDS
+    // the valid tiles of the batch are numbered through (rb_tiles.h: RbTiles)
     int total = 0, j = blockIdx.x;
-    for (int i = tid; i < p.B; i += THREADS) {
-        const int l = p.lens ? p.lens[i] : p.T;
-        pre[p.B + 1 + i] = (l + TTo - 1) / TTo;
-        pre[2 * p.B + 1 + i] = l;
-    }
-    __syncthreads();
-    for (int i = tid; i <= p.B; i += THREADS) {
-        int a = 0;
-        for (int u = 0; u < i; ++u) a += pre[p.B + 1 + u];
-        pre[i] = a;
-    }
-    __syncthreads();
-    total = pre[p.B];
+    tiles.build(p.lens, p.T, TTo, tid, THREADS);
+    total = tiles.total();
     if (j >= total) return;
     const int G = gridDim.x;
 
     typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-    auto locate = [&](int jj, int& bb) {
-        while (pre[bb + 1] <= jj) ++bb;
-        bb = __builtin_amdgcn_readfirstlane(bb);
-    };
     // the residual stream of a tile, fp32, straight into accumulator layout (lane & 31 = row, 4 consecutive channels per 16 B access).
     // Buffer loads over the utterance [0, len) x C return zeros for rows outside it (t < 0 wraps to a huge unsigned offset) = the zero padding.
     auto load_x = [&](f32x16 (&d)[NT], int m, int bb, int base, int ln) {   // 32-row slab m of this wave
@@ -95,12 +81,11 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
                 for (int e = 0; e < 4; ++e) d[n][4 * q + e] = f[e];
             }
     };
-    auto len_of = [&](int bb) { return __builtin_amdgcn_readfirstlane(pre[2 * p.B + 1 + bb]); };
 
     int b = 0, len, t0;
-    locate(j, b);
-    len = len_of(b);
-    t0 = (j - pre[b]) * TTo - (p.wav ? PH : 0);
+    tiles.locate(j, b);
+    len = tiles.len_of(b);
+    t0 = tiles.first_row(j, b, TTo) - (p.wav ? PH : 0);
     f32x16 xr[MT][NT];
 #pragma unroll
     for (int m = 0; m < MT; ++m) load_x(xr[m], m, b, t0 - H, len);
@@ -133,9 +118,9 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
         has_next = jn < total;
         bn = b;
         if (has_next) {
-            locate(jn, bn);
-            lenn = len_of(bn);
-            t0n = (jn - pre[bn]) * TTo - (p.wav ? PH : 0);
+            tiles.locate(jn, bn);
+            lenn = tiles.len_of(bn);
+            t0n = tiles.first_row(jn, bn, TTo) - (p.wav ? PH : 0);
         }
     };
     if (!p.tile_ctr) plan_next();
@@ -207,7 +192,7 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
         } else
             rb_contract<EL, MT, NT, NKG, PITCH, false, 1>(xr, ring, act, xlane - ((p.K - 1) / 2) * d * PITCH, wq, S, d * PITCH);
         if (it == 0) rb_preload<NT>(ring, p.w[1] + wlane, kg_stride);   // the second convolution's first weights fly during barrier + rewrite
-        if (p.tile_ctr && it == 1 && tid == 0) pre[3 * p.B + 1] = G + (int)claim;   // the claimed tile, for everyone (read behind the barrier)
+        if (p.tile_ctr && it == 1 && tid == 0) tiles.publish_claim(G, claim);   // the claimed tile, for everyone (read behind the barrier)
         __syncthreads();               // every wave is done reading the operand tile
         if (it == 0) {
             write_act(xr);             // the operand of the second convolution: leaky_relu of the UPDATED x
@@ -216,11 +201,11 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
     }
 
     if (p.tile_ctr) {
-        jn = __builtin_amdgcn_readfirstlane(pre[3 * p.B + 1]);
+        jn = tiles.claimed();
         plan_next();
     }
     {
-    // ---- epilogue (rblock.hip's): rows [H, H+TT) leave as whole rows through wave-private fp32 staging rows; halo rows are sent out of
+    // ---- epilogue (rblock.hip's transposition, rb_tiles.h's row body): rows [H, H+TT) leave as whole rows through wave-private fp32 staging rows; halo rows are sent out of
     // range explicitly, rows >= len are dropped by the buffer range check
     const auto rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)(p.Sa ? p.Sa + brow * C : (unsigned short*)(p.S + brow * C)), 0,
                                                         len * C * 2, 0x00020000);
@@ -282,79 +267,15 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
                 }
                 continue;
             }
-            if (p.mode == 2) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = o[e] / p.div;
-            }
-            if (!(p.mode == 2 && p.Sa && p.drop_S))
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rs_s, off, 0, VP_ST_AUX);
-            if (p.mode == 2 && p.Sa) {
-                typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-                const u32x2 pk = {pack2bf(lrelu(o[0], p.slope), lrelu(o[1], p.slope)), pack2bf(lrelu(o[2], p.slope), lrelu(o[3], p.slope))};
-                __builtin_amdgcn_raw_buffer_store_b64(pk, rs_a, off == (int)0x80000000 ? off : off >> 1, 0, VP_ST_AUX);
-            }
+            rb_stage_row(o, rs_s, rs_a, off, p.mode, p.div, p.slope, p.drop_S != 0, p.Sa != nullptr, false);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();                               // slab m + 1 reuses this wave's staging block
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
     if constexpr (C == 32) if (wav_now) {   // (the launcher rejects p.wav for other widths)
-        // ---- wav[t] = tanh(b + sum_{tap, c} w[c][tap] * otile[t + tap - 3][c])   (conv_post + tanh, hifigan.py:139-141) in exact fp32,
-        // the arithmetic and the always-on non-finite detector of rblock.hip's fused conv_post, operation for operation
-        __syncthreads();
-        const int q8 = tid & 7, rr = tid >> 3;
-        f32x4 wq[PK];
-#pragma unroll
-        for (int k = 0; k < PK; ++k) wq[k] = *(const f32x4*)(p.post_w + k * C + q8 * 4);
-        const float pb = p.post_b[0];
-        float* wb = p.wav + brow;
-        constexpr int PR = 3;
-        for (int o0 = 0; o0 < TTo; o0 += (THREADS / 8) * PR) {
-            const int ob = o0 + rr * PR;                               // first output of this group: otile rows ob .. ob + PR + PK - 2
-            float a[PR];
-#pragma unroll
-            for (int i = 0; i < PR; ++i) a[i] = 0.f;
-            if (ob < TTo) {
-#pragma unroll
-                for (int jj = 0; jj < PR + PK - 1; ++jj) {
-                    const int row = ob + jj < TTo + PK - 1 ? ob + jj : TTo + PK - 2;   // (rows past the tile feed discarded outputs only)
-                    const f32x4 v = *(const f32x4*)(otile + (size_t)row * OP + q8 * 16);
-#pragma unroll
-                    for (int i = 0; i < PR; ++i) {
-                        const int k = jj - i;
-                        if (k >= 0 && k < PK) {
-                            const float d = __builtin_fmaf(v[3], wq[k][3], __builtin_fmaf(v[2], wq[k][2], __builtin_fmaf(v[1], wq[k][1], __fmul_rn(v[0], wq[k][0]))));
-                            a[i] = __fadd_rn(a[i], d);
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < PR; ++i) {
-                a[i] += __shfl_xor(a[i], 1, 64);
-                a[i] += __shfl_xor(a[i], 2, 64);
-                a[i] += __shfl_xor(a[i], 4, 64);
-            }
-            float prt[PR], th[PR];
-            int nf = 0;   // non-finite SAMPLES of this group (dtts_vocoder_nonfinite counts samples)
-#pragma unroll
-            for (int i = 0; i < PR; ++i) {
-                prt[i] = a[i] + pb;
-                th[i] = __builtin_fmaf(-2.f, __builtin_amdgcn_rcpf(__fadd_rn(__builtin_amdgcn_exp2f(prt[i] * 2.885390081777927f), 1.f)), 1.f);   // (2 log2 e)
-            }
-            if (q8 == 0) {
-#pragma unroll
-                for (int i = 0; i < PR; ++i) {
-                    const int o = ob + i, t = t0 + PH + o;
-                    const bool nonfin = !(__builtin_fabsf(prt[i]) <= 3.0e38f);
-                    if (o < TTo && t < len) {
-                        wb[t] = nonfin ? __builtin_nanf("") : th[i];
-                        nf += nonfin ? 1 : 0;
-                    }
-                }
-                if (nf && p.bad) atomicAdd(p.bad, (unsigned)nf);   // (never on a healthy call)
-            }
-        }
+        __syncthreads();                                               // the fp32 output tile is whole
+        rb_conv_post_tanh<C, THREADS, 3>(otile, p.post_w, p.post_b, p.wav + brow, t0, TTo, len, p.bad, tid);
     }
     }   // (epilogue)
     if constexpr (GUARD) {
@@ -385,33 +306,17 @@ static hipError_t rb2x_launch_cfg(const RB2xParams& p, hipStream_t stream) {
     if (p.wav && (C != 32 || p.mode != 2 || !p.post_w || !p.post_b)) return hipErrorInvalidValue;
     size_t lds = rb2x_lds_bytes(C, W, WT, q.halo, q.guard, p.wav != nullptr);
     q.pre_off = (int)lds;
-    lds += rb2x_table_bytes(p.B);
+    lds += rb_table_bytes(p.B);
     if (lds > 160 * 1024) return hipErrorOutOfMemory;
     if constexpr (EL == EL_F16 && !GUARD) {
         if (p.ovf) return rb2x_launch_cfg<C, MT, NT, WT, WC, EL, true>(p, stream);
     }
-    auto kern = rb2x_kernel<C, MT, NT, WT, WC, EL, GUARD>;
-    static bool configured_dev[64] = {};
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    bool& configured = configured_dev[cur_dev & 63];
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
+    constexpr auto kern = rb2x_kernel<C, MT, NT, WT, WC, EL, GUARD>;
+    if (const hipError_t e = rb_allow_full_lds<kern>(); e != hipSuccess) return e;
     constexpr int THREADS = 64 * WT * WC;
-    static int cus_dev[64] = {};
-    int& cus = cus_dev[cur_dev & 63];
-    if (!cus) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, cur_dev) != hipSuccess) return hipErrorInvalidDevice;
-        cus = prop.multiProcessorCount;
-    }
-    // persistent workgroups: as many as are resident at once (LDS / thread limits), never more than there can be tiles
-    const int per_cu = std::max(1, std::min({(int)(160 * 1024 / lds), 2048 / THREADS, THREADS <= 256 ? 2 : 1}));
-    const long long max_tiles = (long long)p.B * ((p.T + TTo - 1) / TTo);
-    const int grid = (int)std::min<long long>((long long)cus * per_cu, max_tiles);
+    const int cus = rb_device_cus();
+    if (cus <= 0) return hipErrorInvalidDevice;
+    const int grid = rb_resident_grid(cus, lds, THREADS, THREADS <= 256 ? 2 : 1, (long long)p.B * ((p.T + TTo - 1) / TTo));
     if (grid <= 0) return hipSuccess;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), lds, stream, q);
     return hipGetLastError();
@@ -425,18 +330,13 @@ bool rb2x_supported(int C, int K, int d0, int d1) {
     if (!(K & 1) || K < 3 || K > 11 || d0 < 1 || d1 < 1) return false;
     const int halo = rb2x_halo(K, d0, d1), guard = rb2x_guard(K, d0, d1), W = rb2x_base_rows(C);
     if (W - 2 * halo < (C == 32 ? 38 : 32)) return false;
-    return rb2x_lds_bytes(C, W, rb2x_base_time_waves(C), halo, guard, C == 32) + rb2x_table_bytes(DTTS_MAX_VOCODER_BATCH) <= 160 * 1024;
+    return rb2x_lds_bytes(C, W, rb2x_base_time_waves(C), halo, guard, C == 32) + rb_table_bytes(DTTS_MAX_VOCODER_BATCH) <= 160 * 1024;
 }
 
 template <int EL>
 static hipError_t rb2x_launch_el(const RB2xParams& p, int C, hipStream_t stream) {
     const bool wide = rb2x_wide_wanted(C, p.K, rb2x_halo(p.K, p.dil[0], p.dil[1]));
     // RB_TRY: a configuration whose LDS cannot hold the tile table of this many utterances, or whose tile the halo eats, falls through to `base`
-#define RB_TRY(call)                                   \
-    do {                                               \
-        const hipError_t e_ = (call);                  \
-        if (e_ != hipErrorOutOfMemory) return e_;      \
-    } while (0)
     if (C == 32 && wide) RB_TRY((rb2x_launch_cfg<32, 4, 1, 8, 1, EL>(p, stream)));    // 1024-row tile, 8 waves over time
     if (C == 32) return rb2x_launch_cfg<32, 4, 1, 4, 1, EL>(p, stream);               // 512-row tile, 4 waves, two workgroups per CU
     if (C == 64) return rb2x_launch_cfg<64, 4, 1, 4, 2, EL>(p, stream);               // 512-row tile, 8 waves (4 time x 2 channel)
@@ -444,7 +344,6 @@ static hipError_t rb2x_launch_el(const RB2xParams& p, int C, hipStream_t stream)
     if (C == 128) return rb2x_launch_cfg<128, 4, 1, 2, 4, EL>(p, stream);             // 256-row tile, 8 waves (2 time x 4 channel)
     if (C == 256 && wide) RB_TRY((rb2x_launch_cfg<256, 6, 1, 1, 8, EL>(p, stream)));  // 192-row tile
     if (C == 256) return rb2x_launch_cfg<256, 4, 1, 1, 8, EL>(p, stream);             // 128-row tile, 8 waves over channels
-#undef RB_TRY
     return hipErrorInvalidValue;
 }
 

@@ -16,6 +16,7 @@
 // residual registers (accumulator layout, no LDS transposition) slab by slab as the epilogue releases them.
 #include "rblock.h"
 #include "rb_common.h"
+#include "rb_tiles.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -39,14 +40,13 @@ extern "C" __attribute__((visibility("default"))) int dtts_debug_rb_stamps(unsig
 #define RB_T(k)
 #endif
 
-// TB (two LDS activation buffers; no launch configuration selects it: slower, LABNOTES (O)): leaky_relu(x) and leaky_relu(xt) live in SEPARATE buffers, so the rewrite after a
-// contraction needs no write-after-read barrier (nobody reads the buffer it writes): two workgroup barriers per iteration instead of four.
+// (leaky_relu(x) and leaky_relu(xt) time-share ONE LDS buffer.  The form with a buffer each — two workgroup barriers per iteration instead of four —
+// was slower: LABNOTES (O), tools/experiments/rblock_two_buffers.patch)
 // SH: the MFMA shape of every contraction of the kernel (rb_common.h MfmaShape; rblock.h rblock_mfma_shape picks it per width): all row / channel
 // arithmetic of the accumulator layout goes through its helpers, and the packs arrive in its fragment order.
-template <int C, int MT, int NT, int WT, int WC, int EL, int PS, bool GUARD, bool TB = false, class SH = MfmaShape<32>>
+template <int C, int MT, int NT, int WT, int WC, int EL, int PS, bool GUARD, class SH = MfmaShape<32>>
 __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void rblock_kernel(const RBlockParams p) {
     static_assert(WC * NT * 32 == C, "channel tiling must cover C");
-    static_assert(!TB || SH::FRAG == 32, "the two-buffer form was only ever built on 32x32x16");
     typedef typename SH::acc_t acc_t;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int THREADS = 64 * WT * WC;
@@ -58,9 +58,8 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
     constexpr int EP = C * 4 + 16;                 // fp32 staging row
     constexpr int F4 = C / 4, SROWS = WT * 32;
     constexpr size_t ACT_BYTES = (size_t)(W + 2 * RB_GUARD) * PITCH;
-    char* act = smem;                                    // leaky_relu(x)
-    char* act2 = TB ? smem + ACT_BYTES : smem;           // leaky_relu(xt): its own buffer (TB) or the same one, time-shared
-    char* stage = TB ? act2 + RB_GUARD * PITCH : smem + ACT_BYTES;   // epilogue transposition; TB: over the xt buffer's tile rows (dead after the last contraction, rewritten whole by the next tile; its guard bands stay zero)
+    char* act = smem;                                    // leaky_relu(x), then leaky_relu(xt): time-shared
+    char* stage = smem + ACT_BYTES;                      // epilogue transposition
 
     // per-thread coordinates; PS refreshes them through an opaque move at every tile (see the tile loop)
     int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -76,32 +75,20 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
     // takes tiles w, w + G, w + 2G, ...: a table of the per-utterance tile counts' prefix sums lives in LDS.  While a tile is
     // computed the NEXT tile's residual stream is already on its way into registers, so the exposed HBM round trip and the
     // LDS transposition of a per-tile x load disappear from every tile but the workgroup's first.
-    int* pre = (int*)(smem + p.pre_off);
+    const RbTiles tiles{(int*)(smem + p.pre_off), p.B};
     // zero the guard bands (once; the fused conv_post's fp32 output tile aliases them: again after every tile there)
     auto zero_guard_bands = [&](int t) {
         for (int idx = t; idx < 2 * RB_GUARD * (PITCH / 16); idx += THREADS) {
             const int r = idx / (PITCH / 16), c = idx % (PITCH / 16);
             const int row = r < RB_GUARD ? r : W + r;
             *(uint4*)(act + row * PITCH + c * 16) = make_uint4(0, 0, 0, 0);
-            if constexpr (TB) *(uint4*)(act2 + row * PITCH + c * 16) = make_uint4(0, 0, 0, 0);
         }
     };
     zero_guard_bands(tid);
     int total = 0, j = blockIdx.x;
     if constexpr (PS) {
-        for (int i = tid; i < p.B; i += THREADS) {
-            const int l = p.lens ? p.lens[i] : p.T;
-            pre[p.B + 1 + i] = (l + TTo - 1) / TTo;
-            pre[2 * p.B + 1 + i] = l;                  // (the lengths too: no global load between two tiles)
-        }
-        __syncthreads();
-        for (int i = tid; i <= p.B; i += THREADS) {
-            int a = 0;
-            for (int u = 0; u < i; ++u) a += pre[p.B + 1 + u];
-            pre[i] = a;
-        }
-        __syncthreads();
-        total = pre[p.B];
+        tiles.build(p.lens, p.T, TTo, tid, THREADS);
+        total = tiles.total();
         if (j >= total) return;
     }
     const int G = gridDim.x;
@@ -114,11 +101,6 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
     // staged row s = r0 + RPP * u of pass m <-> tile row: 32-row slab m of time-wave s / 32
     auto tile_row = [&](int m, int u) { const int sr = r0 + RPP * u; return ((sr >> 5) * MT + m) * 32 + (sr & 31); };
 
-    // tile j -> (utterance, first output row): the utterance index only ever moves forward
-    auto locate = [&](int jj, int& bb) {
-        while (pre[bb + 1] <= jj) ++bb;
-        bb = __builtin_amdgcn_readfirstlane(bb);
-    };
     // the residual stream of a tile, fp32, straight into accumulator layout (quad q of a lane = 4 consecutive channels of row SH::row(lane, q): one
     // 16 B access.  An access of the wave covers 32 rows x 32 contiguous bytes on MfmaShape<32>, 16 rows x 64 on MfmaShape<16>).
     // Buffer loads over the utterance [0, len) x C return zeros for rows outside it (t < 0 wraps to a huge unsigned offset) = the zero padding.
@@ -134,14 +116,12 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
                 SH::set_quad(d[n], q, __builtin_bit_cast(f32x4, v));
             }
     };
-    // (readfirstlane: a length in a VGPR would put every buffer resource below in VGPRs: a waterfall loop around each buffer access)
-    auto len_of = [&](int bb) { return __builtin_amdgcn_readfirstlane(pre[2 * p.B + 1 + bb]); };
 
     int b = 0, len, t0;
     if constexpr (PS) {
-        locate(j, b);
-        len = len_of(b);
-        t0 = (j - pre[b]) * TTo - (p.wav ? PH : 0);
+        tiles.locate(j, b);
+        len = tiles.len_of(b);
+        t0 = tiles.first_row(j, b, TTo) - (p.wav ? PH : 0);
     } else {   // one tile per workgroup: grid (tiles, utterances)
         b = blockIdx.y;
         // (readfirstlane: hipcc loads lens[b] with a vector load — the kernel also stores through other pointers, so no scalar load)
@@ -239,9 +219,9 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
         has_next = PS && jn < total;
         bn = b;
         if (has_next) {
-            locate(jn, bn);
-            lenn = len_of(bn);
-            t0n = (jn - pre[bn]) * TTo - (p.wav ? PH : 0);
+            tiles.locate(jn, bn);
+            lenn = tiles.len_of(bn);
+            t0n = tiles.first_row(jn, bn, TTo) - (p.wav ? PH : 0);
         }
     };
     if (!(PS && p.tile_ctr) || !last_rb) plan_next();
@@ -336,9 +316,9 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
             rb_contract<EL, MT, NT, NKG, PITCH, true, 1, SH>(acc, ring, act, xlane - ((Kr - 1) / 2) * d * PITCH, R.w1[it] + wlane, S, d * PITCH, &cinit);
         rb_preload(ring, R.w2[it] + wlane, kg_stride);   // next conv's first weights fly during barrier + write
         RB_T(2);
-        if constexpr (!TB) __syncthreads();   // every wave is done reading A (TB: xt has its own buffer, last read before the previous barrier)
+        __syncthreads();               // every wave is done reading A
         RB_T(3);
-        write_act(act2, acc);          // xt (16-bit, activated): overwrites A, or goes to its own buffer
+        write_act(act, acc);           // xt (16-bit, activated): overwrites A
         RB_T(4);
         __syncthreads();
         RB_T(5);
@@ -351,13 +331,13 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
                 for (int q = 0; q < 4; ++q) SH::add_quad(xr[m][n], q, bb[n][q / SH::QB]);
         if (it < 2) load_bias(bb, R.b1[it + 1]);
         if constexpr (REAL_STEPS) {
-            if (S) rb2_contract<EL, MT, NT, NKG, PITCH, 4, false>(xr, ring, act2, xlane - ((Kr - 1) / 2) * PITCH, R.w2[it] + wlane, S, PITCH, cinit);
+            if (S) rb2_contract<EL, MT, NT, NKG, PITCH, 4, false>(xr, ring, act, xlane - ((Kr - 1) / 2) * PITCH, R.w2[it] + wlane, S, PITCH, cinit);
         } else
-            rb_contract<EL, MT, NT, NKG, PITCH, false, 1, SH>(xr, ring, act2, xlane - ((Kr - 1) / 2) * PITCH, R.w2[it] + wlane, S, PITCH);
+            rb_contract<EL, MT, NT, NKG, PITCH, false, 1, SH>(xr, ring, act, xlane - ((Kr - 1) / 2) * PITCH, R.w2[it] + wlane, S, PITCH);
         if (it < 2) rb_preload(ring, R.w1[it + 1] + wlane, kg_stride);
-        if (PS && p.tile_ctr && last_rb && it == 2 && tid == 0) pre[3 * p.B + 1] = G + (int)claim;   // the claimed tile, for everyone (read behind the barrier)
+        if (PS && p.tile_ctr && last_rb && it == 2 && tid == 0) tiles.publish_claim(G, claim);   // the claimed tile, for everyone (read behind the barrier)
         RB_T(6);
-        if (!TB || it == 2) __syncthreads();   // every wave is done reading xt (TB: A is rewritten, not xt; the barrier stays in front of the epilogue)
+        __syncthreads();               // every wave is done reading xt
         RB_T(7);
         if (it < 2) {
             write_act(act, xr);
@@ -368,7 +348,7 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
     }
 
     if (PS && p.tile_ctr && last_rb) {
-        jn = __builtin_amdgcn_readfirstlane(pre[3 * p.B + 1]);
+        jn = tiles.claimed();
         plan_next();
     }
     {
@@ -413,8 +393,7 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
     // the utterance zero = conv_post's zero padding) instead of going to HBM; the transposition buffer moves behind it
     constexpr int OP = C * 4;                      // otile row pitch (bytes)
     char* otile = smem;
-    // (TB: both activation buffers are dead in the epilogue; the staging rows follow the output tile inside them)
-    char* estage = wav_now ? smem + ((TB || (size_t)TT * OP > ACT_BYTES) ? (size_t)TT * OP : ACT_BYTES) : stage;
+    char* estage = wav_now ? smem + ((size_t)TT * OP > ACT_BYTES ? (size_t)TT * OP : ACT_BYTES) : stage;
     char* stg = estage + (wt * 32) * EP + (wc * CW) * 4;                 // this wave's block of the staging buffer
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
@@ -444,20 +423,8 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
                 }
                 continue;
             }
-            if (mode == 2) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = o[e] / p.div;
-            }
-            if (!(mode == 2 && p.Sa && p.drop_S)) {   // the stage's consumers read only the bf16 copy: the fp32 sum can stay unwritten
-                // an intermediate sum of a fused launch is re-read by this workgroup's next ResBlock: write-back cached; final results stream out
-                if (p.nrb > 1 && !last_rb) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rs_s, off, 0, 0);
-                else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rs_s, off, 0, VP_ST_AUX);
-            }
-            if (mode == 2 && p.Sa) {
-                typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-                const u32x2 pk = {pack2bf(lrelu(o[0], p.slope), lrelu(o[1], p.slope)), pack2bf(lrelu(o[2], p.slope), lrelu(o[3], p.slope))};
-                __builtin_amdgcn_raw_buffer_store_b64(pk, rs_a, off == (int)0x80000000 ? off : off >> 1, 0, VP_ST_AUX);
-            }
+            // (an intermediate sum of a fused launch is re-read by this workgroup's next ResBlock: stored cached)
+            rb_stage_row(o, rs_s, rs_a, off, mode, p.div, p.slope, p.drop_S != 0, p.Sa != nullptr, p.nrb > 1 && !last_rb);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();                               // slab m + 1 reuses this wave's staging block
@@ -465,69 +432,8 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
         RB_T(14);                                        // (slab: rows read back, + stage sum, stored)
     }
     if constexpr (C == 32) if (wav_now) {   // (the launcher rejects p.wav for other widths)
-        // ---- wav[t] = tanh(b + sum_{tap, c} w[c][tap] * otile[t + tap - 3][c])   (conv_post + tanh, hifigan.py:139-141) in exact fp32:
-        // 8 lanes per output sample (4 channels each, 7 taps), partial sums joined by three xor-shuffles
-        __syncthreads();
-        const int q8 = tid & 7, rr = tid >> 3;                         // channel quad, row within a pass of THREADS / 8 rows
-        f32x4 wq[PK];
-#pragma unroll
-        for (int k = 0; k < PK; ++k) wq[k] = *(const f32x4*)(p.post_w + k * C + q8 * 4);
-        const float pb = p.post_b[0];
-        float* wb = p.wav + brow;
-        // each 8-lane group slides over PR consecutive outputs (PR + PK - 1 row reads instead of PR * PK; PR odd: neighbouring groups start
-        // 128 B apart modulo the 256 B of the LDS banks); every output is still summed tap by tap in the order of the one-output form
-        constexpr int PR = 3;
-        for (int o0 = 0; o0 < TTo; o0 += (THREADS / 8) * PR) {
-            const int ob = o0 + rr * PR;                               // first output of this group: otile rows ob .. ob + PR + PK - 2
-            float a[PR];
-#pragma unroll
-            for (int i = 0; i < PR; ++i) a[i] = 0.f;
-            if (ob < TTo) {
-#pragma unroll
-                for (int j = 0; j < PR + PK - 1; ++j) {
-                    const int row = ob + j < TTo + PK - 1 ? ob + j : TTo + PK - 2;   // (rows past the tile feed discarded outputs only)
-                    const f32x4 v = *(const f32x4*)(otile + (size_t)row * OP + q8 * 16);
-#pragma unroll
-                    for (int i = 0; i < PR; ++i) {
-                        const int k = j - i;
-                        if (k >= 0 && k < PK) {   // explicit operations: the same rounding sequence for every output, whatever its place in a group / tile
-                            const float d = __builtin_fmaf(v[3], wq[k][3], __builtin_fmaf(v[2], wq[k][2], __builtin_fmaf(v[1], wq[k][1], __fmul_rn(v[0], wq[k][0]))));
-                            a[i] = __fadd_rn(a[i], d);
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < PR; ++i) {
-                a[i] += __shfl_xor(a[i], 1, 64);
-                a[i] += __shfl_xor(a[i], 2, 64);
-                a[i] += __shfl_xor(a[i], 4, 64);
-            }
-            // ALWAYS-ON overflow detector (every instantiation, every call): an fp16 operand that overflowed anywhere upstream is +-inf, every
-            // sum it enters is inf / NaN from there on (the fp32 residual stream never recovers), so it arrives HERE as a non-finite
-            // pre-tanh value.  tanh would turn +-inf into a plausible +-1: the sample is poisoned with NaN instead and counted.
-            // tanh(x) = 1 - 2 / (e^{2x} + 1) on the hardware exp2 / rcp, evaluated by every lane (libm's tanhf ran its ~45 instructions for
-            // the one live lane in eight): absolute error <= 3e-7 (1 / 100 of an int16 step), saturates correctly at +-1.
-            float pre[PR], th[PR];
-            int nf = 0;   // non-finite SAMPLES of this group (the same unit as vconv.hip's post_tanh detector: dtts_vocoder_nonfinite counts samples)
-#pragma unroll
-            for (int i = 0; i < PR; ++i) {
-                pre[i] = a[i] + pb;
-                th[i] = __builtin_fmaf(-2.f, __builtin_amdgcn_rcpf(__fadd_rn(__builtin_amdgcn_exp2f(pre[i] * 2.885390081777927f), 1.f)), 1.f);   // (2 log2 e)
-            }
-            if (q8 == 0) {
-#pragma unroll
-                for (int i = 0; i < PR; ++i) {
-                    const int o = ob + i, t = t0 + PH + o;
-                    const bool nonfin = !(__builtin_fabsf(pre[i]) <= 3.0e38f);
-                    if (o < TTo && t < len) {
-                        wb[t] = nonfin ? __builtin_nanf("") : th[i];
-                        nf += nonfin ? 1 : 0;
-                    }
-                }
-                if (nf && p.bad) atomicAdd(p.bad, (unsigned)nf);   // (never on a healthy call)
-            }
-        }
+        __syncthreads();                                               // the fp32 output tile is whole
+        rb_conv_post_tanh<C, THREADS, 3>(otile, p.post_w, p.post_b, p.wav + brow, t0, TTo, len, p.bad, tid);
     }
     }   // (epilogue)
     RB_T(8);                                             // epilogue (+ the fused conv_post)
@@ -564,18 +470,17 @@ __global__ __launch_bounds__(64 * WT * WC, (64 * WT * WC <= 256) ? 2 : 1) void r
 }
 
 // dynamic LDS of an rb_launch_cfg configuration for TT valid rows per tile, WITHOUT the persistent form's tile table
-template <int C, int MT, int WT, bool TB>
+template <int C, int MT, int WT>
 static size_t rb_lds_bytes(int TT, bool wav) {
     constexpr int W = 32 * MT * WT, PITCH = C * 2 + 16, EP = C * 4 + 16;
     constexpr size_t ACT = (size_t)(W + 2 * RB_GUARD) * PITCH;
     if (wav)   // fused conv_post (7 taps): the fp32 output tile may be larger than the activation tile it replaces
-        return TB ? std::max(2 * ACT, (size_t)TT * C * 4 + (size_t)WT * 32 * EP) : std::max((size_t)TT * C * 4, ACT) + (size_t)WT * 32 * EP;
-    return TB ? std::max(2 * ACT, ACT + (size_t)RB_GUARD * PITCH + (size_t)WT * 32 * EP) : ACT + (size_t)WT * 32 * EP;   // TB: the staging rows lie over the xt buffer
+        return std::max((size_t)TT * C * 4, ACT) + (size_t)WT * 32 * EP;
+    return ACT + (size_t)WT * 32 * EP;
 }
-static size_t rb_table_bytes(int B) { return (size_t)(3 * B + 2) * sizeof(int); }   // tile table: prefix sums [B + 1], counts [B], lengths [B]
 
 // hipErrorOutOfMemory: the configuration's LDS (with the tile table of p.B utterances) exceeds 160 KB — the caller picks another one
-template <int C, int MT, int NT, int WT, int WC, int EL, int PS, bool GUARD = false, bool TB = false>
+template <int C, int MT, int NT, int WT, int WC, int EL, int PS, bool GUARD = false>
 static hipError_t rb_launch_cfg(const RBlockParams& p, hipStream_t stream) {
     typedef MfmaShape<rblock_mfma_shape(C)> SH;   // one shape per width, whatever the tile size (rblock.h)
     constexpr int W = 32 * MT * WT;
@@ -586,7 +491,7 @@ static hipError_t rb_launch_cfg(const RBlockParams& p, hipStream_t stream) {
     if (TT < 32) return hipErrorInvalidValue;
     if ((long long)p.T * C * 4 >= (1LL << 31)) return hipErrorInvalidValue;   // 32-bit byte offsets inside an utterance's buffer resource
     if (p.wav && (C != 32 || (p.nrb == 1 && p.mode != 2) || !p.post_w || !p.post_b)) return hipErrorInvalidValue;
-    size_t lds = rb_lds_bytes<C, MT, WT, TB>(TT, p.wav != nullptr);
+    size_t lds = rb_lds_bytes<C, MT, WT>(TT, p.wav != nullptr);
     const int TTo = p.wav ? TT - 6 : TT;
     RBlockParams q = p;
     q.pre_off = (int)lds;
@@ -596,36 +501,19 @@ static hipError_t rb_launch_cfg(const RBlockParams& p, hipStream_t stream) {
     // spilled — and rb_launch_el sends a census launch to the 512-row tile instead)
     constexpr bool HAS_GUARD = !(C == 64 && MT == 5);
     if constexpr (EL == EL_F16 && !GUARD && HAS_GUARD) {
-        if (p.ovf) return rb_launch_cfg<C, MT, NT, WT, WC, EL, PS, true, TB>(p, stream);
+        if (p.ovf) return rb_launch_cfg<C, MT, NT, WT, WC, EL, PS, true>(p, stream);
     }
     if (EL == EL_F16 && !HAS_GUARD && p.ovf) return hipErrorInvalidValue;
-    auto kern = rblock_kernel<C, MT, NT, WT, WC, EL, PS, GUARD, TB, SH>;
-    // per device (hipFuncSetAttribute is per device; a process may hold contexts on several GPUs)
-    static bool configured_dev[64] = {};
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    bool& configured = configured_dev[cur_dev & 63];
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
+    constexpr auto kern = rblock_kernel<C, MT, NT, WT, WC, EL, PS, GUARD, SH>;
+    if (const hipError_t e = rb_allow_full_lds<kern>(); e != hipSuccess) return e;
     constexpr int THREADS = 64 * WT * WC;
     if (!PS) {
         hipLaunchKernelGGL(kern, dim3((p.T + TTo - 1) / TTo, p.B), dim3(THREADS), lds, stream, q);
         return hipGetLastError();
     }
-    // persistent workgroups: as many as are resident at once (LDS / thread limits), never more than there can be tiles
-    static int cus_dev[64] = {};
-    int& cus = cus_dev[cur_dev & 63];
-    if (!cus) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, cur_dev) != hipSuccess) return hipErrorInvalidDevice;
-        cus = prop.multiProcessorCount;
-    }
-    const int per_cu = std::max(1, std::min({(int)(160 * 1024 / lds), 2048 / THREADS, THREADS <= 256 ? 2 : 1}));
-    const long long max_tiles = (long long)p.B * ((p.T + TTo - 1) / TTo);
-    const int grid = (int)std::min<long long>((long long)cus * per_cu, max_tiles);
+    const int cus = rb_device_cus();
+    if (cus <= 0) return hipErrorInvalidDevice;
+    const int grid = rb_resident_grid(cus, lds, THREADS, THREADS <= 256 ? 2 : 1, (long long)p.B * ((p.T + TTo - 1) / TTo));
     if (grid <= 0) return hipSuccess;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), lds, stream, q);
     return hipGetLastError();
@@ -646,7 +534,7 @@ int rblock_stage_tile_rows(int C, int halo) {
 bool rblock_stage_launch_fits(int C, int halo, int B, bool wav) {
     const int TT = rblock_stage_tile_rows(C, halo);
     if (C != 32 && C != 64) return false;
-    const size_t lds = (C == 32 ? rb_lds_bytes<32, 4, 8, false>(TT, wav) : rb_lds_bytes<64, 4, 4, false>(TT, wav)) + rb_table_bytes(B);
+    const size_t lds = (C == 32 ? rb_lds_bytes<32, 4, 8>(TT, wav) : rb_lds_bytes<64, 4, 4>(TT, wav)) + rb_table_bytes(B);
     return TT >= 32 && lds <= 160 * 1024;
 }
 
@@ -679,14 +567,8 @@ static hipError_t rb_launch_el(const RBlockParams& p, int C, hipStream_t stream)
     // 1024-row form is 14 % slower there).
     // small batches (B = 1: one sentence): when the default tiles leave more than half of the CUs without one, the launch takes as long
     // as ONE tile -> half-size tiles (more halo recomputed, but twice the CUs at work)
-    static int cus_dev[64] = {};
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    int& cus = cus_dev[cur_dev & 63];
-    if (!cus) {
-        hipDeviceProp_t prop;
-        cus = hipGetDeviceProperties(&prop, cur_dev) == hipSuccess ? prop.multiProcessorCount : 256;
-    }
+    const int cus = rb_device_cus();
+    if (cus <= 0) return hipErrorInvalidDevice;
     auto few = [&](int W) {   // tiles of W rows (valid: W - 2 rblock_halo, the fused conv_post 6 less): at most half the CUs get one
         const int tt = W - 2 * rblock_halo(p) - (p.wav ? 6 : 0);
         return tt >= 32 && 2 * (long long)p.B * ((p.T + tt - 1) / tt) <= cus;
@@ -697,13 +579,8 @@ static hipError_t rb_launch_el(const RBlockParams& p, int C, hipStream_t stream)
         if (C == 64) return rb_launch_cfg<64, 4, 1, 4, 2, EL, 1>(p, stream);
         return hipErrorInvalidValue;
     }
-    // RB_TRY: a persistent configuration whose LDS cannot hold the tile table of this many utterances (hipErrorOutOfMemory: the fused
-    // conv_post's 1024-row tile above ~940 utterances, the 128-row C = 256 tile above ~1730) falls through to the next one down
-#define RB_TRY(call)                                   \
-    do {                                               \
-        const hipError_t e_ = (call);                  \
-        if (e_ != hipErrorOutOfMemory) return e_;      \
-    } while (0)
+    // RB_TRY: a persistent configuration whose LDS cannot hold the tile table of this many utterances (the fused conv_post's 1024-row tile
+    // above ~940 utterances, the 128-row C = 256 tile above ~1730) falls through to the next one down
     if (C == 32 && p.K >= 7 && !few(1024)) RB_TRY((rb_launch_cfg<32, 4, 1, 8, 1, EL, 1>(p, stream)));
     if (C == 64 && few(512)) return rb_launch_cfg<64, 4, 1, 2, 2, EL, 1>(p, stream);     // 256-row tile, 4 waves
     if (C == 128 && few(256)) return rb_launch_cfg<128, 4, 1, 1, 4, EL, 1>(p, stream);   // 128-row tile, 4 waves
@@ -720,7 +597,6 @@ static hipError_t rb_launch_el(const RBlockParams& p, int C, hipStream_t stream)
     if (C == 128) return rb_launch_cfg<128, 4, 1, 1, 4, EL, 1>(p, stream);     // (ditto) 128-row tile
     if (C == 256) RB_TRY((rb_launch_cfg<256, 4, 1, 1, 8, EL, 1>(p, stream)));  // 128-row tile, 8 waves over channels
     if (C == 256) return rb_launch_cfg<256, 2, 1, 1, 8, EL, 1>(p, stream);     // (ditto) 64-row tile
-#undef RB_TRY
     return hipErrorInvalidValue;
 }
 

@@ -62,7 +62,6 @@ constexpr int RBN_ROWS[3] = {1024, 512, 256};
 __host__ __device__ inline size_t rbn_lds_bytes(int C, int W, int Kp, int halo, int guard, bool wav) {
     return (size_t)6 * (Kp / rbn_taps_per_step(C)) * 1024 + (size_t)(W + 2 * guard) * (C * 2) + (wav ? (size_t)(W - 2 * halo) * C * 4 : 0);
 }
-inline size_t rbn_table_bytes(int B) { return (size_t)(3 * B + 2) * sizeof(int); }   // prefix sums [B + 1], counts [B], lengths [B], the claimed tile
 
 // (C, K, dilations) the kernel runs for EVERY batch size up to DTTS_MAX_VOCODER_BATCH: widths 16 / 8, odd K 3 .. 11, dilations >= 1, and the smallest
 // tile keeps at least 32 output rows (with the fused conv_post's 6 taken off) with its LDS and the largest tile table inside 160 KB.

@@ -17,6 +17,7 @@
 //     the same utterance inside any batch.
 #include "rbn.h"
 #include "rb_common.h"
+#include "rb_tiles.h"
 #include "../../include/dicttts_hip.h"
 
 #include <algorithm>
@@ -37,7 +38,6 @@ __global__ __launch_bounds__(64 * WT) void rbn_kernel(const RBnParams p) {
     static_assert(C == 16 || C == 8, "the tap-folded contraction is written for 16 and 8 channels");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-    typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
     constexpr int THREADS = 64 * WT;
     constexpr int W = 16 * MT * WT;
     constexpr int PITCH = C * 2;                    // bytes of a 16-bit activation row
@@ -56,9 +56,9 @@ __global__ __launch_bounds__(64 * WT) void rbn_kernel(const RBnParams p) {
     uint4* wl = (uint4*)smem;                                          // [conv 6][k-step][lane]
     char* act = smem + (size_t)6 * NS * 1024;                          // 16-bit activation tile, G zero rows on both sides
     char* otile = act + (size_t)(W + 2 * G) * PITCH;                   // fused conv_post: the fp32 stage output [TT][C]
-    int* pre = (int*)(smem + p.pre_off);
+    const RbTiles tiles{(int*)(smem + p.pre_off), p.B};
 
-    // ---- once per workgroup: the packs, the guard bands, the tile table (prefix sums of the utterances' tile counts, rblock.hip)
+    // ---- once per workgroup: the packs, the guard bands, the tile table (rb_tiles.h: RbTiles)
     for (int c = 0; c < 6; ++c) {
         const uint4* src = (c & 1) ? p.w2[c >> 1] : p.w1[c >> 1];
         for (int i = tid; i < NS * 64; i += THREADS) wl[c * NS * 64 + i] = src[i];
@@ -67,28 +67,12 @@ __global__ __launch_bounds__(64 * WT) void rbn_kernel(const RBnParams p) {
         const int r = idx / (PITCH / 16), c = idx % (PITCH / 16);
         *(uint4*)(act + (r < G ? r : W + r) * PITCH + c * 16) = make_uint4(0, 0, 0, 0);
     }
-    for (int i = tid; i < p.B; i += THREADS) {
-        const int l = p.lens ? p.lens[i] : p.T;
-        pre[p.B + 1 + i] = (l + TTo - 1) / TTo;
-        pre[2 * p.B + 1 + i] = l;
-    }
-    __syncthreads();
-    for (int i = tid; i <= p.B; i += THREADS) {
-        int a = 0;
-        for (int u = 0; u < i; ++u) a += pre[p.B + 1 + u];
-        pre[i] = a;
-    }
-    __syncthreads();
-    const int total = pre[p.B];
+    tiles.build(p.lens, p.T, TTo, tid, THREADS);
+    const int total = tiles.total();
     int j = blockIdx.x;
     if (j >= total) return;
     const int Gd = gridDim.x;
 
-    auto locate = [&](int jj, int& bb) {   // tile jj -> its utterance (the index only ever moves forward)
-        while (pre[bb + 1] <= jj) ++bb;
-        bb = __builtin_amdgcn_readfirstlane(bb);
-    };
-    auto len_of = [&](int bb) { return __builtin_amdgcn_readfirstlane(pre[2 * p.B + 1 + bb]); };
     // this lane's 16 bytes of local row `row` of a [len][C] fp32 tensor whose local row 0 is global row base: byte offset into the utterance's
     // buffer resource.  Rows before the utterance wrap to a huge unsigned offset, rows behind it exceed the resource: zeros / dropped.
     auto goff = [&](int base, int row) { return active ? ((base + row) * C + 4 * fq) * 4 : OOB; };
@@ -98,9 +82,9 @@ __global__ __launch_bounds__(64 * WT) void rbn_kernel(const RBnParams p) {
     };
 
     int b = 0;
-    locate(j, b);
-    int len = len_of(b);
-    int t0 = (j - pre[b]) * TTo - (p.wav ? PH : 0);
+    tiles.locate(j, b);
+    int len = tiles.len_of(b);
+    int t0 = tiles.first_row(j, b, TTo) - (p.wav ? PH : 0);
     f32x4 xr[MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m) load_x(xr[m], m, b, t0 - H, len);
@@ -115,7 +99,7 @@ __global__ __launch_bounds__(64 * WT) void rbn_kernel(const RBnParams p) {
         t0 = __builtin_amdgcn_readfirstlane(t0);
         const int base_t = t0 - H;                  // global time of local row 0
         const long long brow = (long long)b * p.T;
-        // the workgroup's next tile: static (j + Gd), or the next unclaimed tile of the launch from a device counter (rblock.hip): one lane issues
+        // the workgroup's next tile: static (j + Gd), or the next unclaimed tile of the launch from a device counter (rb_tiles.h): one lane issues
         // the atomic here, its result is broadcast through LDS behind the last contraction's barrier
         unsigned claim = 0;
         if (p.tile_ctr && tid == 0) claim = atomicAdd(p.tile_ctr, 1u);
@@ -167,7 +151,7 @@ __global__ __launch_bounds__(64 * WT) void rbn_kernel(const RBnParams p) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) xr[m][e] += bias2[e];
             contract(xr, 2 * it + 1, 1);                   // x = x + b2 + W2 * xt, straight into the residual registers
-            if (it == 2 && p.tile_ctr && tid == 0) pre[3 * p.B + 1] = Gd + (int)claim;
+            if (it == 2 && p.tile_ctr && tid == 0) tiles.publish_claim(Gd, claim);
             __syncthreads();                               // every wave is done reading xt
             if (it < 2) {
                 write_act(xr);
@@ -175,13 +159,13 @@ __global__ __launch_bounds__(64 * WT) void rbn_kernel(const RBnParams p) {
             }
         }
 
-        int jn = p.tile_ctr ? __builtin_amdgcn_readfirstlane(pre[3 * p.B + 1]) : j + Gd;
+        int jn = p.tile_ctr ? tiles.claimed() : j + Gd;
         const bool has_next = jn < total;
         int bn = b, lenn = len, t0n = 0;
         if (has_next) {
-            locate(jn, bn);
-            lenn = len_of(bn);
-            t0n = (jn - pre[bn]) * TTo - (p.wav ? PH : 0);
+            tiles.locate(jn, bn);
+            lenn = tiles.len_of(bn);
+            t0n = tiles.first_row(jn, bn, TTo) - (p.wav ? PH : 0);
         }
 
         // ---- epilogue: rows [H, H + TT) of the tile leave straight from the accumulator layout (a wave's access = 16 whole consecutive rows)
@@ -213,19 +197,14 @@ __global__ __launch_bounds__(64 * WT) void rbn_kernel(const RBnParams p) {
                     }
                     continue;
                 }
-                if (p.mode == 2) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = o[e] / p.div;
-                }
-                if (!(p.mode == 2 && p.Sa && p.drop_S)) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rs_s, off, 0, VP_ST_AUX);
-                if (p.mode == 2 && p.Sa) {
-                    const u32x2 pk = {pack2bf(lrelu(o[0], p.slope), lrelu(o[1], p.slope)), pack2bf(lrelu(o[2], p.slope), lrelu(o[3], p.slope))};
-                    __builtin_amdgcn_raw_buffer_store_b64(pk, rs_a, off == OOB ? off : off >> 1, 0, VP_ST_AUX);
-                }
+                rb_stage_row(o, rs_s, rs_a, off, p.mode, p.div, p.slope, p.drop_S != 0, p.Sa != nullptr, false);
             }
         }
         if (p.wav) {
             // ---- wav[t] = tanh(b + sum_{tap, c} w[c][tap] * otile[t + tap - 3][c])  (conv_post + tanh, hifigan.py:139-141) in exact fp32:
+            // rb_tiles.h's rb_conv_post_tanh with one sample per group, kept as a LOCAL copy: called as the shared function (PR = 1) it is bit-identical, but
+            // hipcc then keeps what it derives from the thread index alive through the contractions (1 - 2 VGPRs more, the C = 8 census kernel of the 512-row
+            // tile falls to two waves per SIMD), and with an opaque move of the index in front of the call the V2 forward measured 2 % slower (LABNOTES).
             // C / 4 lanes per sample (4 channels each, 7 taps in order), partial sums joined by xor-shuffles: the same rounding sequence for
             // every sample, whatever its place in a tile
             __syncthreads();
@@ -249,8 +228,8 @@ __global__ __launch_bounds__(64 * WT) void rbn_kernel(const RBnParams p) {
                 }
                 a += __shfl_xor(a, 1, 64);
                 if constexpr (LPO == 4) a += __shfl_xor(a, 2, 64);
-                // ALWAYS-ON overflow detector (rblock.hip): an fp16 operand that overflowed upstream arrives here as a non-finite pre-tanh value:
-                // the sample is poisoned with NaN and counted.  tanh(x) = 1 - 2 / (e^{2x} + 1) on the hardware exp2 / rcp.
+                // the always-on overflow detector and the tanh of rb_tiles.h's rb_conv_post_tanh, operation for operation: a non-finite pre-tanh value is
+                // poisoned with NaN and counted
                 const float prv = a + pb;
                 const float th = __builtin_fmaf(-2.f, __builtin_amdgcn_rcpf(__fadd_rn(__builtin_amdgcn_exp2f(prv * 2.885390081777927f), 1.f)), 1.f);
                 const int t = t0 + PH + o;
@@ -278,21 +257,7 @@ bool rbn_supported(int C, int K, int d0, int d1, int d2) {
     const int dil[3] = {d0, d1, d2};
     const int halo = rblock_halo_of(K, dil), W = RBN_ROWS[2];
     if (W - 2 * halo - 6 < 32) return false;
-    return rbn_lds_bytes(C, W, rbn_padded_taps(C, K), halo, rbn_guard(C, K, dil), true) + rbn_table_bytes(DTTS_MAX_VOCODER_BATCH) <= 160 * 1024;
-}
-
-// compute units of the current device (cached per device), or 0 when the device cannot be queried: the tile rule and the grid use the same count
-static int rbn_cus() {
-    static int cus_dev[64] = {};
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    int& cus = cus_dev[cur_dev & 63];
-    if (!cus) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, cur_dev) != hipSuccess) return 0;
-        cus = prop.multiProcessorCount;
-    }
-    return cus;
+    return rbn_lds_bytes(C, W, rbn_padded_taps(C, K), halo, rbn_guard(C, K, dil), true) + rb_table_bytes(DTTS_MAX_VOCODER_BATCH) <= 160 * 1024;
 }
 
 // hipErrorOutOfMemory: the tile does not fit (its LDS with the tile table of p.B utterances exceeds 160 KB, or fewer than 32 rows are left): the caller
@@ -305,31 +270,19 @@ static hipError_t rbn_launch_cfg(const RBnParams& p, hipStream_t stream) {
     size_t lds = rbn_lds_bytes(C, W, p.Kp, p.halo, p.guard, p.wav != nullptr);
     RBnParams q = p;
     q.pre_off = (int)lds;
-    lds += rbn_table_bytes(p.B);
+    lds += rb_table_bytes(p.B);
     if (lds > 160 * 1024) return hipErrorOutOfMemory;
     if constexpr (EL == EL_F16 && !GUARD) {
         if (p.ovf) return rbn_launch_cfg<C, MT, WT, EL, true>(p, stream);
     }
-    auto kern = rbn_kernel<C, MT, WT, EL, GUARD>;
-    static bool configured_dev[64] = {};   // per device: hipFuncSetAttribute is per device
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    bool& configured = configured_dev[cur_dev & 63];
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
-    const int cus = rbn_cus();
+    constexpr auto kern = rbn_kernel<C, MT, WT, EL, GUARD>;
+    if (const hipError_t e = rb_allow_full_lds<kern>(); e != hipSuccess) return e;
+    const int cus = rb_device_cus();
     if (cus <= 0) return hipErrorInvalidDevice;
-    // persistent workgroups: as many as are RESIDENT at once — by LDS, threads and registers (the 1024-row kernels take 175 - 182 VGPRs: one 8-wave
-    // workgroup per CU; the 4-wave ones 2 - 4) — never more than there can be tiles.  A surplus workgroup would start only when another one ends, and
-    // copy the packs and build the tile table for a tile or two.
+    // resident workgroups by registers: the 1024-row kernels take 175 - 182 VGPRs (one 8-wave workgroup per CU), the 4-wave ones 2 - 4 per CU
     int by_regs = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&by_regs, (const void*)kern, THREADS, lds) != hipSuccess || by_regs < 1) by_regs = 1;
-    const int per_cu = std::max(1, std::min({(int)(160 * 1024 / lds), 2048 / THREADS, by_regs}));
-    const long long max_tiles = (long long)p.B * ((p.T + TTo - 1) / TTo);
-    const int grid = (int)std::min<long long>((long long)cus * per_cu, max_tiles);
+    const int grid = rb_resident_grid(cus, lds, THREADS, by_regs, (long long)p.B * ((p.T + TTo - 1) / TTo));
     if (grid <= 0) return hipSuccess;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), lds, stream, q);
     return hipGetLastError();
@@ -339,7 +292,7 @@ static hipError_t rbn_launch_cfg(const RBnParams& p, hipStream_t stream) {
 // takes as long as ONE tile) 512-row tiles, and 256-row tiles while those still do.  A tile that does not fit falls through to the next smaller one.
 template <int C, int EL>
 static hipError_t rbn_launch_el(const RBnParams& p, hipStream_t stream) {
-    const int cus = rbn_cus();
+    const int cus = rb_device_cus();
     if (cus <= 0) return hipErrorInvalidDevice;
     auto few = [&](int W) {
         const int tt = W - 2 * p.halo - (p.wav ? 6 : 0);

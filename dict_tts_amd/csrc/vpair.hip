@@ -10,6 +10,7 @@
 // HBM bytes per row and iteration: ~0.8 KB in + 0.5 KB out.  4 waves over output channels, 3 workgroups per CU.
 #include "vpair.h"
 #include "rb_common.h"
+#include "rb_tiles.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -47,29 +48,18 @@ __global__ __launch_bounds__(256, (C == 128 && TT == 128 && WT == 1) ? 3 : 2) vo
     const int h1 = p.dil * (p.K - 1) / 2, h2 = (p.K - 1) / 2;
     const int TTe = TT - 2 * h2;             // valid output rows per tile
     const int S = p.K * NKG;
-    // ---- persistent workgroups (as in rblock.hip): the valid tiles of the batch, ceil(len_b / TTe) per utterance, are numbered
+    // ---- persistent workgroups (rb_tiles.h: RbTiles): the valid tiles of the batch, ceil(len_b / TTe) per utterance, are numbered
     // through and workgroup w takes tiles w, w + G, ...; the table of the per-utterance tile counts' prefix sums and the lengths
     // live in LDS behind the tile.  A tile's stores drain while the next tile is staged, and no workgroup is launched per tile.
-    int* pre = (int*)(smem + p.pre_off);
+    const RbTiles tiles{(int*)(smem + p.pre_off), p.B};
     int total = 1, b = 0;
     if constexpr (PS) {
-        for (int i = tid0; i < p.B; i += 256) {
-            const int l = p.lens ? p.lens[i] : p.T;
-            pre[p.B + 1 + i] = (l + TTe - 1) / TTe;
-            pre[2 * p.B + 1 + i] = l;
-        }
-        __syncthreads();
-        for (int i = tid0; i <= p.B; i += 256) {
-            int a = 0;
-            for (int u = 0; u < i; ++u) a += pre[p.B + 1 + u];
-            pre[i] = a;
-        }
-        __syncthreads();
-        total = pre[p.B];
+        tiles.build(p.lens, p.T, TTe, tid0, 256);
+        total = tiles.total();
     }
 #pragma unroll 1
     for (int j = PS ? blockIdx.x : 0; j < total;) {
-    // the next tile: static (j + G) or, with p.tile_ctr, the next unclaimed tile of the launch (rblock.hip: dynamic tile claiming) — the
+    // the next tile: static (j + G) or, with p.tile_ctr, the next unclaimed tile of the launch (rb_tiles.h: dynamic claiming) — the
     // atomic is issued here, its result is broadcast through LDS behind the barrier that ends the tile
     unsigned claim = 0;
     if (PS && p.tile_ctr && tid0 == 0) claim = atomicAdd(p.tile_ctr, 1u);
@@ -82,11 +72,9 @@ __global__ __launch_bounds__(256, (C == 128 && TT == 128 && WT == 1) ? 3 : 2) vo
     const int wc = wv / WT, wt = wv % WT;
     int len, t0;
     if constexpr (PS) {
-        while (pre[b + 1] <= j) ++b;             // the utterance index only moves forward
-        b = __builtin_amdgcn_readfirstlane(b);
-        // (readfirstlane: a length in a VGPR would put every buffer resource below in VGPRs: a waterfall loop around each buffer access)
-        len = __builtin_amdgcn_readfirstlane(pre[2 * p.B + 1 + b]);
-        t0 = __builtin_amdgcn_readfirstlane((j - pre[b]) * TTe);
+        tiles.locate(j, b);
+        len = tiles.len_of(b);
+        t0 = __builtin_amdgcn_readfirstlane(tiles.first_row(j, b, TTe));
     } else {   // one tile per workgroup: grid (tiles, utterances)
         b = blockIdx.y;
         len = __builtin_amdgcn_readfirstlane(p.lens ? p.lens[b] : p.T);
@@ -307,9 +295,9 @@ __global__ __launch_bounds__(256, (C == 128 && TT == 128 && WT == 1) ? 3 : 2) vo
         }
     }
     if constexpr (!PS) break;
-    if (p.tile_ctr && tid0 == 0) pre[3 * p.B + 1] = (int)gridDim.x + (int)claim;
+    if (p.tile_ctr && tid0 == 0) tiles.publish_claim((int)gridDim.x, claim);
     __syncthreads();   // the epilogue's staging rows alias the tile the next iteration stages into
-    j = p.tile_ctr ? __builtin_amdgcn_readfirstlane(pre[3 * p.B + 1]) : j_static;
+    j = p.tile_ctr ? tiles.claimed() : j_static;
     }   // (tiles of this workgroup)
 }
 
@@ -344,71 +332,44 @@ static hipError_t vpair_launch_tt(const VPairParams& p, hipStream_t stream) {
     if (ep > lds) lds = ep;
     VPairParams q = p;
     q.tile_rows = (int)rows;
-    q.pre_off = (int)lds;                          // tile table: prefix sums [B + 1], counts [B], lengths [B]
+    q.pre_off = (int)lds;                          // the tile table (rb_tiles.h) lies behind the tile
     constexpr bool PS = !(CC == 128 && TT == 128 && WT == 1);
-    if (PS) lds += (size_t)(3 * p.B + 2) * sizeof(int);
+    if (PS) lds += rb_table_bytes(p.B);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    auto kern = vpair_kernel<CC, TT, EL, GUARD, WT, X16>;
-    // per device (hipFuncSetAttribute is per device; a process may hold contexts on several GPUs)
-    static bool configured_dev[64] = {};
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    bool& configured = configured_dev[cur_dev & 63];
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
+    constexpr auto kern = vpair_kernel<CC, TT, EL, GUARD, WT, X16>;
+    if (const hipError_t e = rb_allow_full_lds<kern>(); e != hipSuccess) return e;
     if (!PS) {
         hipLaunchKernelGGL(kern, dim3((p.T + TTe - 1) / TTe, p.B), dim3(256), lds, stream, q);
         return hipGetLastError();
     }
-    // persistent workgroups: as many as are resident at once (LDS, the kernel's register bound), never more than there can be tiles
-    static int cus_dev[64] = {};
-    int& cus = cus_dev[cur_dev & 63];
-    if (!cus) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, cur_dev) != hipSuccess) return hipErrorInvalidDevice;
-        cus = prop.multiProcessorCount;
-    }
-    const int per_cu = std::max(1, std::min((int)(160 * 1024 / lds), (CC == 128 && TT == 128 && WT == 1) ? 3 : 2));
-    const long long max_tiles = (long long)p.B * ((p.T + TTe - 1) / TTe);
-    const int grid = (int)std::min<long long>((long long)cus * per_cu, max_tiles);
+    const int cus = rb_device_cus();
+    if (cus <= 0) return hipErrorInvalidDevice;
+    // (by registers: the kernel's launch bound, two workgroups per CU for every persistent instantiation)
+    const int grid = rb_resident_grid(cus, lds, 256, 2, (long long)p.B * ((p.T + TTe - 1) / TTe));
     if (grid <= 0) return hipSuccess;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, q);
     return hipGetLastError();
-}
-
-// CUs of the current device (cached per device)
-static int vpair_cus() {
-    static int cus_dev[64] = {};
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    int& cus = cus_dev[cur_dev & 63];
-    if (!cus) {
-        hipDeviceProp_t prop;
-        cus = hipGetDeviceProperties(&prop, cur_dev) == hipSuccess ? prop.multiProcessorCount : 256;
-    }
-    return cus;
 }
 
 template <int EL>
 static hipError_t vpair_launch_el(const VPairParams& p, int C, hipStream_t stream) {
     // small batches (B = 1: one sentence): the default tiles would leave most CUs without one and the launch takes as long as ONE tile
     // -> half-size tiles (more halo rows recomputed, twice the weight stream per row, but twice the CUs at work)
+    const int cus = rb_device_cus();
+    if (cus <= 0) return hipErrorInvalidDevice;
     auto tiles_of = [&](int tt) { return (long long)p.B * ((p.T + (tt - (p.K - 1)) - 1) / (tt - (p.K - 1))); };
     if (C == 256) {
-        if (2 * tiles_of(128) <= vpair_cus()) return vpair_launch_tt<256, 64, EL>(p, stream);
+        if (2 * tiles_of(128) <= cus) return vpair_launch_tt<256, 64, EL>(p, stream);
         // 128-row tiles, or 96-row ones where only those leave room for TWO workgroups per CU (one workgroup = one wave per SIMD exposes
         // every latency of the memory phases: k = 7 with dilation 5, k = 11 with dilation 3)
-        auto lds_of = [&](int tt) { return ((size_t)tt + (size_t)p.dil * (p.K - 1) + std::max(p.dil + 1, 4)) * (256 * 2 + 16) + (size_t)(3 * p.B + 2) * sizeof(int); };
+        auto lds_of = [&](int tt) { return ((size_t)tt + (size_t)p.dil * (p.K - 1) + std::max(p.dil + 1, 4)) * (256 * 2 + 16) + rb_table_bytes(p.B); };
         if (2 * lds_of(128) > 160 * 1024 && 2 * lds_of(96) <= 160 * 1024) return vpair_launch_tt<256, 96, EL>(p, stream);
         return vpair_launch_tt<256, 128, EL>(p, stream);
     }
     // 256-row tiles while two workgroups still fit a CU's 160 KB of LDS (all but k = 11 with dilation 5)
     const size_t rows256 = (size_t)256 + (size_t)p.dil * (p.K - 1) + std::max(p.dil + 1, 8);
-    const bool big = (rows256 * (128 * 2 + 16) + (size_t)(3 * p.B + 2) * sizeof(int)) * 2 <= 160 * 1024;
-    if (2 * tiles_of(256) <= vpair_cus()) return vpair_launch_tt<128, 128, EL>(p, stream);
+    const bool big = (rows256 * (128 * 2 + 16) + rb_table_bytes(p.B)) * 2 <= 160 * 1024;
+    if (2 * tiles_of(256) <= cus) return vpair_launch_tt<128, 128, EL>(p, stream);
     if (big) return vpair_launch_tt<128, 256, EL>(p, stream);
     // k = 11 with dilation 5: 192-row tiles (two workgroups per CU, persistent) instead of 128-row ones (three, one tile each)
     return vpair_launch_tt<128, 192, EL>(p, stream);

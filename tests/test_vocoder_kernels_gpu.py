@@ -81,7 +81,7 @@ def _cdiv(a, b):
 
 
 def _rb_lds(C, W, WT, TT, wav):
-    """rblock.hip rb_lds_bytes (TB = false): dynamic LDS of a configuration without the tile table"""
+    """rblock.hip rb_lds_bytes: dynamic LDS of a configuration without the tile table"""
     act = (W + 2 * 40) * (C * 2 + 16)
     stage = WT * 32 * (C * 4 + 16)
     return (max(TT * C * 4, act) if wav else act) + stage
