@@ -232,8 +232,13 @@ bool pack_transposed(dtts_ctx* h, Need& need, PackedConv& L, int engine, const s
     const int C_in = (int)w->shape[0], C_out = (int)w->shape[1], k = (int)w->shape[2];
     std::vector<float> b0 = bias_of(need, base);
     if (b0.empty()) return false;
-    if (k > 2 * u || p >= u) {
-        fail(h, DTTS_E_INVAL, "%s: unsupported transposed conv k=%d stride=%d pad=%d", base.c_str(), k, u, p);
+    // Accepted: stride <= k <= 2 * stride with k - stride even and pad = (k - stride) / 2 — exactly T * stride output rows (what stage_geom,
+    // scale_lens and the hop assume) and at most the three taps {-1, 0, +1}.  Refused in EVERY precision (the shape is wrong, not the arithmetic):
+    // an odd k - stride (ConvTranspose1d then yields T * stride + 1 rows: the polyphase form would drop each stage's last row) and k < stride
+    // ((k - stride) / 2 truncates toward zero in C; the reference's padding would be negative, which PyTorch refuses).
+    if (u < 1 || k < u || k > 2 * u || (k - u) % 2 || 2 * p != k - u) {
+        fail(h, DTTS_E_INVAL, "%s: unsupported transposed conv k=%d stride=%d pad=%d (accepted: stride <= k <= 2 * stride, k - stride even, pad = (k - stride) / 2)",
+             base.c_str(), k, u, p);
         return false;
     }
     const bool single = (k == u && p == 0);

@@ -12,9 +12,12 @@ namespace {
 //   worst case (a PROOF when it stays below 65504):  u_out[co] = |b[co]| + sum_ci u_in[ci] * sum_k |w[co][ci][k]|   (transposed convolutions:
 //     the largest output phase), leaky_relu does not grow a bound, the residual adds, the stage output is the mean of its ResBlocks;
 //   RMS estimate (NOT a proof: independent, zero-mean terms):  m_out[co] = b^2 + sum_ci m_in[ci] * sum_k w^2, leaky_relu halves it.
-// Every (operand, channel) bound is affine in M (M^2 for the second moments): a_q + b_q * M with a_q = the value at M = 0 and b_q = value(1) -
-// value(0), both >= 0.  The PEAK over channels is a maximum of affine functions — convex, so a secant through the peaks at M = 0 and 1
-// would UNDERestimate it beyond M = 1 (a bias-dominated channel sets both peaks while another channel's gain term overtakes it at
+// Every (operand, channel) bound is a_q + b_q * M (M^2 for the second moments), both >= 0.  The two parts are propagated SEPARATELY — pass 0: the
+// biases with M = 0 (a_q), pass 1: the weights alone, no bias, with M = 1 (b_q) — because the transposed convolutions' maximum over the output
+// phases is a maximum of affine functions too: a_q = max_ph a_ph and b_q = max_ph b_ph bound every phase at every M, whereas value(1) - value(0)
+// of the phase maxima underestimated the slope whenever another phase leads at M = 1 than at M = 6 (found by tests/test_upsampler_forms_gpu.py:
+// 4e-5 .. 2e-4 below the directly evaluated peak at M = 6 for k < 2u, where the phases have unequal numbers of taps).
+// The PEAK over channels is a maximum of affine functions — convex, so a secant through the peaks at M = 0 and 1 would UNDERestimate it beyond M = 1 (a bias-dominated channel sets both peaks while another channel's gain term overtakes it at
 // M = 6: ADVICE r5).  Reported instead: max_q a_q + M * max_q b_q >= max_q (a_q + b_q M) for every M >= 0 — looser, but a bound.
 // For real checkpoints the worst case is astronomically loose (it compounds sum|w| ~ 10-40 per convolution over 6 convolutions per
 // ResBlock): it proves small-gain generators only.  Everything else runs fp16 under the always-on detector (conv_post epilogue).
@@ -22,9 +25,9 @@ bool vocoder_fp16_analysis(dtts_ctx* h, Need& need) {
     const dtts_config& c = h->cfg;
     const std::string v = "vocoder.";
     const int nk = c.n_resblock_kernels;
-    std::vector<double> pt_wc[2], pt_m2[2];   // [pass][operand point x channel, in traversal order]: pass 0 = M = 0 (the bias part), pass 1 = M = 1
+    std::vector<double> pt_wc[2], pt_m2[2];   // [pass][operand point x channel, in traversal order]: pass 0 = the bias part (M = 0), pass 1 = the slope (no bias, M = 1)
     for (int pass = 0; pass < 2; ++pass) {
-        const double M = pass;
+        const double M = pass, bs = pass == 0 ? 1.0 : 0.0;   // bs: the biases count in pass 0 only
         auto conv = [&](const std::string& base, const std::vector<double>& uin, const std::vector<double>& min, std::vector<double>& uout,
                         std::vector<double>& mout) -> bool {   // Conv1d weight [co][ci][k]
             const HostTensor* w = folded_weight(h, need, base);
@@ -35,7 +38,7 @@ bool vocoder_fp16_analysis(dtts_ctx* h, Need& need) {
             uout.assign(co_n, 0.0);
             mout.assign(co_n, 0.0);
             for (int co = 0; co < co_n; ++co) {
-                double su = std::fabs((double)b[co]), sm = (double)b[co] * b[co];
+                double su = bs * std::fabs((double)b[co]), sm = bs * (double)b[co] * b[co];
                 for (int ci = 0; ci < ci_n; ++ci) {
                     double a1 = 0, a2 = 0;
                     const float* pw = &w->f[((size_t)co * ci_n + ci) * k_n];
@@ -64,7 +67,7 @@ bool vocoder_fp16_analysis(dtts_ctx* h, Need& need) {
             std::vector<double> ux(co_n, 0.0), mx(co_n, 0.0);
             for (int co = 0; co < co_n; ++co)
                 for (int ph = 0; ph < r; ++ph) {   // output phase ph collects the taps k == ph + pad (mod r)
-                    double su = std::fabs((double)b[co]), sm = (double)b[co] * b[co];
+                    double su = bs * std::fabs((double)b[co]), sm = bs * (double)b[co] * b[co];
                     for (int ci = 0; ci < ci_n; ++ci) {
                         const float* pw = &w->f[((size_t)ci * co_n + co) * k_n];
                         double a1 = 0, a2 = 0;
@@ -120,9 +123,9 @@ bool vocoder_fp16_analysis(dtts_ctx* h, Need& need) {
     double a_wc = 0, b_wc = 0, a_m2 = 0, b_m2 = 0;   // max_q a_q, max_q b_q (possibly different channels: that is the point)
     for (size_t q = 0; q < pt_wc[0].size(); ++q) {
         a_wc = std::max(a_wc, pt_wc[0][q]);
-        b_wc = std::max(b_wc, pt_wc[1][q] - pt_wc[0][q]);
+        b_wc = std::max(b_wc, pt_wc[1][q]);
         a_m2 = std::max(a_m2, pt_m2[0][q]);
-        b_m2 = std::max(b_m2, pt_m2[1][q] - pt_m2[0][q]);
+        b_m2 = std::max(b_m2, pt_m2[1][q]);
     }
     h->wc_const = a_wc;
     h->wc_lin = b_wc;
