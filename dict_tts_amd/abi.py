@@ -16,9 +16,11 @@ VOC_BF16, VOC_BF16X3, VOC_F16 = 0, 1, 2
 VOC_PRECISIONS = {"f16": VOC_F16, "bf16": VOC_BF16, "bf16x3": VOC_BF16X3}
 PART_ACOUSTIC, PART_VOCODER, PART_FFT = 1, 2, 4
 PART_MELSPEC = 8    # the log-mel front end: "melspec.mel_basis" + "melspec.window"; rebuilt by every finalize that names it
+PART_STFT = 16      # the multi-resolution STFT distance: "stft.<i>.window" [n_fft], up to four; rebuilt by every finalize that names it
 OUT_PRON_ATTN, OUT_DUR, OUT_MEL2WORD, OUT_DICT_ATTN, OUT_WORD_ENCODER_OUT, OUT_X_MASK, OUT_CONTEXT, OUT_MEL_LENS = range(1, 9)
 OUT_POSTERIOR = 9   # not a copy: the posterior pass, dst = a PosteriorArgs block (include/dicttts_hip.h)
 OUT_MELSPEC = 10     # not a copy, needs no encode: wav -> log-mel, dst = a MelspecArgs block
+OUT_STFT_DISTANCE = 11   # not a copy, needs no encode: a pair of waveform batches -> the sums behind sc / mag, dst = a StftArgs block
 SPK_EMBED, SPK_ID = 1, 2   # dtts_text2mel_speakers kinds: fp32 [B,256] (use_spk_embed) / int64 [B] (use_spk_id)
 TIMER_VOC_CONV, TIMER_S2PA = 1, 2
 TIMER_STAGE_ENCODER, TIMER_STAGE_DICT_ENCODER, TIMER_STAGE_FVAE, TIMER_STAGE_HIFIGAN = 3, 4, 5, 6   # the reference's profile_infer names
@@ -42,6 +44,13 @@ class MelspecArgs(C.Structure):
     """dtts_melspec_args (include/dicttts_hip.h): the argument block of dtts_text2mel_fetch(DTTS_OUT_MELSPEC)"""
     _fields_ = [("size", C.c_int32), ("hop", C.c_int32), ("B", C.c_int32), ("wav_ld", C.c_int32), ("mel_cap", C.c_int32), ("eps", C.c_float),
                 ("wav_dev", C.c_void_p), ("wav_lens_dev", C.c_void_p), ("mel_dev", C.c_void_p), ("mel_lens_dev", C.c_void_p), ("lin_dev", C.c_void_p)]
+
+
+class StftArgs(C.Structure):
+    """dtts_stft_args (include/dicttts_hip.h): the argument block of dtts_text2mel_fetch(DTTS_OUT_STFT_DISTANCE)"""
+    _fields_ = [("size", C.c_int32), ("n_res", C.c_int32), ("hop", C.c_int32 * 4), ("B", C.c_int32), ("wav_ld", C.c_int32), ("mag_cap", C.c_int32),
+                ("reserved", C.c_int32), ("x_dev", C.c_void_p), ("y_dev", C.c_void_p), ("lens_dev", C.c_void_p), ("sums_dev", C.c_void_p),
+                ("count_dev", C.c_void_p), ("mag_dev", C.c_void_p)]
 
 
 class DttsConfig(C.Structure):
@@ -226,6 +235,17 @@ class Context:
         lin f32 like mel or None: the mel values before the floor and the logarithm"""
         a = MelspecArgs(C.sizeof(MelspecArgs), int(hop), int(B), int(wav_ld), int(mel_cap), float(eps), wav, wav_lens or None, mel, mel_lens or None, lin or None)
         self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_MELSPEC, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_MELSPEC)")
+
+    def stft_distance(self, x, y, lens, B, wav_ld, hops, sums, count, stream, mag=None, mag_cap=0):
+        """the sums behind the multi-resolution STFT figures of B waveform pairs (dtts_text2mel_fetch(DTTS_OUT_STFT_DISTANCE); needs PART_STFT
+        finalised, no encode): device pointers x, y f32 [B, wav_ld] (y the recording), lens i32 [B] or None, sums f64 [n_res, B, 3] out,
+        count i64 [n_res, B] out, mag f32 or None (the clamped magnitudes, resolution after resolution [2, B, mag_cap, n_fft_i / 2 + 1]);
+        hops: one hop per resolution, n_res = len(hops)"""
+        hops = [int(v) for v in hops]
+        if not 1 <= len(hops) <= 4:
+            raise DttsError(f"stft_distance: {len(hops)} resolutions (supported: 1 .. 4)")
+        a = StftArgs(C.sizeof(StftArgs), len(hops), (C.c_int32 * 4)(*hops), int(B), int(wav_ld), int(mag_cap), 0, x, y, lens or None, sums, count, mag or None)
+        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_STFT_DISTANCE, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_STFT_DISTANCE)")
 
     def fetch(self, what, dst, stream):
         self._chk(self.lib.dtts_text2mel_fetch(self.h, what, dst, stream), "dtts_text2mel_fetch")

@@ -27,6 +27,7 @@
 #include "rbn.h"
 #include "flowstack.h"
 #include "melspec.h"
+#include "stftdist.h"
 
 // dtts_config.tune_flags: the bits the library honours are listed at TUNE_RELEASE_MASK (context.hip)
 #define DTTS_TUNE(h, bit) (((h)->tune & (bit)) != 0)
@@ -221,6 +222,15 @@ struct dtts_ctx {
     int ms_n_fft = 0, ms_n_mels = 0, ms_win = 0, ms_sg_lo = 0, ms_sg_hi = 0;
     float *ms_basis = nullptr, *ms_melpack = nullptr;   // windowed DFT basis and mel basis in fragment order
     int ms_skew_hop = 0, ms_skew = 8;                   // the slab skew chosen for the hop of the last call
+    // ---- multi-resolution STFT distance (dtts_text2mel_fetch(DTTS_OUT_STFT_DISTANCE); stftdist.hip): the plans of the last
+    // dtts_finalize_weights(DTTS_PART_STFT), one per "stft.<i>.window", and the workspace of the per-tile sums
+    struct StftPlan {
+        int n_fft = 0, sg_lo = 0, sg_hi = 0;
+        float* basis = nullptr;                         // windowed DFT basis in fragment order (melspec_pack_basis)
+        int layout_hop = 0, ps = 31, tt = 1, ybase = 0; // the LDS layout chosen for the hop of the last call (stft_layout)
+    };
+    std::vector<StftPlan> stft_plans;
+    dtts::Arena a_stft;
 };
 
 namespace dtts {
@@ -320,5 +330,7 @@ int build_vocoder(dtts_ctx* h);
 int build_fft(dtts_ctx* h);
 int build_melspec(dtts_ctx* h);   // melspec.hip
 int melspec_forward(dtts_ctx* h, const dtts_melspec_args* a, hipStream_t stream);
+int build_stft(dtts_ctx* h);      // stftdist.hip
+int stft_forward(dtts_ctx* h, const dtts_stft_args* a, hipStream_t stream);
 
 } // namespace dtts

@@ -149,6 +149,7 @@ class HifiGAN:
         ctx.finalize(abi.PART_VOCODER)
         self.ctx, self.precision = ctx, precision
         self._seen_bad = 0   # (a new context counts from zero)
+        self._stft = None    # (and has no STFT plans yet: stft_distance loads them again)
 
     # -- reference API -------------------------------------------------------------------------------------
     def spec2wav(self, mel, **kwargs):
@@ -206,6 +207,24 @@ class HifiGAN:
         valid = (torch.arange(T, device=mels.device)[None, :] < lens[:, None]).to(torch.float32)
         diff = (back[:, :T] - mels).abs().mean(dim=2) * valid
         return diff.sum(dim=1) / lens.clamp(min=1).to(torch.float32)
+
+    def stft_distance(self, mels, wavs, lens=None):
+        """spec2wav(mel) against the recording without leaving the device: the multi-resolution STFT figures of the reference's vocoder
+        validation (tasks/vocoder/hifigan.py:62-76; dict_tts_amd/stftloss.py).  mels [B, T, n_mels] float32 cuda tensor, wavs [B, T * hop]
+        float32 cuda tensor (the recordings: y, the normaliser), lens [B] valid frames or None -> the dict of
+        ``stftloss.MultiResolutionSTFT.__call__`` (sc, mag [B]; sc_res, mag_res [n_res, B]; sc_batch, mag_batch), float64 cuda tensors.
+        The plans live in the vocoder's context."""
+        from . import stftloss
+        mr = getattr(self, "_stft", None)
+        if mr is None:
+            mr = self._stft = stftloss.MultiResolutionSTFT(ctx=self.ctx)
+        B, T, _ = mels.shape
+        if tuple(wavs.shape) != (B, T * self.hop):
+            raise abi.DttsError(f"stft_distance: wavs of shape {tuple(wavs.shape)}, the mels give {(B, T * self.hop)}")
+        if lens is not None:
+            lens = lens.to(device=mels.device, dtype=torch.int32)
+        wav = self.forward_batch(mels, lens)
+        return mr(wav, wavs, None if lens is None else lens * self.hop)
 
     def overflowed(self):
         """True when a forward since the last call of this method (or construction) delivered non-finite pre-tanh samples, i.e. an fp16

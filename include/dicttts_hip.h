@@ -167,6 +167,12 @@ DTTS_API int dtts_load_weight(dtts_handle h, const char* name, const void* host_
  * value.  Unlike the other parts this one is rebuilt by EVERY call that names it, from the tensors loaded last: finalising again with
  * other tensors replaces the plan (the old packs stay allocated until dtts_destroy: a launch in flight may still read them). */
 #define DTTS_PART_MELSPEC 8
+/* The multi-resolution STFT distance (DTTS_OUT_STFT_DISTANCE below): up to four plans, one per "stft.<i>.window" [n_fft], i = 0, 1, .. without a
+ * gap.  Each window arrives as torch.stft applies it: the win_length samples (the reference: torch.hann_window(win_length), periodic) zero
+ * padded to n_fft with (n_fft - win_length) / 2 zeros on the left.  n_fft is the tensor's length (512 / 1024 / 2048, else DTTS_E_INVAL naming
+ * it); the samples outside the window's non-zero support are left out of the contraction.  Rebuilt by EVERY call that names it, like
+ * DTTS_PART_MELSPEC.  DTTS_E_NOENT without "stft.0.window". */
+#define DTTS_PART_STFT 16
 /* Fold, repack into MFMA fragment order and upload.  Fails with DTTS_E_NOENT naming the first missing tensor. */
 DTTS_API int dtts_finalize_weights(dtts_handle h, int parts);
 
@@ -325,6 +331,38 @@ typedef struct dtts_melspec_args {
     int32_t* mel_lens_dev;        /* or NULL */
     float* lin_dev;               /* or NULL: f32 [B][mel_cap][n_mels], the mel values BEFORE max(eps, .) and the logarithm (accuracy tests) */
 } dtts_melspec_args;
+/*
+ * DTTS_OUT_STFT_DISTANCE: not a copy, needs NO encode — the sums behind the reference's multi-resolution STFT figures `sc` / `mag`
+ * (modules/hifigan/stft_loss.py as tasks/vocoder/hifigan.py:62-76 reports them; MultiResolutionSTFTLoss.forward(x, y): y is the recording and
+ * the normaliser) for a batch of waveform PAIRS, one launch per resolution plus one reduction launch on `stream`, no host synchronisation, no
+ * atomics: dst = (dtts_stft_args*), args->size = sizeof(*args).  Resolution i < n_res uses plan i of dtts_finalize_weights(DTTS_PART_STFT) at
+ * hop[i].  Per utterance b of len_b = lens_dev[b] samples (clamped to [0, wav_ld]; NULL = wav_ld), as torch.stft(center=True,
+ * pad_mode='reflect') of x[b, :len_b] and y[b, :len_b] alone: n_fft / 2 mirrored samples on both sides (the edge sample not repeated),
+ * T_b = 1 + len_b / hop frames, n_fft / 2 + 1 bins, m = sqrt(max(re^2 + im^2, 1e-7)).
+ *   sums_dev  f64 [n_res][B][3]: sum (m_y - m_x)^2, sum m_y^2, sum |log m_y - log m_x| over the utterance's T_b (n_fft / 2 + 1) values, so that
+ *             sc = sqrt(sums[0] / sums[1]) and mag = sums[2] / count (pooled over a batch: add the sums and the counts first);
+ *   count_dev i64 [n_res][B]: T_b (n_fft / 2 + 1); 0, with zero sums, where len_b <= n_fft / 2 (a length torch.stft refuses);
+ *   mag_dev   f32 or NULL: the clamped magnitudes, resolution after resolution, each [2 (x, y)][B][mag_cap][n_fft_i / 2 + 1]; rows >= T_b
+ *             are left untouched (tests and diagnosis; mag_cap >= 1 + wav_ld / hop[i] for every i).
+ * The contraction is DTTS_OUT_MELSPEC's (exact fp32 products, fp32 over eight samples, fp64 across those); the sums are fp32 over 32 bins of
+ * a frame, fp64 beyond, in a fixed order: the same inputs give the same bits, and an utterance's three sums are bit-identical alone and
+ * inside any batch.  DTTS_E_STATE without a finalised plan; DTTS_E_INVAL (naming the value) for a wrong size, n_res outside 1 .. the number
+ * of plans, a hop outside 1 .. n_fft, B <= 0, a mag_cap that is too small, or a NULL x / y / sums / count pointer.
+ */
+#define DTTS_OUT_STFT_DISTANCE 11
+typedef struct dtts_stft_args {
+    int32_t size;                 /* sizeof(dtts_stft_args) */
+    int32_t n_res;                /* resolutions to run: plans 0 .. n_res - 1 */
+    int32_t hop[4];               /* hop of each: any integer in 1 .. n_fft */
+    int32_t B, wav_ld, mag_cap;   /* mag_cap: rows per utterance of mag_dev (ignored when mag_dev is NULL) */
+    int32_t reserved;             /* 0 */
+    const float* x_dev;           /* f32 [B][wav_ld]: the generated waveforms */
+    const float* y_dev;           /* f32 [B][wav_ld]: the recordings (the normaliser of sc) */
+    const int32_t* lens_dev;      /* or NULL */
+    double* sums_dev;
+    int64_t* count_dev;
+    float* mag_dev;               /* or NULL */
+} dtts_stft_args;
 DTTS_API int dtts_text2mel_fetch(dtts_handle h, int what, void* dst_dev, dtts_stream stream);
 
 /*

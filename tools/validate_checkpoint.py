@@ -23,6 +23,9 @@ It prints, in this order:
      the first --gate mels;
   4b. the mel round trip mel(spec2wav(mel)) against mel per utterance (HifiGAN.mel_roundtrip: mean |delta log10-mel|), the figure the
      reference's vocoder validation reports.  It means something for a trained checkpoint only: a synthetic generator does not invert mels;
+  4c. the multi-resolution STFT distance sc / mag (HifiGAN.stft_distance, the other pair of figures of that validation, every bin of three
+     resolutions instead of 80 pooled ones) of the fp16 waveform against the bf16x3 waveform of the same mels — the ERROR of the fp16 mode on
+     this checkpoint, measured on the device without an oracle — and, with --wavs, of the vocoder's output against the recordings;
   5. the verdict: the mode HifiGAN(precision=None) runs this checkpoint in, and whether that mode met the gate.
 Exit code 0 = the mode AUTO chose meets the gate with a clean guard; 1 otherwise.
 """
@@ -124,14 +127,14 @@ def main():
     else:
         ap.error("give a checkpoint directory or --synthetic")
     full_cfg = {**vocoder.HIFIGAN_DEFAULTS, **(cfg or {})}
-    wav_mels = []
+    wav_mels, recordings = [], []
     if a.wavs:
         import glob
         files = sorted(glob.glob(os.path.join(a.wavs, "*.wav")))
         if not files:
             sys.exit(f"--wavs {a.wavs}: no *.wav files")
-        wav_mels = [vocoder.HifiGAN.wav2spec(fn)[1] for fn in files]
-    mels = wav_mels or [np.load(f).astype(np.float32) for f in a.mel_npy] or [synth.random_mel(100 + i, a.frames, f"val{i}") for i in range(a.mels)]
+        recordings, wav_mels = zip(*[vocoder.HifiGAN.wav2spec(fn) for fn in files])   # (the recording padded to whole hops, its mel)
+    mels = list(wav_mels) or [np.load(f).astype(np.float32) for f in a.mel_npy] or [synth.random_mel(100 + i, a.frames, f"val{i}") for i in range(a.mels)]
     print(f"checkpoint: {src}\n  upsample_rates {full_cfg['upsample_rates']}  initial channels {full_cfg['upsample_initial_channel']}  "
           f"resblock kernels {full_cfg['resblock_kernel_sizes']}\n  {len(mels)} mels, {sum(m.shape[0] for m in mels)} frames, "
           f"|mel| max {max(float(np.abs(m).max()) for m in mels):.2f}")
@@ -208,6 +211,24 @@ def main():
     print("\n4b. mel round trip mel(spec2wav(mel)) vs mel, mean |delta log10-mel| per utterance" + (" (synthetic weights: the value means nothing)" if a.synthetic else ""))
     for i, m in enumerate(mels[:max(a.gate, 1)]):
         print(f"   mel {i} ({m.shape[0]} frames): {float(auto.mel_roundtrip(T_(m[None]).cuda())[0]):.4f}")
+
+    print("\n4c. multi-resolution STFT distance (sc = ||m_y - m_x|| / ||m_y||, mag = mean |log m_y - log m_x|; resolutions 1024/120/600, 2048/240/1200, 512/50/240)")
+    exact = modes[-1][1]
+    fmt = lambda r: f"sc {float(r['sc'][0]):.4e}  mag {float(r['mag'][0]):.4e}"
+    for i, m in enumerate(mels[:max(a.gate, 1)]):
+        mel = T_(m[None]).cuda()
+        if mel.shape[1] * auto.hop <= 1024:
+            print(f"   mel {i} ({m.shape[0]} frames): too short for the 2048-sample resolution")
+            continue
+        line = f"   mel {i} ({m.shape[0]} frames):"
+        if probe is not None:
+            line += f"  fp16 against bf16x3: {fmt(probe.stft_distance(mel, exact.forward_batch(mel)))}"
+        if recordings:
+            n = m.shape[0] * auto.hop   # wav2spec gives one frame more than whole hops of samples
+            rec = np.zeros(n, np.float32)
+            rec[:min(n, len(recordings[i]))] = recordings[i][:n]
+            line += f"  {VOC_NAMES.get(auto.precision, auto.precision)} against the recording: {fmt(auto.stft_distance(mel, T_(rec[None]).cuda()))}"
+        print(line)
 
     chosen = VOC_NAMES.get(auto.precision, str(auto.precision))
     chosen_key = "f16" if auto.precision == abi.VOC_F16 else "bf16x3"
