@@ -17,10 +17,13 @@ VOC_PRECISIONS = {"f16": VOC_F16, "bf16": VOC_BF16, "bf16x3": VOC_BF16X3}
 PART_ACOUSTIC, PART_VOCODER, PART_FFT = 1, 2, 4
 PART_MELSPEC = 8    # the log-mel front end: "melspec.mel_basis" + "melspec.window"; rebuilt by every finalize that names it
 PART_STFT = 16      # the multi-resolution STFT distance: "stft.<i>.window" [n_fft], up to four; rebuilt by every finalize that names it
+PART_ISTFT = 32     # STFT -> magnitude edit -> inverse STFT: "istft.window" [n_fft]; rebuilt by every finalize that names it
 OUT_PRON_ATTN, OUT_DUR, OUT_MEL2WORD, OUT_DICT_ATTN, OUT_WORD_ENCODER_OUT, OUT_X_MASK, OUT_CONTEXT, OUT_MEL_LENS = range(1, 9)
 OUT_POSTERIOR = 9   # not a copy: the posterior pass, dst = a PosteriorArgs block (include/dicttts_hip.h)
 OUT_MELSPEC = 10     # not a copy, needs no encode: wav -> log-mel, dst = a MelspecArgs block
 OUT_STFT_DISTANCE = 11   # not a copy, needs no encode: a pair of waveform batches -> the sums behind sc / mag, dst = a StftArgs block
+OUT_SPECTRAL = 12    # not a copy, needs no encode: STFT / edit / inverse STFT of a batch of waveforms, dst = a SpectralArgs block
+SPECTRAL_FORWARD, SPECTRAL_INVERSE = 1, 2   # dtts_spectral_args.mode bits; both = the reference's denoise
 SPK_EMBED, SPK_ID = 1, 2   # dtts_text2mel_speakers kinds: fp32 [B,256] (use_spk_embed) / int64 [B] (use_spk_id)
 TIMER_VOC_CONV, TIMER_S2PA = 1, 2
 TIMER_STAGE_ENCODER, TIMER_STAGE_DICT_ENCODER, TIMER_STAGE_FVAE, TIMER_STAGE_HIFIGAN = 3, 4, 5, 6   # the reference's profile_infer names
@@ -51,6 +54,13 @@ class StftArgs(C.Structure):
     _fields_ = [("size", C.c_int32), ("n_res", C.c_int32), ("hop", C.c_int32 * 4), ("B", C.c_int32), ("wav_ld", C.c_int32), ("mag_cap", C.c_int32),
                 ("reserved", C.c_int32), ("x_dev", C.c_void_p), ("y_dev", C.c_void_p), ("lens_dev", C.c_void_p), ("sums_dev", C.c_void_p),
                 ("count_dev", C.c_void_p), ("mag_dev", C.c_void_p)]
+
+
+class SpectralArgs(C.Structure):
+    """dtts_spectral_args (include/dicttts_hip.h): the argument block of dtts_text2mel_fetch(DTTS_OUT_SPECTRAL)"""
+    _fields_ = [("size", C.c_int32), ("mode", C.c_int32), ("hop", C.c_int32), ("B", C.c_int32), ("wav_ld", C.c_int32), ("spec_cap", C.c_int32),
+                ("floor", C.c_float), ("wav_dev", C.c_void_p), ("lens_dev", C.c_void_p), ("frames_dev", C.c_void_p), ("spec_dev", C.c_void_p),
+                ("out_dev", C.c_void_p), ("out_lens_dev", C.c_void_p)]
 
 
 class DttsConfig(C.Structure):
@@ -246,6 +256,15 @@ class Context:
             raise DttsError(f"stft_distance: {len(hops)} resolutions (supported: 1 .. 4)")
         a = StftArgs(C.sizeof(StftArgs), len(hops), (C.c_int32 * 4)(*hops), int(B), int(wav_ld), int(mag_cap), 0, x, y, lens or None, sums, count, mag or None)
         self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_STFT_DISTANCE, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_STFT_DISTANCE)")
+
+    def spectral(self, mode, B, wav_ld, hop, spec_cap, stream, wav=None, lens=None, frames=None, spec=None, out=None, out_lens=None, floor=0.0):
+        """STFT (mode SPECTRAL_FORWARD), inverse STFT (SPECTRAL_INVERSE) or STFT -> max(|S| - floor, 0) -> inverse STFT (both bits: the
+        reference's denoise) of B waveforms (dtts_text2mel_fetch(DTTS_OUT_SPECTRAL); needs PART_ISTFT finalised, no encode).  Device
+        pointers: wav f32 [B, wav_ld], lens i32 [B] or None, frames i32 [B], spec f32 [B, spec_cap, n_fft / 2 + 1, 2], out f32 [B, wav_ld],
+        out_lens i32 [B] or None; with both bits spec and frames may be None (the context's workspace)."""
+        a = SpectralArgs(C.sizeof(SpectralArgs), int(mode), int(hop), int(B), int(wav_ld), int(spec_cap), float(floor), wav or None, lens or None,
+                         frames or None, spec or None, out or None, out_lens or None)
+        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_SPECTRAL, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_SPECTRAL)")
 
     def fetch(self, what, dst, stream):
         self._chk(self.lib.dtts_text2mel_fetch(self.h, what, dst, stream), "dtts_text2mel_fetch")

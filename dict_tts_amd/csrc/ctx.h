@@ -28,6 +28,7 @@
 #include "flowstack.h"
 #include "melspec.h"
 #include "stftdist.h"
+#include "istft.h"
 
 // dtts_config.tune_flags: the bits the library honours are listed at TUNE_RELEASE_MASK (context.hip)
 #define DTTS_TUNE(h, bit) (((h)->tune & (bit)) != 0)
@@ -231,6 +232,16 @@ struct dtts_ctx {
     };
     std::vector<StftPlan> stft_plans;
     dtts::Arena a_stft;
+    // ---- STFT -> magnitude edit -> inverse STFT (dtts_text2mel_fetch(DTTS_OUT_SPECTRAL); istft.hip): the plan of the last
+    // dtts_finalize_weights(DTTS_PART_ISTFT) and the workspace of the spectrum and the windowed frames between the launches
+    bool istft_ready = false;
+    int is_n_fft = 0, is_sg_lo = 0, is_sg_hi = 0;
+    float *is_basis = nullptr, *is_wi = nullptr;        // forward basis (melspec_pack_basis) and inverse basis (istft_pack_inverse), fragment order
+    double* is_w2 = nullptr;                            // the window's squares [n_fft]
+    std::vector<float> is_window;                       // host copy: the envelope criterion is checked per hop
+    std::map<int, double> is_env;                       // hop -> smallest envelope value (istft_envelope_min), per plan
+    int is_skew_hop = 0, is_skew = 8;                   // the slab skew chosen for the hop of the last forward call
+    dtts::Arena a_spec;
 };
 
 namespace dtts {
@@ -332,5 +343,7 @@ int build_melspec(dtts_ctx* h);   // melspec.hip
 int melspec_forward(dtts_ctx* h, const dtts_melspec_args* a, hipStream_t stream);
 int build_stft(dtts_ctx* h);      // stftdist.hip
 int stft_forward(dtts_ctx* h, const dtts_stft_args* a, hipStream_t stream);
+int build_istft(dtts_ctx* h);     // istft.hip
+int spectral_forward(dtts_ctx* h, const dtts_spectral_args* a, hipStream_t stream);
 
 } // namespace dtts

@@ -36,12 +36,15 @@ def wav_to_int16(wav, norm=False):
     return wav.astype(np.int16)
 
 
-def infer_batch(model, vocoder, batch, z_p=None):
+def infer_batch(model, vocoder, batch, z_p=None, denoise_c=0.0):
     """batch: dict of tensors as DictTTSDataset.collater produces (word_tokens, keys, values, key_map, pinyin,
-    pinyin_map, pron_modified).  Returns (outputs dict, list of float32 waveforms, one per utterance)."""
+    pinyin_map, pron_modified).  Returns (outputs dict, list of float32 waveforms, one per utterance).
+    denoise_c > 0: the vocoder's spectral-subtraction filter at that strength (``run_inference``)."""
     out = _model_forward(model, batch, z_p)
     lens = out["mel_lens"]
     wav = vocoder.forward_batch(out["mel_out"], lens, check=True) if hasattr(vocoder, "overflowed") else vocoder.forward_batch(out["mel_out"], lens)
+    if denoise_c > 0:
+        wav, _ = vocoder.denoise(wav, lens, denoise_c)
     hop = vocoder.hop
     lens_h = lens.cpu().tolist()
     wav_h = wav.cpu().numpy()
@@ -58,13 +61,13 @@ def _model_forward(model, batch, z_p):
                  (batch["keys"], batch["values"], batch["key_map"], batch["pinyin"], batch["pinyin_map"]), infer=True, z_p=z_p, **kw)
 
 
-def _iter_results(model, vocoder, batches, pipeline, out_wav_norm=False):
+def _iter_results(model, vocoder, batches, pipeline, out_wav_norm=False, denoise_c=0.0):
     """yields (batch, outputs, waveforms) per batch.  pipeline=True: the vocoder of batch i runs on a second HIP stream
     while text->mel of batch i+1 runs on the current one (the acoustic model's small kernels leave most CUs idle;
     bench.py measures this arrangement), and batch i's device->host copies happen after batch i+1 has been enqueued."""
     if not pipeline:
         for batch in batches:
-            out, wavs = infer_batch(model, vocoder, batch, batch.get("z_p"))
+            out, wavs = infer_batch(model, vocoder, batch, batch.get("z_p"), denoise_c)
             yield batch, out, wavs
         return
     main = torch.cuda.current_stream()
@@ -85,6 +88,8 @@ def _iter_results(model, vocoder, batches, pipeline, out_wav_norm=False):
             if need:
                 with torch.cuda.stream(voc_stream):
                     wav = vocoder.forward_batch(out["mel_out"], out["mel_lens"], check=True)
+                    if denoise_c > 0:
+                        wav, _ = vocoder.denoise(wav, out["mel_lens"], denoise_c)
                     if int16_on_device:
                         wav = vocoder.to_int16(wav, out["mel_lens"], norm=out_wav_norm)
         with torch.cuda.stream(voc_stream):
@@ -98,6 +103,8 @@ def _iter_results(model, vocoder, batches, pipeline, out_wav_norm=False):
         voc_stream.wait_stream(main)
         with torch.cuda.stream(voc_stream):
             wav = vocoder.forward_batch(out["mel_out"], out["mel_lens"])
+            if denoise_c > 0:
+                wav, _ = vocoder.denoise(wav, out["mel_lens"], denoise_c)
             if int16_on_device:
                 wav = vocoder.to_int16(wav, out["mel_lens"], norm=out_wav_norm)
         out["mel_out"].record_stream(voc_stream)
@@ -112,16 +119,20 @@ def _iter_results(model, vocoder, batches, pipeline, out_wav_norm=False):
 
 
 def run_inference(model, vocoder, batches, gen_dir, pinyin_encoder, sample_rate=22050, save_wavs=True, out_wav_norm=False,
-                  pipeline=None):
+                  pipeline=None, denoise_c=0.0):
     """batches: iterable of dicts with the tensors above plus 'item_name' (list[str]) and 'text' (list[str]).
     pinyin_encoder: list mapping pinyin-token id -> string (``pinyin_encoder.pkl`` of the reference).
     Writes <gen_dir>/wavs/*.wav and <gen_dir>/meta.csv; returns the meta rows.
-    pipeline: overlap the vocoder with the next batch's text->mel on two streams (default: on for the HIP model)."""
+    pipeline: overlap the vocoder with the next batch's text->mel on two streams (default: on for the HIP model).
+    denoise_c: > 0 runs the reference's spectral-subtraction post-filter ``denoise(wav, v=denoise_c)`` (vocoders/vocoder_utils.py:7-15) on
+    the vocoder's stream, between the generator and the int16 conversion (``vocoder.denoise``).  The reference ships the strength as
+    hparams['vocoder_denoise_c'] (egs/egs_bases/tts/base.yaml:112) but its spec2wav never applies it, so nothing here reads that key:
+    pass ``denoise_c=hparams['vocoder_denoise_c']`` to have it.  0.0 (the default) leaves every output as it was."""
     os.makedirs(os.path.join(gen_dir, "wavs"), exist_ok=True)
     rows, results_id = [], 0
     if pipeline is None:
         pipeline = hasattr(model, "ctx") and hasattr(vocoder, "ctx")
-    for batch, out, wavs in _iter_results(model, vocoder, batches, pipeline, out_wav_norm):
+    for batch, out, wavs in _iter_results(model, vocoder, batches, pipeline, out_wav_norm, denoise_c):
         pron_attn = out["pron_attn"].cpu()
         for i, wav in enumerate(wavs):
             item_name, text = batch["item_name"][i], batch["text"][i]

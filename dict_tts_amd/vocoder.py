@@ -150,6 +150,7 @@ class HifiGAN:
         self.ctx, self.precision = ctx, precision
         self._seen_bad = 0   # (a new context counts from zero)
         self._stft = None    # (and has no STFT plans yet: stft_distance loads them again)
+        self._spectral = None   # (nor the plan of denoise)
 
     # -- reference API -------------------------------------------------------------------------------------
     def spec2wav(self, mel, **kwargs):
@@ -225,6 +226,26 @@ class HifiGAN:
             lens = lens.to(device=mels.device, dtype=torch.int32)
         wav = self.forward_batch(mels, lens)
         return mr(wav, wavs, None if lens is None else lens * self.hop)
+
+    def denoise(self, wav, lens=None, v=0.1):
+        """the reference's post-filter ``denoise(wav, v)`` (vocoders/vocoder_utils.py:7-15: STFT, max(|S| - v, 0) with the phase kept,
+        inverse STFT at hparams fft_size / hop_size / win_size) on the device, for a batch: wav [B, T * hop] float32 cuda tensor as
+        forward_batch returns it, lens [B] valid FRAMES or None -> (wav [B, T * hop], out_lens [B] int32, in samples = lens * hop_size);
+        samples past each utterance are zero.  The reference's strength key is ``vocoder_denoise_c``; its spec2wav never applies the
+        filter, and neither does this class unless asked (dict_tts_amd/infer.py: denoise_c).  The plan lives in the vocoder's context
+        (dict_tts_amd/spectral.py)."""
+        from . import spectral
+        sp = getattr(self, "_spectral", None)
+        if sp is None:
+            sp = spectral.Spectral({**hparams_mod.BIAOBEI_DEFAULTS, **hparams_mod.hparams}, ctx=self.ctx)
+            if sp.hop != self.hop:   # lens are frames of the generator: another hop would cut every utterance's tail
+                raise abi.DttsError(f"denoise: hop_size={sp.hop} of the hparams, but the generator upsamples by {self.hop}")
+            self._spectral = sp
+        if not (wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 2 and wav.shape[1] % self.hop == 0):
+            raise abi.DttsError(f"denoise: wav of shape {tuple(wav.shape)}, forward_batch gives [B, T * {self.hop}] float32 cuda tensors")
+        if lens is not None:
+            lens = lens.to(device=wav.device, dtype=torch.int32) * self.hop
+        return sp.denoise(wav, lens, v)
 
     def overflowed(self):
         """True when a forward since the last call of this method (or construction) delivered non-finite pre-tanh samples, i.e. an fp16

@@ -173,6 +173,11 @@ DTTS_API int dtts_load_weight(dtts_handle h, const char* name, const void* host_
  * it); the samples outside the window's non-zero support are left out of the contraction.  Rebuilt by EVERY call that names it, like
  * DTTS_PART_MELSPEC.  DTTS_E_NOENT without "stft.0.window". */
 #define DTTS_PART_STFT 16
+/* STFT -> magnitude edit -> inverse STFT (DTTS_OUT_SPECTRAL below): ONE plan from "istft.window" [n_fft], the analysis AND synthesis window as
+ * torch.stft / torch.istft apply it (the win_length samples zero padded and centred to n_fft, as "stft.<i>.window" is).  n_fft is the tensor's
+ * length (512 / 1024 / 2048, else DTTS_E_INVAL naming it).  Rebuilt by EVERY call that names it, like DTTS_PART_MELSPEC.  DTTS_E_NOENT
+ * without "istft.window". */
+#define DTTS_PART_ISTFT 32
 /* Fold, repack into MFMA fragment order and upload.  Fails with DTTS_E_NOENT naming the first missing tensor. */
 DTTS_API int dtts_finalize_weights(dtts_handle h, int parts);
 
@@ -363,6 +368,49 @@ typedef struct dtts_stft_args {
     int64_t* count_dev;
     float* mag_dev;               /* or NULL */
 } dtts_stft_args;
+/*
+ * DTTS_OUT_SPECTRAL: not a copy, needs NO encode — the reference's one post-filter on the vocoder's output, denoise(wav, v)
+ * (vocoders/vocoder_utils.py:7-15: librosa.stft, max(|S| - v, 0) with the phase kept, librosa.istft; strength key vocoder_denoise_c,
+ * egs/egs_bases/tts/base.yaml:112), and its two halves alone (_stft / _istft of utils/audio.py:35-42, Griffin-Lim's building blocks), for a
+ * batch: dst = (dtts_spectral_args*), args->size = sizeof(*args).  mode = DTTS_SPECTRAL_FORWARD | DTTS_SPECTRAL_INVERSE is denoise, FORWARD
+ * alone is _stft (with the edit when floor > 0), INVERSE alone is _istft of ANY spectrum, consistent or not.  The window and n_fft are those of
+ * dtts_finalize_weights(DTTS_PART_ISTFT).  Per utterance b of len_b = lens_dev[b] samples (clamped to [0, wav_ld]; NULL = wav_ld):
+ *   FORWARD  n_fft / 2 zeros on both sides (center=True, pad_mode='constant'), T_b = 1 + len_b / hop frames,
+ *            S[t][k] = sum_n w[n] x_pad[t hop + n] e^(-2 pi i k n / n_fft), k = 0 .. n_fft / 2; then m = |S|, S' = S max(m - floor, 0) / m
+ *            (0 where m = 0; floor = 0 leaves S as it is, without the division).  frames_dev[b] = T_b; rows >= T_b of spec_dev untouched.
+ *   INVERSE  T_b = frames_dev[b] clamped to [0, 1 + wav_ld / hop]; y_t[n] = w[n] irfft(S'[t])[n] (the imaginary parts of bins 0 and n_fft / 2
+ *            are never read), overlap-add at t hop in ascending frame order, each sample divided by the envelope sum_t w^2[n - t hop] over the
+ *            frames that cover it, n_fft / 2 samples dropped at both ends: out_len_b = hop (T_b - 1) samples (0 for one frame); samples
+ *            >= out_len_b of out_dev untouched; out_lens_dev[b] = out_len_b.
+ *   wav_dev f32 [B][wav_ld] (FORWARD) · lens_dev i32 [B] or NULL (FORWARD) · frames_dev i32 [B] · spec_dev f32 [B][spec_cap][n_fft / 2 + 1][2],
+ *   interleaved re, im (torch.view_as_real's layout), 8-byte aligned · out_dev f32 [B][wav_ld] (INVERSE) · out_lens_dev i32 [B] or NULL.
+ *   With both mode bits spec_dev and frames_dev may be NULL: the spectrum and the frame counts then live in a workspace of the context
+ *   (reserved on the first call, like the posterior pass's; it also holds the windowed frames [B][spec_cap][n_fft] of every INVERSE).
+ * One launch (FORWARD), two (INVERSE: the frames' inverse DFT, then the overlap-add) or three on `stream`; no host synchronisation unless the
+ * workspace grows; no atomics.  Both contractions are DTTS_OUT_MELSPEC's (exact fp32 products, fp32 over eight values, fp64 across those)
+ * against bases computed in fp64; the overlap-add and the envelope are fp64, rounded once.  Every utterance's result is bit-identical alone
+ * and inside any batch.  DTTS_E_STATE without a finalised plan; DTTS_E_INVAL (naming the value) for a wrong size, a mode outside 1 .. 3,
+ * B <= 0, a hop outside 1 .. n_fft, a (window, hop) whose envelope does not stay above 1e-11 at every kept sample (torch.istft's criterion,
+ * evaluated in fp64 on the host for a two-frame signal, whose envelope bounds every longer one's from below; the message names hop and the
+ * smallest value; INVERSE only), spec_cap < 1 + wav_ld / hop, a floor that is negative or not finite, a NULL pointer the mode needs, or
+ * an out_dev that is wav_dev or overlaps any of its B wav_ld samples (the buffers must be disjoint: nothing runs in place).
+ */
+#define DTTS_OUT_SPECTRAL 12
+#define DTTS_SPECTRAL_FORWARD 1
+#define DTTS_SPECTRAL_INVERSE 2
+typedef struct dtts_spectral_args {
+    int32_t size;                 /* sizeof(dtts_spectral_args) */
+    int32_t mode;                 /* DTTS_SPECTRAL_FORWARD, DTTS_SPECTRAL_INVERSE or both */
+    int32_t hop;                  /* any integer in 1 .. n_fft */
+    int32_t B, wav_ld, spec_cap;  /* spec_cap: rows per utterance of the spectrum, >= 1 + wav_ld / hop */
+    float floor;                  /* v >= 0: subtracted from every magnitude (FORWARD); the reference's default is 0.1 */
+    const float* wav_dev;         /* FORWARD */
+    const int32_t* lens_dev;      /* FORWARD, or NULL */
+    int32_t* frames_dev;          /* written by FORWARD, read by INVERSE alone; NULL allowed with both bits */
+    float* spec_dev;              /* written by FORWARD, read by INVERSE alone; NULL allowed with both bits */
+    float* out_dev;               /* INVERSE */
+    int32_t* out_lens_dev;        /* INVERSE, or NULL */
+} dtts_spectral_args;
 DTTS_API int dtts_text2mel_fetch(dtts_handle h, int what, void* dst_dev, dtts_stream stream);
 
 /*
