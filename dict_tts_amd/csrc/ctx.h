@@ -220,14 +220,14 @@ struct dtts_ctx {
     dtts::Arena a_post;
     // ---- log-mel front end (dtts_text2mel_fetch(DTTS_OUT_MELSPEC); melspec.hip): the plan of the last dtts_finalize_weights(DTTS_PART_MELSPEC)
     bool melspec_ready = false;
-    int ms_n_fft = 0, ms_n_mels = 0, ms_win = 0, ms_sg_lo = 0, ms_sg_hi = 0;
-    float *ms_basis = nullptr, *ms_melpack = nullptr;   // windowed DFT basis and mel basis in fragment order
+    dtts::StftBasisPlan ms;                             // windowed DFT basis in fragment order, n_fft, the super-groups the window keeps
+    int ms_n_mels = 0, ms_win = 0;
+    float* ms_melpack = nullptr;                        // mel basis in fragment order (melspec_pack_mel)
     int ms_skew_hop = 0, ms_skew = 8;                   // the slab skew chosen for the hop of the last call
     // ---- multi-resolution STFT distance (dtts_text2mel_fetch(DTTS_OUT_STFT_DISTANCE); stftdist.hip): the plans of the last
     // dtts_finalize_weights(DTTS_PART_STFT), one per "stft.<i>.window", and the workspace of the per-tile sums
     struct StftPlan {
-        int n_fft = 0, sg_lo = 0, sg_hi = 0;
-        float* basis = nullptr;                         // windowed DFT basis in fragment order (melspec_pack_basis)
+        dtts::StftBasisPlan core;
         int layout_hop = 0, ps = 31, tt = 1, ybase = 0; // the LDS layout chosen for the hop of the last call (stft_layout)
     };
     std::vector<StftPlan> stft_plans;
@@ -235,8 +235,8 @@ struct dtts_ctx {
     // ---- STFT -> magnitude edit -> inverse STFT (dtts_text2mel_fetch(DTTS_OUT_SPECTRAL); istft.hip): the plan of the last
     // dtts_finalize_weights(DTTS_PART_ISTFT) and the workspace of the spectrum and the windowed frames between the launches
     bool istft_ready = false;
-    int is_n_fft = 0, is_sg_lo = 0, is_sg_hi = 0;
-    float *is_basis = nullptr, *is_wi = nullptr;        // forward basis (melspec_pack_basis) and inverse basis (istft_pack_inverse), fragment order
+    dtts::StftBasisPlan is;                             // the forward half's plan
+    float* is_wi = nullptr;                             // inverse basis (istft_pack_inverse), fragment order
     double* is_w2 = nullptr;                            // the window's squares [n_fft]
     std::vector<float> is_window;                       // host copy: the envelope criterion is checked per hop
     std::map<int, double> is_env;                       // hop -> smallest envelope value (istft_envelope_min), per plan
@@ -340,6 +340,7 @@ int build_acoustic(dtts_ctx* h);
 int build_vocoder(dtts_ctx* h);
 int build_fft(dtts_ctx* h);
 int build_melspec(dtts_ctx* h);   // melspec.hip
+int check_wav_ld(dtts_ctx* h, const char* me, int wav_ld, int n_fft);   // melspec.hip: stft_wav_ld_ok or the one refusal (0 = in range)
 int melspec_forward(dtts_ctx* h, const dtts_melspec_args* a, hipStream_t stream);
 int build_stft(dtts_ctx* h);      // stftdist.hip
 int stft_forward(dtts_ctx* h, const dtts_stft_args* a, hipStream_t stream);

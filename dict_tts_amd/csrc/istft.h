@@ -7,22 +7,22 @@
 #include <cstddef>
 #include <vector>
 
+#include "stft_core.h"
+
 namespace dtts {
 
 constexpr int ISTFT_TILE = 32;          // frames per workgroup (one wave) of the inverse contraction: the only tile size it has
 constexpr int ISTFT_GATHER = 256;       // output samples per workgroup of the overlap-add
 constexpr double ISTFT_ENV_MIN = 1e-11; // torch.istft's criterion on the window envelope
 
-// forward + edit: melspec.hip's contraction with re / im kept, S' = S max(|S| - floor, 0) / |S| written as [B][spec_cap][n_fft / 2 + 1][2]
+// forward + edit: the shared contraction with re / im kept, S' = S max(|S| - floor, 0) / |S| written as [B][spec_cap][n_fft / 2 + 1][2]
 struct SpecFwdParams {
     const float* wav;        // [B][wav_ld]
     const int* lens;         // [B] samples, or null = wav_ld
     int* frames;             // [B] out: T_b = 1 + len_b / hop
     float* spec;             // [B][spec_cap][n_fft / 2 + 1][2] out, rows < T_b
-    const float4* basis;     // melspec_pack_basis of the (centred) window
-    int B, wav_ld, spec_cap, hop, n_fft;
-    int sg_lo, sg_hi;        // the 32-sample super-groups the window does not zero (multiples of four)
-    int tt, ntile, ps;       // frames per tile, tiles per utterance at wav_ld samples, slab skew (melspec.h)
+    StftGeom g;              // the basis of the (centred) window; tt and ntile are set by spectral_forward_launch
+    int B, wav_ld, spec_cap;
     int csplit;              // workgroups per tile, each with n_fft / 64 / csplit bin blocks (istft_split)
     float floor;             // v >= 0; 0 = no edit (and no division)
 };

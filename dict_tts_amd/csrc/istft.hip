@@ -1,11 +1,9 @@
 // Spectral-subtraction denoising on the device, and its two halves alone: the reference's denoise(wav, v) (vocoders/vocoder_utils.py:7-15:
 // librosa.stft -> max(|S| - v, 0), phase kept -> librosa.istft; center=True, pad_mode='constant'), _stft and _istft (utils/audio.py:35-42).
 //
-// FORWARD + EDIT (spectral_fwd_kernel) is melspec.hip's contraction: the samples of a tile of frames staged once by
-// bounds-checked buffer loads (outside [0, len) they read zero, which IS the constant padding), v_mfma_f32_32x32x2_f32 against the windowed DFT
-// basis of melspec_pack_basis, fp32 chains of MELSPEC_CHUNK steps joined in fp64, re[n_fft / 2] in the im slot of bin 0.  re and im stay in
-// the accumulators, the edit S' = S max(|S| - v, 0) / |S| happens there (v = 0: nothing, no division), and S' leaves as interleaved
-// (re, im) pairs [B][spec_cap][n_fft / 2 + 1][2], torch.view_as_real's layout.
+// FORWARD + EDIT (spectral_fwd_kernel) is the shared contraction of stft_core.h, staged with zeros outside
+// [0, len), which IS the constant padding.  re and im stay in the accumulators, the edit S' = S max(|S| - v, 0) / |S| happens there (v = 0:
+// nothing, no division), and S' leaves as interleaved (re, im) pairs [B][spec_cap][n_fft / 2 + 1][2], torch.view_as_real's layout.
 //
 // INVERSE (section 3.8), two launches:
 //   * istft_frames_kernel: D[sample 32][frame 32] += Wi[sample][q 2] * S'[q 2][frame], one wave per 32 frames, over the n_fft REAL spectral
@@ -24,95 +22,29 @@
 
 namespace dtts {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16i;
-
 template <int WT>
 __global__ __launch_bounds__(64 * WT) void spectral_fwd_kernel(const SpecFwdParams p) {
     extern __shared__ __attribute__((aligned(16))) float slab[];
-    constexpr int THREADS = 64 * WT;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, fi = lane & 31, hf = lane >> 5;
-    const int cg = blockIdx.x % p.csplit, bt = blockIdx.x / p.csplit, b = bt / p.ntile, tile = bt % p.ntile;
-    int len = p.lens ? p.lens[b] : p.wav_ld;
-    len = len < 0 ? 0 : (len > p.wav_ld ? p.wav_ld : len);
-    const int T = 1 + len / p.hop;
+    const int cg = blockIdx.x % p.csplit, bt = blockIdx.x / p.csplit, b = bt / p.g.ntile, tile = bt % p.g.ntile;
+    const int len = stft_len(p.lens, b, p.wav_ld);
+    const int T = 1 + len / p.g.hop;
     if (tile == 0 && cg == 0 && tid == 0) p.frames[b] = T;
-    const int f0 = tile * p.tt;
+    const int f0 = tile * p.g.tt;
     if (f0 >= T) return;
-    const int nf = T - f0 < p.tt ? T - f0 : p.tt;   // frames of this tile
-    const int ps = p.ps;
-
-    // ---- the tile's samples: global sample g0 + q -> slab position q; outside [0, len) the buffer resource returns zero
-    {
-        const int P = (nf - 1) * p.hop + p.n_fft;
-        const int g0 = f0 * p.hop - p.n_fft / 2;
-        const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.wav + (size_t)b * p.wav_ld), 0, len * 4, 0x00020000);
-        for (int q = tid; q < P; q += THREADS) {
-            const unsigned v = __builtin_amdgcn_raw_buffer_load_b32(rs, (g0 + q) * 4, 0, 0);   // (a negative offset is a huge unsigned one)
-            slab[q + (q >> ps)] = __builtin_bit_cast(float, v);
-        }
-    }
+    const int nf = T - f0 < p.g.tt ? T - f0 : p.g.tt;   // frames of this tile
+    const float* const sig[1] = {p.wav + (size_t)b * p.wav_ld};
+    stft_stage<64 * WT>(slab, 0, sig, len, f0, nf, p.g, tid, [](int g) { return g; });
     __syncthreads();
     if (wv * 32 >= nf) return;   // (no barrier below)
     const int f = wv * 32 + fi;
     const bool live = f < nf;
-    const int abase = (live ? f : wv * 32) * p.hop + hf;   // a dead lane recomputes the wave's first frame and stores nothing
-    const int SG = p.n_fft / 32, c_lo = cg * (p.n_fft / 64 / p.csplit), c_hi = c_lo + p.n_fft / 64 / p.csplit;   // this workgroup's bin blocks
-    float* row = p.spec + ((size_t)b * p.spec_cap + f0 + (live ? f : wv * 32)) * (size_t)(p.n_fft + 2);
+    const int abase = (live ? f : wv * 32) * p.g.hop + hf;   // a dead lane recomputes the wave's first frame and stores nothing
+    const int N = p.g.n_fft, c_lo = cg * (N / 64 / p.csplit), c_hi = c_lo + N / 64 / p.csplit;   // this workgroup's bin blocks
+    float* row = p.spec + ((size_t)b * p.spec_cap + f0 + (live ? f : wv * 32)) * (size_t)(N + 2);
     const float v = p.floor;
 
-    // the basis stream of melspec_kernel: two register buffers of one 32-sample super-group (eight 16-byte fragments per lane) take turns
-    auto fetch = [&](float4 (&d)[8], int c, int sg) {
-        const float4* s = p.basis + ((size_t)(c * SG + sg) * 8) * 64 + lane;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) d[q] = s[q * 64];
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    float4 fa[8], fb[8];
-    fetch(fa, c_lo, p.sg_lo);
-#pragma unroll 1
-    for (int c = c_lo; c < c_hi; ++c) {
-        double dre[16], dim[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dre[r] = dim[r] = 0.0;
-        auto contract = [&](const float4 (&w)[8], int sg) {
-            const int a0 = abase + 32 * sg;
-#pragma unroll
-            for (int ch = 0; ch < 16 / MELSPEC_CHUNK; ++ch) {
-                f32x16i re, im;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) re[r] = im[r] = 0.f;
-#pragma unroll
-                for (int jj = 0; jj < MELSPEC_CHUNK; ++jj) {
-                    const int j = ch * MELSPEC_CHUNK + jj, a = a0 + 2 * j;
-                    const float x = slab[a + (a >> ps)];
-                    re = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j >> 2][j & 3], x, re, 0, 0, 0);
-                    im = __builtin_amdgcn_mfma_f32_32x32x2f32(w[4 + (j >> 2)][j & 3], x, im, 0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    dre[r] += (double)re[r];
-                    dim[r] += (double)im[r];
-                }
-            }
-        };
-#pragma unroll 1
-        for (int sg = p.sg_lo; sg < p.sg_hi; sg += 4) {
-            fetch(fb, c, sg + 1);
-            contract(fa, sg);
-            fetch(fa, c, sg + 2);
-            contract(fb, sg + 1);
-            fetch(fb, c, sg + 3);
-            contract(fa, sg + 2);
-            const bool wrap = sg + 4 == p.sg_hi;
-            fetch(fa, wrap ? (c + 1 < c_hi ? c + 1 : c) : c, wrap ? p.sg_lo : sg + 4);
-            contract(fb, sg + 3);
-        }
-        float re[16], im[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            re[r] = (float)dre[r];
-            im[r] = (float)dim[r];
-        }
+    stft_contract(p.g.basis, N / 32, p.g.sg_lo, p.g.sg_hi, c_lo, c_hi, slab, abase, p.g.ps, lane, [&](int c, stft_f32x16 re, stft_f32x16 im) {
         // ---- bin 0 is real and its im slot carried re[n_fft / 2], a (real) bin of its own
         const bool edge = c == 0 && hf == 0;
         float nyq = 0.f;
@@ -139,11 +71,13 @@ __global__ __launch_bounds__(64 * WT) void spectral_fwd_kernel(const SpecFwdPara
 #pragma unroll
                 for (int e = 0; e < 4; ++e) d[e] = make_float2(re[4 * rq + e], im[4 * rq + e]);
             }
-            if (edge) *(float2*)(row + p.n_fft) = make_float2(nyq, 0.f);
+            if (edge) *(float2*)(row + N) = make_float2(nyq, 0.f);
         }
-    }
+    });
 }
 
+// NOT stft_contract, though the pipeline has the same shape: the B operand is no slab read but registers fetched alongside the basis (xa / xb
+// travel with fa / fb), and every chain ends at a sched_barrier of its own.  A shared loop would have to branch on its caller.
 __global__ __launch_bounds__(64) void istft_frames_kernel(const SpecInvParams p) {
     const int lane = threadIdx.x, fi = lane & 31, hf = lane >> 5;
     const int cg = blockIdx.x % p.csplit, bt = blockIdx.x / p.csplit, b = bt / p.ntile, tile = bt % p.ntile;
@@ -180,7 +114,7 @@ __global__ __launch_bounds__(64) void istft_frames_kernel(const SpecInvParams p)
         auto contract = [&](const float4 (&w)[8], const float2 (&x)[8]) {
 #pragma unroll
             for (int ch = 0; ch < 16 / MELSPEC_CHUNK; ++ch) {
-                f32x16i y0, y1;
+                stft_f32x16 y0, y1;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) y0[r] = y1[r] = 0.f;
 #pragma unroll
@@ -291,35 +225,18 @@ int istft_split(long long tiles, int blocks, long long want) {
 
 template <int WT>
 static hipError_t spectral_fwd_cfg(SpecFwdParams p, int n_cu, hipStream_t stream) {
-    p.tt = melspec_tile_frames(WT, p.hop, p.n_fft, p.ps);
-    const int t_cap = 1 + p.wav_ld / p.hop;
-    p.ntile = (t_cap + p.tt - 1) / p.tt;
-    const size_t lds = melspec_slab_dwords(p.tt, p.hop, p.n_fft, p.ps) * 4;
-    p.csplit = istft_split((long long)p.ntile * p.B, p.n_fft / 64, 4LL * n_cu);
-    if (lds > (size_t)MELSPEC_LDS_BYTES || (long long)p.ntile * p.B * p.csplit > INT_MAX) return hipErrorInvalidValue;
-    auto kern = spectral_fwd_kernel<WT>;
-    static bool configured_dev[64] = {};   // per device: hipFuncSetAttribute is per device
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    bool& configured = configured_dev[cur_dev & 63];
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, MELSPEC_LDS_BYTES);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(p.ntile * p.B * p.csplit)), dim3(64 * WT), lds, stream, p);
+    const size_t lds = stft_set_tile(p.g, WT, p.wav_ld);
+    p.csplit = istft_split((long long)p.g.ntile * p.B, p.g.n_fft / 64, 4LL * n_cu);
+    if (lds > (size_t)MELSPEC_LDS_BYTES || (long long)p.g.ntile * p.B * p.csplit > INT_MAX) return hipErrorInvalidValue;
+    if (hipError_t e = stft_lds_limit<spectral_fwd_kernel<WT>>()) return e;
+    hipLaunchKernelGGL(spectral_fwd_kernel<WT>, dim3((unsigned)(p.g.ntile * p.B * p.csplit)), dim3(64 * WT), lds, stream, p);
     return hipGetLastError();
 }
 
-// melspec_launch's tile rule: four waves x 32 frames; two waves while the larger tiles would leave more than half of the CUs without one
 hipError_t spectral_forward_launch(SpecFwdParams p, int n_cu, hipStream_t stream) {
-    if (!melspec_supported(p.n_fft, p.hop, p.n_fft, 1)) return hipErrorInvalidValue;
-    if (p.B < 1 || p.wav_ld < 0 || p.sg_lo < 0 || p.sg_hi > p.n_fft / 32 || p.sg_lo >= p.sg_hi || (p.sg_lo & 3) || (p.sg_hi & 3) || p.ps < 1) return hipErrorInvalidValue;
-    if (((long long)p.wav_ld + MELSPEC_LDS_BYTES / 4 + p.n_fft) * 4 >= (1LL << 31)) return hipErrorInvalidValue;   // 32-bit byte offsets of the buffer loads
-    if (p.spec_cap < 1 + p.wav_ld / p.hop || !p.frames || !p.spec || ((uintptr_t)p.spec & 7)) return hipErrorInvalidValue;
-    const int tt4 = melspec_tile_frames(4, p.hop, p.n_fft, p.ps);
-    const long long tiles4 = (long long)p.B * ((1 + p.wav_ld / p.hop + tt4 - 1) / tt4);
-    return 2 * tiles4 <= n_cu ? spectral_fwd_cfg<2>(p, n_cu, stream) : spectral_fwd_cfg<4>(p, n_cu, stream);
+    if (!stft_geom_ok(p.g, p.B, p.wav_ld)) return hipErrorInvalidValue;
+    if (p.spec_cap < 1 + p.wav_ld / p.g.hop || !p.frames || !p.spec || ((uintptr_t)p.spec & 7)) return hipErrorInvalidValue;
+    return stft_tile_waves(p.B, p.wav_ld, p.g.hop, p.g.n_fft, p.g.ps, n_cu) == 2 ? spectral_fwd_cfg<2>(p, n_cu, stream) : spectral_fwd_cfg<4>(p, n_cu, stream);
 }
 
 hipError_t istft_frames_launch(SpecInvParams p, int n_cu, hipStream_t stream) {
@@ -350,27 +267,19 @@ int build_istft(dtts_ctx* h) {
     const int n_fft = (int)std::min<int64_t>(wn->shape[0], INT_MAX);
     std::string why;
     if (!melspec_supported(n_fft, n_fft, n_fft, 1, &why)) return fail(h, DTTS_E_INVAL, "%s: istft.window: unsupported %s", me, why.c_str());
-    int lo = n_fft, hi = -1;   // the non-zero support
-    for (int k = 0; k < n_fft; ++k) {
+    for (int k = 0; k < n_fft; ++k)
         if (!std::isfinite(wn->f[k])) return fail(h, DTTS_E_INVAL, "%s: istft.window[%d] is not finite", me, k);
-        if (wn->f[k] != 0.f) {
-            lo = std::min(lo, k);
-            hi = k;
-        }
-    }
-    if (hi < 0) return fail(h, DTTS_E_INVAL, "%s: istft.window is all zero", me);
+    const SgRange sup = window_support(wn->f);
+    if (!sup.hi) return fail(h, DTTS_E_INVAL, "%s: istft.window is all zero", me);
     std::vector<double> w2(n_fft);
     for (int k = 0; k < n_fft; ++k) w2[k] = (double)wn->f[k] * (double)wn->f[k];
     float* basis = upload(h, melspec_pack_basis(n_fft, wn->f));
     float* wi = upload(h, istft_pack_inverse(n_fft, wn->f));
     double* w2d = upload(h, w2);
     if (!basis || !wi || !w2d) return fail(h, DTTS_E_NOMEM, "%s: device allocation failed", me);
-    h->is_basis = basis;
+    h->is = StftBasisPlan{basis, n_fft, sup.lo, sup.hi};
     h->is_wi = wi;
     h->is_w2 = w2d;
-    h->is_n_fft = n_fft;
-    h->is_sg_lo = lo / 128 * 4;           // whole FOURS of 32-sample super-groups, as the contraction walks them
-    h->is_sg_hi = (hi + 128) / 128 * 4;
     h->is_window = wn->f;
     h->is_env.clear();
     h->is_skew_hop = 0;
@@ -385,13 +294,12 @@ int spectral_forward(dtts_ctx* h, const dtts_spectral_args* a, hipStream_t strea
     if (a->size != (int32_t)sizeof(dtts_spectral_args))
         return fail(h, DTTS_E_INVAL, "%s: argument block of size = %d bytes, this library's is %d", me, a->size, (int)sizeof(dtts_spectral_args));
     if (!h->istft_ready) return fail(h, DTTS_E_STATE, "%s before dtts_finalize_weights(DTTS_PART_ISTFT)", me);
-    const int N = h->is_n_fft;
+    const int N = h->is.n_fft;
     if (a->mode < 1 || a->mode > 3) return fail(h, DTTS_E_INVAL, "%s: mode = %d (DTTS_SPECTRAL_FORWARD = 1, DTTS_SPECTRAL_INVERSE = 2, or both = 3)", me, a->mode);
     const bool fwd = (a->mode & DTTS_SPECTRAL_FORWARD) != 0, inv = (a->mode & DTTS_SPECTRAL_INVERSE) != 0;
     if (a->B <= 0) return fail(h, DTTS_E_INVAL, "%s: B = %d", me, a->B);
     if (a->hop < 1 || a->hop > N) return fail(h, DTTS_E_INVAL, "%s: hop = %d (supported: 1 .. n_fft = %d)", me, a->hop, N);
-    if (a->wav_ld < 0 || ((long long)a->wav_ld + MELSPEC_LDS_BYTES / 4 + N) * 4 >= (1LL << 31))
-        return fail(h, DTTS_E_INVAL, "%s: wav_ld = %d samples (supported: 0 .. 2^29 - 2^16)", me, a->wav_ld);
+    if (int e = check_wav_ld(h, me, a->wav_ld, N)) return e;
     const int t_need = 1 + a->wav_ld / a->hop;
     if (a->spec_cap < t_need)
         return fail(h, DTTS_E_INVAL, "%s: spec_cap = %d rows, wav_ld = %d samples at hop %d give %d", me, a->spec_cap, a->wav_ld, a->hop, t_need);
@@ -439,15 +347,10 @@ int spectral_forward(dtts_ctx* h, const dtts_spectral_args* a, hipStream_t strea
         p.lens = a->lens_dev;
         p.frames = frames;
         p.spec = spec;
-        p.basis = (const float4*)h->is_basis;
+        p.g = stft_geom(h->is, a->hop, h->is_skew);
         p.B = a->B;
         p.wav_ld = a->wav_ld;
         p.spec_cap = a->spec_cap;
-        p.hop = a->hop;
-        p.n_fft = N;
-        p.sg_lo = h->is_sg_lo;
-        p.sg_hi = h->is_sg_hi;
-        p.ps = h->is_skew;
         p.floor = a->floor;
         LAUNCH(spectral_forward_launch(p, h->n_cu, stream));
     }

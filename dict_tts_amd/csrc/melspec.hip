@@ -2,122 +2,45 @@
 // data_gen/tts/data_gen_utils.py:122-134): zero padding of n_fft / 2 samples on both sides, frames of n_fft samples every hop, periodic Hann
 // window of win_length centred in the frame, |rfft|, mel basis, log10(max(eps, .)).  One launch per batch.
 //
-// The time window is the contraction index: v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 chains of MELSPEC_CHUNK steps joined in fp64),
-//   D[bin 32][frame 32] += Wd[bin][k 2] * X[k 2][frame],   X[k][frame f] = slab[f * hop + k],
-// a row-shifted window of ONE LDS tile: the samples of a tile of frames are staged once, (tt - 1) * hop + n_fft floats,
-// by bounds-checked buffer loads — samples before 0 and past wav_lens[b] read as zero, which IS the reference's constant padding.
-//   * Wd is the windowed DFT basis, computed in fp64 at finalisation, rounded once to fp32, stored in fragment order and streamed from L2.
-//     Its real output columns number exactly n_fft: re[0 .. n_fft/2] and im[1 .. n_fft/2 - 1].  A wave holds re and im of the SAME 32 bins in
-//     two accumulators with matching positions, so the magnitude needs no exchange; re[n_fft/2] rides in the (otherwise zero) im slot of bin 0.
+// The STFT is the shared contraction of stft_core.h: the samples of a tile of frames staged once into one LDS slab —
+// samples before 0 and past wav_lens[b] read as zero, which IS the reference's constant padding — and contracted against the windowed DFT
+// basis on v_mfma_f32_32x32x2_f32.  What this unit adds:
+//   * re and im of the same 32 bins sit in matching accumulator positions, so the magnitude needs no exchange.
 //   * |X| stays in accumulator layout and is at once the B operand of the mel projection D2[mel 32][frame 32] += M[mel][bin 2] * |X|[bin 2][frame]:
 //     register r of the two lane halves holds bins b and b + 4, which is the k pair of one MFMA; the mel pack is stored in that order.
-//   * every frame is summed in the same order whatever tile it falls into (k in order, bin blocks in order): an utterance alone is
-//     bit-identical to the same utterance inside any batch, at either tile size.
-//   * a wave owns 32 frames of the tile; the slab is placed with a skew (sample a at dword a + (a >> ps)) so that the 32 rows of a fragment,
-//     hop samples apart, fall into different banks (melspec_conflict_degree enumerates the read).
+//   * a wave owns 32 frames of the tile; bin blocks are projected in order, so an utterance alone is bit-identical to the same utterance
+//     inside any batch, at either tile size.
 #include "ctx.h"
 
 namespace dtts {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16m;
-
 template <int WT>
 __global__ __launch_bounds__(64 * WT) void melspec_kernel(const MelspecParams p) {
     extern __shared__ __attribute__((aligned(16))) float slab[];
-    constexpr int THREADS = 64 * WT;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, fi = lane & 31, hf = lane >> 5;
-    const int b = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
-    int len = p.wav_lens ? p.wav_lens[b] : p.wav_ld;
-    len = len < 0 ? 0 : (len > p.wav_ld ? p.wav_ld : len);
-    const int T = 1 + len / p.hop;
+    const int b = blockIdx.x / p.g.ntile, tile = blockIdx.x % p.g.ntile;
+    const int len = stft_len(p.wav_lens, b, p.wav_ld);
+    const int T = 1 + len / p.g.hop;
     if (tile == 0 && tid == 0 && p.mel_lens) p.mel_lens[b] = T;
-    const int f0 = tile * p.tt;
+    const int f0 = tile * p.g.tt;
     if (f0 >= T) return;
-    const int nf = T - f0 < p.tt ? T - f0 : p.tt;   // frames of this tile
-    const int ps = p.ps;
-
-    // ---- the tile's samples: global sample g0 + q -> slab position q; outside [0, len) the buffer resource returns zero
-    {
-        const int P = (nf - 1) * p.hop + p.n_fft;
-        const int g0 = f0 * p.hop - p.n_fft / 2;
-        const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.wav + (size_t)b * p.wav_ld), 0, len * 4, 0x00020000);
-        for (int q = tid; q < P; q += THREADS) {
-            const unsigned v = __builtin_amdgcn_raw_buffer_load_b32(rs, (g0 + q) * 4, 0, 0);   // (a negative offset is a huge unsigned one)
-            slab[q + (q >> ps)] = __builtin_bit_cast(float, v);
-        }
-    }
+    const int nf = T - f0 < p.g.tt ? T - f0 : p.g.tt;   // frames of this tile
+    const float* const sig[1] = {p.wav + (size_t)b * p.wav_ld};
+    stft_stage<64 * WT>(slab, 0, sig, len, f0, nf, p.g, tid, [](int g) { return g; });
     __syncthreads();
     if (wv * 32 >= nf) return;   // (no barrier below)
     const int f = wv * 32 + fi;
     const bool live = f < nf;
-    const int abase = (live ? f : wv * 32) * p.hop + hf;   // a dead lane recomputes the wave's first frame and stores nothing
+    const int abase = (live ? f : wv * 32) * p.g.hop + hf;   // a dead lane recomputes the wave's first frame and stores nothing
 
-    const int NB = p.n_fft / 64, SG = p.n_fft / 32, NM = (p.n_mels + 31) / 32;
-    f32x16m macc[4];
+    const int NB = p.g.n_fft / 64, NM = (p.n_mels + 31) / 32;
+    stft_f32x16 macc[4];
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) macc[mt][r] = 0.f;
 
-    // one super-group = 16 MFMA steps = 32 samples: eight 16-byte fragments per lane (re of steps 0-3, .., 12-15, then im).  Two register
-    // buffers take turns: while one is contracted (2048 MFMA cycles) the next super-group — of the next bin block behind this one's last — is on
-    // its way from L2.  The launcher hands out a multiple of four super-groups per bin block (sg_lo a multiple of four too), so the turns need no copy.
-    auto fetch = [&](float4 (&d)[8], int c, int sg) {
-        const float4* s = p.basis + ((size_t)(c * SG + sg) * 8) * 64 + lane;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) d[q] = s[q * 64];
-        __builtin_amdgcn_sched_barrier(0);   // the loads go out before the contraction they hide behind
-    };
-    float4 fa[8], fb[8];
-    fetch(fa, 0, p.sg_lo);
-#pragma unroll 1
-    for (int c = 0; c < NB; ++c) {
-        // Short fp32 chains joined in fp64: every MELSPEC_CHUNK MFMA steps (2 MELSPEC_CHUNK samples) start from zero and their sum goes into an
-        // fp64 accumulator (exact next to fp32), rounded to fp32 once per bin block.  An fp32 chain rounds every step at the size of its
-        // PARTIAL sum, which next to a strong harmonic or an offset is tens of times the final value; a chain of a few
-        // samples never gets there.  The order stays fixed: chunks in k order.
-        double dre[16], dim[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dre[r] = dim[r] = 0.0;
-        auto contract = [&](const float4 (&w)[8], int sg) {
-            const int a0 = abase + 32 * sg;
-#pragma unroll
-            for (int ch = 0; ch < 16 / MELSPEC_CHUNK; ++ch) {
-                f32x16m re, im;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) re[r] = im[r] = 0.f;
-#pragma unroll
-                for (int jj = 0; jj < MELSPEC_CHUNK; ++jj) {
-                    const int j = ch * MELSPEC_CHUNK + jj, a = a0 + 2 * j;
-                    const float x = slab[a + (a >> ps)];
-                    re = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j >> 2][j & 3], x, re, 0, 0, 0);
-                    im = __builtin_amdgcn_mfma_f32_32x32x2f32(w[4 + (j >> 2)][j & 3], x, im, 0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    dre[r] += (double)re[r];
-                    dim[r] += (double)im[r];
-                }
-            }
-        };
-#pragma unroll 1
-        for (int sg = p.sg_lo; sg < p.sg_hi; sg += 4) {
-            fetch(fb, c, sg + 1);
-            contract(fa, sg);
-            fetch(fa, c, sg + 2);
-            contract(fb, sg + 1);
-            fetch(fb, c, sg + 3);
-            contract(fa, sg + 2);
-            const bool wrap = sg + 4 == p.sg_hi;
-            fetch(fa, wrap ? (c + 1 < NB ? c + 1 : c) : c, wrap ? p.sg_lo : sg + 4);
-            contract(fb, sg + 3);
-        }
-        f32x16m re, im;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            re[r] = (float)dre[r];
-            im[r] = (float)dim[r];
-        }
+    stft_contract(p.g.basis, p.g.n_fft / 32, p.g.sg_lo, p.g.sg_hi, 0, NB, slab, abase, p.g.ps, lane, [&](int c, stft_f32x16 re, stft_f32x16 im) {
         // ---- magnitudes in place, then straight into the mel projection
         float mag[16];
 #pragma unroll
@@ -142,7 +65,7 @@ __global__ __launch_bounds__(64 * WT) void melspec_kernel(const MelspecParams p)
                 }
             }
         }
-    }
+    });
 
     // ---- log10(max(eps, mel)) rows [T][n_mels]; the logarithm in fp64 (80 per frame against 2 n_fft^2 FLOP), rounded once
     if (live) {
@@ -253,38 +176,34 @@ std::vector<float> melspec_pack_mel(int n_fft, int n_mels, const std::vector<flo
     return out;
 }
 
+SgRange window_support(const std::vector<float>& window) {
+    int lo = (int)window.size(), hi = -1;
+    for (int k = 0; k < (int)window.size(); ++k)
+        if (window[k] != 0.f) {
+            lo = std::min(lo, k);
+            hi = k;
+        }
+    return SgRange{lo / 128 * 4, (hi + 128) / 128 * 4};
+}
+
+int check_wav_ld(dtts_ctx* h, const char* me, int wav_ld, int n_fft) {
+    if (stft_wav_ld_ok(wav_ld, n_fft)) return DTTS_OK;
+    return fail(h, DTTS_E_INVAL, "%s: wav_ld = %d samples (supported: 0 .. 2^29 - 2^16)", me, wav_ld);
+}
+
 template <int WT>
 static hipError_t melspec_launch_cfg(MelspecParams p, hipStream_t stream) {
-    p.tt = melspec_tile_frames(WT, p.hop, p.n_fft, p.ps);
-    const int t_cap = 1 + p.wav_ld / p.hop;
-    p.ntile = (t_cap + p.tt - 1) / p.tt;
-    const size_t lds = melspec_slab_dwords(p.tt, p.hop, p.n_fft, p.ps) * 4;
-    if (lds > (size_t)MELSPEC_LDS_BYTES || (long long)p.ntile * p.B > INT_MAX) return hipErrorInvalidValue;
-    auto kern = melspec_kernel<WT>;
-    static bool configured_dev[64] = {};   // per device: hipFuncSetAttribute is per device
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    bool& configured = configured_dev[cur_dev & 63];
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, MELSPEC_LDS_BYTES);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(p.ntile * p.B)), dim3(64 * WT), lds, stream, p);
+    const size_t lds = stft_set_tile(p.g, WT, p.wav_ld);
+    if (lds > (size_t)MELSPEC_LDS_BYTES || (long long)p.g.ntile * p.B > INT_MAX) return hipErrorInvalidValue;
+    if (hipError_t e = stft_lds_limit<melspec_kernel<WT>>()) return e;
+    hipLaunchKernelGGL(melspec_kernel<WT>, dim3((unsigned)(p.g.ntile * p.B)), dim3(64 * WT), lds, stream, p);
     return hipGetLastError();
 }
 
-// The tile rule: four waves x 32 frames; while those tiles would leave more than half of the CUs without one (B = 1), two waves x 32 frames
-// (two workgroups share a CU).  Where the LDS holds fewer frames (long hops) a tile carries what fits.
 hipError_t melspec_launch(const MelspecParams& p, int n_cu, hipStream_t stream) {
-    if (!melspec_supported(p.n_fft, p.hop, p.n_fft, p.n_mels)) return hipErrorInvalidValue;
-    if (p.B < 1 || p.wav_ld < 0 || p.sg_lo < 0 || p.sg_hi > p.n_fft / 32 || p.sg_lo >= p.sg_hi || (p.sg_lo & 3) || (p.sg_hi & 3) || p.ps < 1) return hipErrorInvalidValue;
-    // 32-bit byte offsets inside an utterance's buffer resource: a tile reaches at most one slab past the utterance's end
-    if (((long long)p.wav_ld + MELSPEC_LDS_BYTES / 4 + p.n_fft) * 4 >= (1LL << 31)) return hipErrorInvalidValue;
-    if (p.mel_cap < 1 + p.wav_ld / p.hop) return hipErrorInvalidValue;
-    const int tt4 = melspec_tile_frames(4, p.hop, p.n_fft, p.ps);
-    const long long tiles4 = (long long)p.B * ((1 + p.wav_ld / p.hop + tt4 - 1) / tt4);
-    return 2 * tiles4 <= n_cu ? melspec_launch_cfg<2>(p, stream) : melspec_launch_cfg<4>(p, stream);
+    if (!stft_geom_ok(p.g, p.B, p.wav_ld) || p.n_mels < 1 || p.n_mels > MELSPEC_MAX_MELS) return hipErrorInvalidValue;
+    if (p.mel_cap < 1 + p.wav_ld / p.g.hop) return hipErrorInvalidValue;
+    return stft_tile_waves(p.B, p.wav_ld, p.g.hop, p.g.n_fft, p.g.ps, n_cu) == 2 ? melspec_launch_cfg<2>(p, stream) : melspec_launch_cfg<4>(p, stream);
 }
 
 // ---- dtts_finalize_weights(DTTS_PART_MELSPEC): "melspec.mel_basis" [n_mels][n_fft / 2 + 1] + "melspec.window" [win_length] -> the plan.
@@ -307,13 +226,10 @@ int build_melspec(dtts_ctx* h) {
     if (!basis || !melpack) return fail(h, DTTS_E_NOMEM, "dtts_finalize_weights(DTTS_PART_MELSPEC): device allocation failed");
     // the samples a zero of the centred window removes from the contraction (win_length < n_fft), in whole FOURS of 32-sample super-groups
     const int lpad = (n_fft - win) / 2;
-    h->ms_basis = basis;
+    h->ms = StftBasisPlan{basis, n_fft, lpad / 128 * 4, (lpad + win + 127) / 128 * 4};
     h->ms_melpack = melpack;
-    h->ms_n_fft = n_fft;
     h->ms_n_mels = n_mels;
     h->ms_win = win;
-    h->ms_sg_lo = lpad / 128 * 4;
-    h->ms_sg_hi = (lpad + win + 127) / 128 * 4;
     h->ms_skew_hop = 0;
     h->melspec_ready = true;
     return DTTS_OK;
@@ -326,10 +242,9 @@ int melspec_forward(dtts_ctx* h, const dtts_melspec_args* a, hipStream_t stream)
         return fail(h, DTTS_E_INVAL, "%s: argument block of size = %d bytes, this library's is %d", me, a->size, (int)sizeof(dtts_melspec_args));
     if (!h->melspec_ready) return fail(h, DTTS_E_STATE, "%s before dtts_finalize_weights(DTTS_PART_MELSPEC)", me);
     std::string why;
-    if (!melspec_supported(h->ms_n_fft, a->hop, h->ms_win, h->ms_n_mels, &why)) return fail(h, DTTS_E_INVAL, "%s: unsupported %s", me, why.c_str());
+    if (!melspec_supported(h->ms.n_fft, a->hop, h->ms_win, h->ms_n_mels, &why)) return fail(h, DTTS_E_INVAL, "%s: unsupported %s", me, why.c_str());
     if (a->B <= 0) return fail(h, DTTS_E_INVAL, "%s: B = %d", me, a->B);
-    if (a->wav_ld < 0 || ((long long)a->wav_ld + MELSPEC_LDS_BYTES / 4 + h->ms_n_fft) * 4 >= (1LL << 31))
-        return fail(h, DTTS_E_INVAL, "%s: wav_ld = %d samples (supported: 0 .. 2^29 - 2^16)", me, a->wav_ld);
+    if (int e = check_wav_ld(h, me, a->wav_ld, h->ms.n_fft)) return e;
     if (a->mel_cap < 1 + a->wav_ld / a->hop)
         return fail(h, DTTS_E_INVAL, "%s: mel_cap = %d rows, wav_ld = %d samples at hop %d give %d", me, a->mel_cap, a->wav_ld, a->hop, 1 + a->wav_ld / a->hop);
     if (!(a->eps > 0.f) || !(a->eps < 3.0e38f)) return fail(h, DTTS_E_INVAL, "%s: eps = %g (must be positive and finite)", me, (double)a->eps);
@@ -344,17 +259,12 @@ int melspec_forward(dtts_ctx* h, const dtts_melspec_args* a, hipStream_t stream)
     p.mel = a->mel_dev;
     p.mel_lens = a->mel_lens_dev;
     p.lin = a->lin_dev;
-    p.basis = (const float4*)h->ms_basis;
     p.melpack = (const float4*)h->ms_melpack;
+    p.g = stft_geom(h->ms, a->hop, h->ms_skew);
     p.B = a->B;
     p.wav_ld = a->wav_ld;
     p.mel_cap = a->mel_cap;
-    p.hop = a->hop;
-    p.n_fft = h->ms_n_fft;
     p.n_mels = h->ms_n_mels;
-    p.sg_lo = h->ms_sg_lo;
-    p.sg_hi = h->ms_sg_hi;
-    p.ps = h->ms_skew;
     p.eps = a->eps;
     LAUNCH(melspec_launch(p, h->n_cu, stream));
     return DTTS_OK;

@@ -3,7 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "melspec.h"
+#include "stft_core.h"
 
 namespace dtts {
 
@@ -17,14 +17,10 @@ struct StftParams {
     const float* x;          // [B][wav_ld]
     const float* y;          // [B][wav_ld]
     const int* lens;         // [B] samples, or null = wav_ld
-    const float4* basis;     // melspec_pack_basis of the window, zero padded and centred to n_fft
     double* part;            // [B][ntile][3]: sum d^2, sum p_y, sum |log m_y - log m_x| of one tile
     float* mag;              // [2][B][mag_cap][n_fft / 2 + 1] out, or null: the clamped magnitudes of x (0) and y (1)
-    int B, wav_ld, mag_cap, hop, n_fft;
-    int sg_lo, sg_hi;        // as MelspecParams
-    int tt;                  // frame pairs per tile (<= 16 * STFT_WAVES)
-    int ntile;               // tiles per utterance at wav_ld samples
-    int ps;                  // slab skew, as MelspecParams
+    StftGeom g;              // the basis of the window, zero padded and centred to n_fft; tt = frame PAIRS per tile (<= 16 * STFT_WAVES)
+    int B, wav_ld, mag_cap;
     int ybase;               // LDS dword at which the slab of y starts
     int red;                 // LDS dword (even) of the waves' fp64 triples, behind slab y: set by stft_launch
 };

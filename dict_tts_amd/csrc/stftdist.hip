@@ -4,8 +4,7 @@
 //   m = sqrt(max(re^2 + im^2, 1e-7)) of torch.stft(sig, n_fft, hop, win, hann_window(win))   (center=True, pad_mode='reflect')
 //   sums[0] = sum (m_y - m_x)^2,  sums[1] = sum m_y^2,  sums[2] = sum |log m_y - log m_x|     over the T_b (n_fft / 2 + 1) values of the utterance.
 //
-// The contraction is melspec.hip's: v_mfma_f32_32x32x2_f32 against the windowed DFT basis of melspec_pack_basis in
-// fragment order, fp32 chains of MELSPEC_CHUNK steps joined in fp64, re[n_fft / 2] in the im slot of bin 0.  What differs (section 3.7):
+// The STFT is the shared contraction of stft_core.h.  What this unit adds (section 3.7):
 //   * the 32 frame columns of the MFMA hold the PAIR: columns 0 - 15 = frames f .. f + 15 of x, columns 16 - 31 = the same frames of y, read
 //     from two slabs of one LDS tile.  A basis fragment fetched from L2 serves both signals, and m_x / m_y of one (bin, frame) sit in lanes l
 //     and l ^ 16 of the same accumulator register: one exchange per register per bin block brings them together.
@@ -18,41 +17,25 @@
 
 namespace dtts {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16s;
-
 template <int WT>
 __global__ __launch_bounds__(64 * WT) void stftdist_kernel(const StftParams p) {
     extern __shared__ __attribute__((aligned(16))) float slab[];
-    constexpr int THREADS = 64 * WT;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, fi = lane & 31, hf = lane >> 5, sig = fi >> 4, fr = fi & 15;
-    const int b = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
-    int len = p.lens ? p.lens[b] : p.wav_ld;
-    len = len < 0 ? 0 : (len > p.wav_ld ? p.wav_ld : len);
-    if (len <= p.n_fft / 2) return;   // torch.stft refuses it (the mirror would leave the signal): count 0, the reduction writes zeros
-    const int T = 1 + len / p.hop;
-    const int f0 = tile * p.tt;
-    if (f0 >= T) return;              // (whole workgroup, before any barrier; the reduction reads only the tiles below T)
-    const int nf = T - f0 < p.tt ? T - f0 : p.tt;   // frame pairs of this tile
-    const int ps = p.ps;
+    const int b = blockIdx.x / p.g.ntile, tile = blockIdx.x % p.g.ntile;
+    const int len = stft_len(p.lens, b, p.wav_ld);
+    if (len <= p.g.n_fft / 2) return;   // torch.stft refuses it (the mirror would leave the signal): count 0, the reduction writes zeros
+    const int T = 1 + len / p.g.hop;
+    const int f0 = tile * p.g.tt;
+    if (f0 >= T) return;                // (whole workgroup, before any barrier; the reduction reads only the tiles below T)
+    const int nf = T - f0 < p.g.tt ? T - f0 : p.g.tt;   // frame pairs of this tile
 
-    // ---- the tile's samples of both signals: global sample g0 + q, mirrored at 0 and at len - 1, -> slab position q.  len > n_fft / 2 keeps
-    // every mirrored index inside [0, len); the buffer resource would return zero for one that is not
-    {
-        const int P = (nf - 1) * p.hop + p.n_fft;
-        const int g0 = f0 * p.hop - p.n_fft / 2;
-        const auto rx = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + (size_t)b * p.wav_ld), 0, len * 4, 0x00020000);
-        const auto ry = __builtin_amdgcn_make_buffer_rsrc((void*)(p.y + (size_t)b * p.wav_ld), 0, len * 4, 0x00020000);
-        for (int q = tid; q < P; q += THREADS) {
-            int g = g0 + q;
-            g = g < 0 ? -g : g;
-            g = g >= len ? 2 * (len - 1) - g : g;
-            const unsigned vx = __builtin_amdgcn_raw_buffer_load_b32(rx, g * 4, 0, 0);
-            const unsigned vy = __builtin_amdgcn_raw_buffer_load_b32(ry, g * 4, 0, 0);
-            const int d = q + (q >> ps);
-            slab[d] = __builtin_bit_cast(float, vx);
-            slab[p.ybase + d] = __builtin_bit_cast(float, vy);
-        }
-    }
+    // ---- the tile's samples of both signals, mirrored at 0 and at len - 1.  len > n_fft / 2 keeps every mirrored index inside [0, len); the
+    // buffer resource would return zero for one that is not
+    const float* const xy[2] = {p.x + (size_t)b * p.wav_ld, p.y + (size_t)b * p.wav_ld};
+    stft_stage<64 * WT>(slab, p.ybase, xy, len, f0, nf, p.g, tid, [len](int g) {
+        g = g < 0 ? -g : g;
+        return g >= len ? 2 * (len - 1) - g : g;
+    });
     __syncthreads();
 
     double s_d2 = 0.0, s_py = 0.0, s_lg = 0.0;
@@ -60,75 +43,25 @@ __global__ __launch_bounds__(64 * WT) void stftdist_kernel(const StftParams p) {
         const int f = wv * 16 + fr;
         const bool live = f < nf;   // the same for lanes l and l ^ 16
         const int sbase = sig ? p.ybase : 0;
-        const int abase = (live ? f : wv * 16) * p.hop + hf;   // a dead column recomputes the wave's first frame and contributes nothing
-        const int NB = p.n_fft / 64, SG = p.n_fft / 32, nbins = p.n_fft / 2 + 1;
+        const int abase = (live ? f : wv * 16) * p.g.hop + hf;   // a dead column recomputes the wave's first frame and contributes nothing
+        const int nbins = p.g.n_fft / 2 + 1;
         float* mrow = p.mag && live ? p.mag + (((size_t)sig * p.B + b) * p.mag_cap + f0 + f) * nbins : nullptr;
 
-        // the basis stream of melspec_kernel: two register buffers of one 32-sample super-group (eight 16-byte fragments per lane) take turns
-        auto fetch = [&](float4 (&d)[8], int c, int sg) {
-            const float4* s = p.basis + ((size_t)(c * SG + sg) * 8) * 64 + lane;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) d[q] = s[q * 64];
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        float4 fa[8], fb[8];
-        fetch(fa, 0, p.sg_lo);
-#pragma unroll 1
-        for (int c = 0; c < NB; ++c) {
-            double dre[16], dim[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) dre[r] = dim[r] = 0.0;
-            auto contract = [&](const float4 (&w)[8], int sg) {
-                const int a0 = abase + 32 * sg;
-#pragma unroll
-                for (int ch = 0; ch < 16 / MELSPEC_CHUNK; ++ch) {
-                    f32x16s re, im;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) re[r] = im[r] = 0.f;
-#pragma unroll
-                    for (int jj = 0; jj < MELSPEC_CHUNK; ++jj) {
-                        const int j = ch * MELSPEC_CHUNK + jj, a = a0 + 2 * j;
-                        const float x = slab[sbase + a + (a >> ps)];
-                        re = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j >> 2][j & 3], x, re, 0, 0, 0);
-                        im = __builtin_amdgcn_mfma_f32_32x32x2f32(w[4 + (j >> 2)][j & 3], x, im, 0, 0, 0);
-                    }
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        dre[r] += (double)re[r];
-                        dim[r] += (double)im[r];
-                    }
-                }
-            };
-#pragma unroll 1
-            for (int sg = p.sg_lo; sg < p.sg_hi; sg += 4) {
-                fetch(fb, c, sg + 1);
-                contract(fa, sg);
-                fetch(fa, c, sg + 2);
-                contract(fb, sg + 1);
-                fetch(fb, c, sg + 3);
-                contract(fa, sg + 2);
-                const bool wrap = sg + 4 == p.sg_hi;
-                fetch(fa, wrap ? (c + 1 < NB ? c + 1 : c) : c, wrap ? p.sg_lo : sg + 4);
-                contract(fb, sg + 3);
-            }
+        stft_contract(p.g.basis, p.g.n_fft / 32, p.g.sg_lo, p.g.sg_hi, 0, p.g.n_fft / 64, slab + sbase, abase, p.g.ps, lane, [&](int c, stft_f32x16 re, stft_f32x16 im) {
             // ---- clamped powers of this lane's signal; bin 0 is real and its im slot carried re[n_fft / 2], a bin of its own
             float pw[16];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float re = (float)dre[r], im = (float)dim[r];
-                pw[r] = __builtin_fmaxf(__builtin_fmaf(re, re, __fmul_rn(im, im)), STFT_CLAMP);
-            }
+            for (int r = 0; r < 16; ++r) pw[r] = __builtin_fmaxf(__builtin_fmaf(re[r], re[r], __fmul_rn(im[r], im[r])), STFT_CLAMP);
             float pn = STFT_CLAMP;
             const bool edge = c == 0 && hf == 0;
             if (edge) {
-                const float re = (float)dre[0], im = (float)dim[0];
-                pw[0] = __builtin_fmaxf(__fmul_rn(re, re), STFT_CLAMP);
-                pn = __builtin_fmaxf(__fmul_rn(im, im), STFT_CLAMP);
+                pw[0] = __builtin_fmaxf(__fmul_rn(re[0], re[0]), STFT_CLAMP);
+                pn = __builtin_fmaxf(__fmul_rn(im[0], im[0]), STFT_CLAMP);
             }
             if (mrow) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) mrow[32 * c + 8 * (r >> 2) + 4 * hf + (r & 3)] = __builtin_sqrtf(pw[r]);
-                if (edge) mrow[p.n_fft / 2] = __builtin_sqrtf(pn);
+                if (edge) mrow[p.g.n_fft / 2] = __builtin_sqrtf(pn);
             }
             // ---- the pair: lane l (x) takes p_y from lane l ^ 16.  One fp32 logarithm per bin: |log m_y - log m_x| = |log(p_y / p_x)| / 2
             float a_d2 = 0.f, a_py = 0.f, a_lg = 0.f;
@@ -151,7 +84,7 @@ __global__ __launch_bounds__(64 * WT) void stftdist_kernel(const StftParams p) {
             s_d2 += (double)a_d2;
             s_py += (double)a_py;
             s_lg += (double)a_lg;
-        }
+        });
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) {   // a butterfly: every lane ends with the same sum, in an order that depends on nothing
             s_d2 += __shfl_xor(s_d2, o);
@@ -171,7 +104,7 @@ __global__ __launch_bounds__(64 * WT) void stftdist_kernel(const StftParams p) {
         double s = 0.0;
 #pragma unroll
         for (int w = 0; w < WT; ++w) s += red[3 * w + tid];
-        p.part[((size_t)b * p.ntile + tile) * 3 + tid] = s;
+        p.part[((size_t)b * p.g.ntile + tile) * 3 + tid] = s;
     }
 }
 
@@ -179,8 +112,7 @@ __global__ __launch_bounds__(64 * WT) void stftdist_kernel(const StftParams p) {
 __global__ void stft_reduce_kernel(const StftReduceParams p) {
     const int i = blockIdx.x, b = blockIdx.y * blockDim.x + threadIdx.x;
     if (b >= p.B) return;
-    int len = p.lens ? p.lens[b] : p.wav_ld;
-    len = len < 0 ? 0 : (len > p.wav_ld ? p.wav_ld : len);
+    const int len = stft_len(p.lens, b, p.wav_ld);
     double s[3] = {0.0, 0.0, 0.0};
     long long count = 0;
     if (len > p.n_fft[i] / 2) {
@@ -226,26 +158,16 @@ StftLayout stft_layout(int hop, int n_fft) {
 }
 
 hipError_t stft_launch(StftParams p, hipStream_t stream) {
-    if (!melspec_supported(p.n_fft, p.hop, p.n_fft, 1)) return hipErrorInvalidValue;
-    if (p.B < 1 || p.wav_ld < 0 || p.sg_lo < 0 || p.sg_hi > p.n_fft / 32 || p.sg_lo >= p.sg_hi || (p.sg_lo & 3) || (p.sg_hi & 3) || p.ps < 1) return hipErrorInvalidValue;
-    if (((long long)p.wav_ld + MELSPEC_LDS_BYTES / 4 + p.n_fft) * 4 >= (1LL << 31)) return hipErrorInvalidValue;   // 32-bit byte offsets of the buffer loads
-    if (p.mag && p.mag_cap < 1 + p.wav_ld / p.hop) return hipErrorInvalidValue;
-    const size_t S = melspec_slab_dwords(p.tt, p.hop, p.n_fft, p.ps);
-    const size_t lds = stft_lds_bytes(p.tt, p.hop, p.n_fft, p.ps, p.ybase);
-    if (p.tt < 1 || p.tt > 16 * STFT_WAVES || (size_t)p.ybase < S || lds > (size_t)MELSPEC_LDS_BYTES) return hipErrorInvalidValue;
-    if (p.ntile != (1 + p.wav_ld / p.hop + p.tt - 1) / p.tt || (long long)p.ntile * p.B > INT_MAX) return hipErrorInvalidValue;
+    const StftGeom& g = p.g;
+    if (!stft_geom_ok(g, p.B, p.wav_ld)) return hipErrorInvalidValue;
+    if (p.mag && p.mag_cap < 1 + p.wav_ld / g.hop) return hipErrorInvalidValue;
+    const size_t S = melspec_slab_dwords(g.tt, g.hop, g.n_fft, g.ps);
+    const size_t lds = stft_lds_bytes(g.tt, g.hop, g.n_fft, g.ps, p.ybase);
+    if (g.tt < 1 || g.tt > 16 * STFT_WAVES || (size_t)p.ybase < S || lds > (size_t)MELSPEC_LDS_BYTES) return hipErrorInvalidValue;
+    if (g.ntile != (1 + p.wav_ld / g.hop + g.tt - 1) / g.tt || (long long)g.ntile * p.B > INT_MAX) return hipErrorInvalidValue;
     p.red = (int)(((size_t)p.ybase + S + 1) & ~(size_t)1);
-    auto kern = stftdist_kernel<STFT_WAVES>;
-    static bool configured_dev[64] = {};   // per device: hipFuncSetAttribute is per device
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    bool& configured = configured_dev[cur_dev & 63];
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, MELSPEC_LDS_BYTES);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(p.ntile * p.B)), dim3(64 * STFT_WAVES), lds, stream, p);
+    if (hipError_t e = stft_lds_limit<stftdist_kernel<STFT_WAVES>>()) return e;
+    hipLaunchKernelGGL(stftdist_kernel<STFT_WAVES>, dim3((unsigned)(g.ntile * p.B)), dim3(64 * STFT_WAVES), lds, stream, p);
     return hipGetLastError();
 }
 
@@ -269,19 +191,11 @@ int build_stft(dtts_ctx* h) {
         const int n_fft = (int)std::min<int64_t>(wn.shape[0], INT_MAX);
         std::string why;
         if (!melspec_supported(n_fft, n_fft, n_fft, 1, &why)) return fail(h, DTTS_E_INVAL, "%s: stft.%d.window: unsupported %s", me, i, why.c_str());
-        int lo = n_fft, hi = -1;   // the non-zero support
-        for (int k = 0; k < n_fft; ++k)
-            if (wn.f[k] != 0.f) {
-                lo = std::min(lo, k);
-                hi = k;
-            }
-        if (hi < 0) return fail(h, DTTS_E_INVAL, "%s: stft.%d.window is all zero", me, i);
+        const SgRange sup = window_support(wn.f);
+        if (!sup.hi) return fail(h, DTTS_E_INVAL, "%s: stft.%d.window is all zero", me, i);
         dtts_ctx::StftPlan pl;
-        pl.n_fft = n_fft;
-        pl.sg_lo = lo / 128 * 4;           // whole FOURS of 32-sample super-groups, as the contraction walks them
-        pl.sg_hi = (hi + 128) / 128 * 4;
-        pl.basis = upload(h, melspec_pack_basis(n_fft, wn.f));
-        if (!pl.basis) return fail(h, DTTS_E_NOMEM, "%s: device allocation failed", me);
+        pl.core = StftBasisPlan{upload(h, melspec_pack_basis(n_fft, wn.f)), n_fft, sup.lo, sup.hi};
+        if (!pl.core.basis) return fail(h, DTTS_E_NOMEM, "%s: device allocation failed", me);
         plans.push_back(pl);
     }
     if (plans.empty()) return fail(h, DTTS_E_NOENT, "%s: missing weight stft.0.window", me);
@@ -298,10 +212,9 @@ int stft_forward(dtts_ctx* h, const dtts_stft_args* a, hipStream_t stream) {
     if (a->n_res < 1 || a->n_res > (int)h->stft_plans.size())
         return fail(h, DTTS_E_INVAL, "%s: n_res = %d (this context has %d plans)", me, a->n_res, (int)h->stft_plans.size());
     if (a->B <= 0) return fail(h, DTTS_E_INVAL, "%s: B = %d", me, a->B);
-    if (a->wav_ld < 0 || ((long long)a->wav_ld + MELSPEC_LDS_BYTES / 4 + 2048) * 4 >= (1LL << 31))
-        return fail(h, DTTS_E_INVAL, "%s: wav_ld = %d samples (supported: 0 .. 2^29 - 2^16)", me, a->wav_ld);
+    if (int e = check_wav_ld(h, me, a->wav_ld, 2048)) return e;   // (the largest n_fft: one bound for every resolution)
     for (int i = 0; i < a->n_res; ++i) {
-        const int n_fft = h->stft_plans[i].n_fft;
+        const int n_fft = h->stft_plans[i].core.n_fft;
         if (a->hop[i] < 1 || a->hop[i] > n_fft)
             return fail(h, DTTS_E_INVAL, "%s: hop[%d] = %d (supported: 1 .. n_fft = %d)", me, i, a->hop[i], n_fft);
         if (a->mag_dev && a->mag_cap < 1 + a->wav_ld / a->hop[i])
@@ -316,7 +229,7 @@ int stft_forward(dtts_ctx* h, const dtts_stft_args* a, hipStream_t stream) {
     for (int i = 0; i < a->n_res; ++i) {
         dtts_ctx::StftPlan& pl = h->stft_plans[i];
         if (pl.layout_hop != a->hop[i]) {
-            const StftLayout l = stft_layout(a->hop[i], pl.n_fft);
+            const StftLayout l = stft_layout(a->hop[i], pl.core.n_fft);
             pl.ps = l.ps;
             pl.tt = l.tt;
             pl.ybase = l.ybase;
@@ -327,30 +240,25 @@ int stft_forward(dtts_ctx* h, const dtts_stft_args* a, hipStream_t stream) {
         p.x = a->x_dev;
         p.y = a->y_dev;
         p.lens = a->lens_dev;
-        p.basis = (const float4*)pl.basis;
         p.mag = a->mag_dev ? a->mag_dev + mag_off : nullptr;
         p.B = a->B;
         p.wav_ld = a->wav_ld;
         p.mag_cap = a->mag_cap;
-        p.hop = a->hop[i];
-        p.n_fft = pl.n_fft;
-        p.sg_lo = pl.sg_lo;
-        p.sg_hi = pl.sg_hi;
-        p.tt = pl.tt;
-        p.ntile = (1 + a->wav_ld / a->hop[i] + pl.tt - 1) / pl.tt;
-        p.ps = pl.ps;
+        p.g = stft_geom(pl.core, a->hop[i], pl.ps);
+        p.g.tt = pl.tt;
+        p.g.ntile = (1 + a->wav_ld / a->hop[i] + pl.tt - 1) / pl.tt;
         p.ybase = pl.ybase;
-        if ((long long)p.ntile * a->B > INT_MAX) return fail(h, DTTS_E_INVAL, "%s: B = %d utterances of %d tiles", me, a->B, p.ntile);
-        mag_off += (size_t)2 * a->B * (a->mag_dev ? a->mag_cap : 0) * (pl.n_fft / 2 + 1);
-        ws += ((size_t)a->B * p.ntile * 3 * sizeof(double) + 255) & ~(size_t)255;
-        rp.hop[i] = p.hop;
-        rp.n_fft[i] = p.n_fft;
-        rp.tt[i] = p.tt;
-        rp.ntile[i] = p.ntile;
+        if ((long long)p.g.ntile * a->B > INT_MAX) return fail(h, DTTS_E_INVAL, "%s: B = %d utterances of %d tiles", me, a->B, p.g.ntile);
+        mag_off += (size_t)2 * a->B * (a->mag_dev ? a->mag_cap : 0) * (p.g.n_fft / 2 + 1);
+        ws += ((size_t)a->B * p.g.ntile * 3 * sizeof(double) + 255) & ~(size_t)255;
+        rp.hop[i] = p.g.hop;
+        rp.n_fft[i] = p.g.n_fft;
+        rp.tt[i] = p.g.tt;
+        rp.ntile[i] = p.g.ntile;
     }
     HIPCHK(h->a_stft.reserve(ws, stream));
     for (int i = 0; i < a->n_res; ++i) {
-        sp[i].part = h->a_stft.alloc<double>((size_t)a->B * sp[i].ntile * 3);
+        sp[i].part = h->a_stft.alloc<double>((size_t)a->B * sp[i].g.ntile * 3);
         if (!sp[i].part) return fail(h, DTTS_E_NOMEM, "%s: workspace", me);
         rp.part[i] = sp[i].part;
     }

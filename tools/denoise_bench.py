@@ -6,7 +6,7 @@ call by call; device time by an event pair around each call, median of --reps af
 the filter's two halves alone (Spectral.stft / Spectral.istft) are timed alongside.  Also prints both pipelines' error against float64 on
 utterance 0 in the units of tests/test_spectral_gpu.py.  No gate: these are figures for LABNOTES.md.
 
-    python tools/denoise_bench.py [--batch 60] [--frames 700] [--v 0.1] [--reps 20] [--warmup 5]
+    python tools/denoise_bench.py [--batch 60] [--frames 700] [--v 0.1] [--reps 20] [--warmup 5] [--lib path/to/libdicttts_hip.so]
 """
 import argparse
 import json
@@ -19,7 +19,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 
-from dict_tts_amd import synth, vocoder
+from dict_tts_amd import abi
 
 
 def one(fn):
@@ -51,7 +51,11 @@ def main():
     ap.add_argument("--v", type=float, default=0.1)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--lib", default=None, help="path of the library build to load instead of the in-tree release library (A/B runs: nothing is copied over it)")
     a = ap.parse_args()
+    if a.lib:
+        abi.load_library(os.path.abspath(a.lib))
+    from dict_tts_amd import synth, vocoder
     import istft_ref as ir
     T_ = lambda v: torch.from_numpy(np.ascontiguousarray(v))
     voc = vocoder.HifiGAN(state_dict={k: T_(v) for k, v in synth.hifigan_state_dict(1234).items()}, config=synth.hifigan_config())

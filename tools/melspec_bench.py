@@ -5,7 +5,7 @@ flagship batch of bench.py).  Device time by event pairs around each call, media
 same batch is timed alongside for the launch's share of it (--no-vocoder skips it).  Also prints both pipelines' error against float64
 on utterance 0 in the units of tests/test_melspec_gpu.py.
 
-    python tools/melspec_bench.py [--batch 60] [--frames 700] [--reps 20] [--warmup 5] [--no-vocoder]
+    python tools/melspec_bench.py [--batch 60] [--frames 700] [--reps 20] [--warmup 5] [--no-vocoder] [--lib path/to/libdicttts_hip.so]
 """
 import argparse
 import json
@@ -18,7 +18,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 
-from dict_tts_amd import melspec, synth, vocoder
+from dict_tts_amd import abi
 
 
 def timed(fn, reps, warmup):
@@ -43,7 +43,11 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--no-vocoder", action="store_true")
+    ap.add_argument("--lib", default=None, help="path of the library build to load instead of the in-tree release library (A/B runs: nothing is copied over it)")
     a = ap.parse_args()
+    if a.lib:
+        abi.load_library(os.path.abspath(a.lib))
+    from dict_tts_amd import melspec, synth, vocoder
     import melspec_ref as mr
     fe = melspec.MelSpectrogram()
     L = a.frames * fe.hop
