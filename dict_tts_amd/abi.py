@@ -23,6 +23,7 @@ OUT_POSTERIOR = 9   # not a copy: the posterior pass, dst = a PosteriorArgs bloc
 OUT_MELSPEC = 10     # not a copy, needs no encode: wav -> log-mel, dst = a MelspecArgs block
 OUT_STFT_DISTANCE = 11   # not a copy, needs no encode: a pair of waveform batches -> the sums behind sc / mag, dst = a StftArgs block
 OUT_SPECTRAL = 12    # not a copy, needs no encode: STFT / edit / inverse STFT of a batch of waveforms, dst = a SpectralArgs block
+OUT_GRIFFIN_LIM = 13   # not a copy, needs no encode: magnitudes (or log10-mels) -> waveforms by Griffin-Lim, dst = a GriffinLimArgs block
 SPECTRAL_FORWARD, SPECTRAL_INVERSE = 1, 2   # dtts_spectral_args.mode bits; both = the reference's denoise
 SPK_EMBED, SPK_ID = 1, 2   # dtts_text2mel_speakers kinds: fp32 [B,256] (use_spk_embed) / int64 [B] (use_spk_id)
 TIMER_VOC_CONV, TIMER_S2PA = 1, 2
@@ -61,6 +62,13 @@ class SpectralArgs(C.Structure):
     _fields_ = [("size", C.c_int32), ("mode", C.c_int32), ("hop", C.c_int32), ("B", C.c_int32), ("wav_ld", C.c_int32), ("spec_cap", C.c_int32),
                 ("floor", C.c_float), ("wav_dev", C.c_void_p), ("lens_dev", C.c_void_p), ("frames_dev", C.c_void_p), ("spec_dev", C.c_void_p),
                 ("out_dev", C.c_void_p), ("out_lens_dev", C.c_void_p)]
+
+
+class GriffinLimArgs(C.Structure):
+    """dtts_griffinlim_args (include/dicttts_hip.h): the argument block of dtts_text2mel_fetch(DTTS_OUT_GRIFFIN_LIM)"""
+    _fields_ = [("size", C.c_int32), ("B", C.c_int32), ("spec_cap", C.c_int32), ("hop", C.c_int32), ("n_iter", C.c_int32), ("wav_ld", C.c_int32),
+                ("n_mels", C.c_int32), ("reserved", C.c_int32), ("mag_dev", C.c_void_p), ("mel_dev", C.c_void_p), ("init_dev", C.c_void_p),
+                ("frames_dev", C.c_void_p), ("out_dev", C.c_void_p), ("out_lens_dev", C.c_void_p), ("spec_out_dev", C.c_void_p)]
 
 
 class DttsConfig(C.Structure):
@@ -265,6 +273,16 @@ class Context:
         a = SpectralArgs(C.sizeof(SpectralArgs), int(mode), int(hop), int(B), int(wav_ld), int(spec_cap), float(floor), wav or None, lens or None,
                          frames or None, spec or None, out or None, out_lens or None)
         self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_SPECTRAL, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_SPECTRAL)")
+
+    def griffin_lim(self, B, spec_cap, hop, n_iter, wav_ld, out, stream, mag=None, mel=None, n_mels=0, init=None, frames=None, out_lens=None,
+                    spec_out=None):
+        """Griffin-Lim of B magnitude (mag f32 [B, spec_cap, n_fft / 2 + 1]) or log10-mel (mel f32 [B, spec_cap, n_mels]; needs
+        "istft.inv_mel_basis" in the plan) spectrograms (dtts_text2mel_fetch(DTTS_OUT_GRIFFIN_LIM); needs PART_ISTFT finalised, no encode).
+        Device pointers: init f32 [B, spec_cap, n_fft / 2 + 1, 2] or None = zero phase, frames i32 [B] or None = spec_cap, out f32
+        [B, wav_ld], out_lens i32 [B] or None, spec_out f32 like init or None: the spectrum `out` was inverted from."""
+        a = GriffinLimArgs(C.sizeof(GriffinLimArgs), int(B), int(spec_cap), int(hop), int(n_iter), int(wav_ld), int(n_mels), 0, mag or None, mel or None,
+                           init or None, frames or None, out or None, out_lens or None, spec_out or None)
+        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_GRIFFIN_LIM, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_GRIFFIN_LIM)")
 
     def fetch(self, what, dst, stream):
         self._chk(self.lib.dtts_text2mel_fetch(self.h, what, dst, stream), "dtts_text2mel_fetch")

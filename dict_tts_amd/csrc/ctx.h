@@ -241,6 +241,8 @@ struct dtts_ctx {
     std::vector<float> is_window;                       // host copy: the envelope criterion is checked per hop
     std::map<int, double> is_env;                       // hop -> smallest envelope value (istft_envelope_min), per plan
     int is_skew_hop = 0, is_skew = 8;                   // the slab skew chosen for the hop of the last forward call
+    float* is_pinv = nullptr;                           // "istft.inv_mel_basis" transposed, [n_mels][n_fft / 2 + 1], or null (griffinlim.hip)
+    int is_pinv_mels = 0;
     dtts::Arena a_spec;
 };
 
@@ -346,5 +348,7 @@ int build_stft(dtts_ctx* h);      // stftdist.hip
 int stft_forward(dtts_ctx* h, const dtts_stft_args* a, hipStream_t stream);
 int build_istft(dtts_ctx* h);     // istft.hip
 int spectral_forward(dtts_ctx* h, const dtts_spectral_args* a, hipStream_t stream);
+int check_envelope(dtts_ctx* h, const char* me, int hop);   // istft.hip: the inverse's criterion on (window, hop) or the one refusal (0 = met)
+int griffin_lim(dtts_ctx* h, const dtts_griffinlim_args* a, hipStream_t stream);   // griffinlim.hip
 
 } // namespace dtts

@@ -4,7 +4,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cstddef>
+#include <cstdint>
 #include <vector>
 
 #include "stft_core.h"
@@ -59,6 +61,27 @@ double istft_envelope_min(const std::vector<float>& window, int hop);
 
 hipError_t spectral_forward_launch(SpecFwdParams p, int n_cu, hipStream_t stream);
 int istft_split(long long tiles, int blocks, long long want);   // workgroups per tile: a power of two <= blocks
+
+// The forward launcher's rule — what it refuses, the tile (stft_tile_waves), the split of a tile's bin blocks over workgroups — for ANY
+// kernel pair K2 / K4 (two and four waves) of the signature (SpecFwdParams, extra ...): spectral_fwd_kernel, and Griffin-Lim's projection
+// (griffinlim.hip), which is the same contraction with another epilogue and one more argument.  Written here and nowhere else.
+template <int WT, auto Kern, class... X>
+hipError_t spectral_fwd_cfg(SpecFwdParams p, int n_cu, hipStream_t stream, X... extra) {
+    const size_t lds = stft_set_tile(p.g, WT, p.wav_ld);
+    p.csplit = istft_split((long long)p.g.ntile * p.B, p.g.n_fft / 64, 4LL * n_cu);
+    if (lds > (size_t)MELSPEC_LDS_BYTES || (long long)p.g.ntile * p.B * p.csplit > INT_MAX) return hipErrorInvalidValue;
+    if (hipError_t e = stft_lds_limit<Kern>()) return e;
+    hipLaunchKernelGGL(Kern, dim3((unsigned)(p.g.ntile * p.B * p.csplit)), dim3(64 * WT), lds, stream, p, extra...);
+    return hipGetLastError();
+}
+
+template <auto K2, auto K4, class... X>
+hipError_t spectral_forward_pick(const SpecFwdParams& p, int n_cu, hipStream_t stream, X... extra) {
+    if (!stft_geom_ok(p.g, p.B, p.wav_ld)) return hipErrorInvalidValue;
+    if (p.spec_cap < 1 + p.wav_ld / p.g.hop || !p.frames || !p.spec || ((uintptr_t)p.spec & 7)) return hipErrorInvalidValue;
+    return stft_tile_waves(p.B, p.wav_ld, p.g.hop, p.g.n_fft, p.g.ps, n_cu) == 2 ? spectral_fwd_cfg<2, K2>(p, n_cu, stream, extra...)
+                                                                                : spectral_fwd_cfg<4, K4>(p, n_cu, stream, extra...);
+}
 hipError_t istft_frames_launch(SpecInvParams p, int n_cu, hipStream_t stream);
 hipError_t istft_gather_launch(const SpecGatherParams& p, hipStream_t stream);
 

@@ -223,20 +223,8 @@ int istft_split(long long tiles, int blocks, long long want) {
     return split;
 }
 
-template <int WT>
-static hipError_t spectral_fwd_cfg(SpecFwdParams p, int n_cu, hipStream_t stream) {
-    const size_t lds = stft_set_tile(p.g, WT, p.wav_ld);
-    p.csplit = istft_split((long long)p.g.ntile * p.B, p.g.n_fft / 64, 4LL * n_cu);
-    if (lds > (size_t)MELSPEC_LDS_BYTES || (long long)p.g.ntile * p.B * p.csplit > INT_MAX) return hipErrorInvalidValue;
-    if (hipError_t e = stft_lds_limit<spectral_fwd_kernel<WT>>()) return e;
-    hipLaunchKernelGGL(spectral_fwd_kernel<WT>, dim3((unsigned)(p.g.ntile * p.B * p.csplit)), dim3(64 * WT), lds, stream, p);
-    return hipGetLastError();
-}
-
 hipError_t spectral_forward_launch(SpecFwdParams p, int n_cu, hipStream_t stream) {
-    if (!stft_geom_ok(p.g, p.B, p.wav_ld)) return hipErrorInvalidValue;
-    if (p.spec_cap < 1 + p.wav_ld / p.g.hop || !p.frames || !p.spec || ((uintptr_t)p.spec & 7)) return hipErrorInvalidValue;
-    return stft_tile_waves(p.B, p.wav_ld, p.g.hop, p.g.n_fft, p.g.ps, n_cu) == 2 ? spectral_fwd_cfg<2>(p, n_cu, stream) : spectral_fwd_cfg<4>(p, n_cu, stream);
+    return spectral_forward_pick<spectral_fwd_kernel<2>, spectral_fwd_kernel<4>>(p, n_cu, stream);
 }
 
 hipError_t istft_frames_launch(SpecInvParams p, int n_cu, hipStream_t stream) {
@@ -273,10 +261,33 @@ int build_istft(dtts_ctx* h) {
     if (!sup.hi) return fail(h, DTTS_E_INVAL, "%s: istft.window is all zero", me);
     std::vector<double> w2(n_fft);
     for (int k = 0; k < n_fft; ++k) w2[k] = (double)wn->f[k] * (double)wn->f[k];
+    // optional: "istft.inv_mel_basis" [n_fft / 2 + 1][n_mels], the pseudo-inverse of the mel filterbank that Griffin-Lim's mel input goes
+    // through (griffinlim.hip), stored transposed, [n_mels][n_fft / 2 + 1], so that neighbouring bins are neighbouring loads
+    float* pinv = nullptr;
+    int pinv_mels = 0;
+    const auto pit = h->w.find("istft.inv_mel_basis");
+    if (pit != h->w.end()) {
+        const HostTensor& pt = pit->second;
+        const int bins = n_fft / 2 + 1;
+        if (pt.shape.size() != 2 || pt.shape[0] != bins || pt.shape[1] < 1 || pt.shape[1] > 128)
+            return fail(h, DTTS_E_INVAL, "%s: istft.inv_mel_basis must be [n_fft / 2 + 1 = %d][n_mels in 1 .. 128] (got %d dimensions, %lld x %lld)", me, bins,
+                        (int)pt.shape.size(), (long long)(pt.shape.size() > 0 ? pt.shape[0] : 0), (long long)(pt.shape.size() > 1 ? pt.shape[1] : 0));
+        pinv_mels = (int)pt.shape[1];
+        std::vector<float> tr((size_t)pinv_mels * bins);
+        for (int k = 0; k < bins; ++k)
+            for (int j = 0; j < pinv_mels; ++j) {
+                const float v = pt.f[(size_t)k * pinv_mels + j];
+                if (!std::isfinite(v)) return fail(h, DTTS_E_INVAL, "%s: istft.inv_mel_basis[%d][%d] is not finite", me, k, j);
+                tr[(size_t)j * bins + k] = v;
+            }
+        if (!(pinv = upload(h, tr))) return fail(h, DTTS_E_NOMEM, "%s: device allocation failed", me);
+    }
     float* basis = upload(h, melspec_pack_basis(n_fft, wn->f));
     float* wi = upload(h, istft_pack_inverse(n_fft, wn->f));
     double* w2d = upload(h, w2);
     if (!basis || !wi || !w2d) return fail(h, DTTS_E_NOMEM, "%s: device allocation failed", me);
+    h->is_pinv = pinv;
+    h->is_pinv_mels = pinv_mels;
     h->is = StftBasisPlan{basis, n_fft, sup.lo, sup.hi};
     h->is_wi = wi;
     h->is_w2 = w2d;
@@ -284,6 +295,16 @@ int build_istft(dtts_ctx* h) {
     h->is_env.clear();
     h->is_skew_hop = 0;
     h->istft_ready = true;
+    return DTTS_OK;
+}
+
+// the envelope criterion per (window, hop), fp64 on the host, remembered (0 = met)
+int check_envelope(dtts_ctx* h, const char* me, int hop) {
+    auto it = h->is_env.find(hop);
+    if (it == h->is_env.end()) it = h->is_env.emplace(hop, istft_envelope_min(h->is_window, hop)).first;
+    if (!(it->second > ISTFT_ENV_MIN))
+        return fail(h, DTTS_E_INVAL, "%s: hop = %d: the window's envelope sum_t w^2[n - t hop] falls to %g at a kept sample (must stay above %g)", me, hop,
+                    it->second, ISTFT_ENV_MIN);
     return DTTS_OK;
 }
 
@@ -315,13 +336,8 @@ int spectral_forward(dtts_ctx* h, const dtts_spectral_args* a, hipStream_t strea
             return fail(h, DTTS_E_INVAL, "%s: out_dev overlaps wav_dev (out_dev == wav_dev %+lld samples, B wav_ld = %lld: the filter does not run in place)", me,
                         (long long)(a->out_dev - a->wav_dev), (long long)n);
     }
-    if (inv) {   // the envelope criterion per (window, hop), fp64 on the host, remembered
-        auto it = h->is_env.find(a->hop);
-        if (it == h->is_env.end()) it = h->is_env.emplace(a->hop, istft_envelope_min(h->is_window, a->hop)).first;
-        if (!(it->second > ISTFT_ENV_MIN))
-            return fail(h, DTTS_E_INVAL, "%s: hop = %d: the window's envelope sum_t w^2[n - t hop] falls to %g at a kept sample (must stay above %g)", me,
-                        a->hop, it->second, ISTFT_ENV_MIN);
-    }
+    if (inv)
+        if (int e = check_envelope(h, me, a->hop)) return e;
     const long long n_tiles_inv = (long long)a->B * ((t_need + ISTFT_TILE - 1) / ISTFT_TILE);
     const long long n_chunks = (long long)a->B * std::max(1, (a->wav_ld + ISTFT_GATHER - 1) / ISTFT_GATHER);
     if (n_tiles_inv * (N / 64) > INT_MAX || n_chunks > INT_MAX) return fail(h, DTTS_E_INVAL, "%s: B = %d utterances of wav_ld = %d samples", me, a->B, a->wav_ld);

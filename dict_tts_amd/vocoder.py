@@ -313,3 +313,56 @@ class HifiGAN:
             batch[i, :lens[i]] = torch.as_tensor(np.asarray(m), dtype=torch.float32)
         wav = self.forward_batch(batch.to(self.device), torch.tensor(lens, dtype=torch.int32), check=True).cpu().numpy()
         return [wav[i, :lens[i] * self.hop] for i in range(len(mels))]
+
+
+@register_vocoder
+class GriffinLim:
+    """The reference's checkpoint-free way from a mel to a waveform — ``griffin_lim(_mel_to_linear(10 ** mel))`` (utils/audio.py:35-42,
+    91-95) — as a vocoder plugin: built from hparams alone (fft_size, hop_size, win_size, audio_num_mel_bins, fmin, fmax,
+    audio_sample_rate, griffin_lim_iters; no ``vocoder_ckpt``), run by ``dict_tts_amd.spectral.Spectral.griffin_lim`` on the device.
+    Select it with ``--hparams=vocoder=dict_tts_amd.vocoder.GriffinLim``.  The start phase is drawn from torch's generator on the device:
+    ``torch.manual_seed`` repeats a run.  The context is created by the first call, so construction needs no GPU."""
+
+    def __init__(self, hparams=None, ctx=None, n_iter=None):
+        from . import spectral
+        hp = {**hparams_mod.BIAOBEI_DEFAULTS, **hparams_mod.hparams, **(hparams or {})}
+        self.n_iter = int(hp.get("griffin_lim_iters", 60) if n_iter is None else n_iter)   # egs/egs_bases/tts/base.yaml:57
+        if self.n_iter < 0:
+            raise ValueError(f"griffin_lim_iters = {self.n_iter} (must not be negative)")
+        self.spectral = spectral.Spectral(hp, ctx=ctx)
+        self.hop, self.n_mels = self.spectral.hop, int(hp["audio_num_mel_bins"])
+
+    @property
+    def ctx(self):
+        return self.spectral.ctx
+
+    def spec2wav(self, mel, **kwargs):
+        """mel [T, n_mels] log10-mel (numpy) -> np.float32 [hop (T - 1)]: what the reference's function returns for T frames"""
+        c = torch.as_tensor(np.asarray(mel), dtype=torch.float32).unsqueeze(0).cuda()
+        return self.spectral.griffin_lim(mel=c, n_iter=self.n_iter)[0].view(-1).cpu().numpy()
+
+    def forward_batch(self, mel, lens=None):
+        """mel [B, T, n_mels] float32 cuda tensor, lens [B] valid frames or None -> wav [B, T * hop] float32 cuda tensor, the layout of
+        ``HifiGAN.forward_batch``: utterance b holds its hop (lens[b] - 1) samples, zeros from there on (Griffin-Lim returns one hop less
+        than a generator; callers that cut at lens[b] * hop keep working)."""
+        wav, _ = self.spectral.griffin_lim(mel=mel, frames=lens, n_iter=self.n_iter)
+        return torch.nn.functional.pad(wav, (0, self.hop))
+
+    def denoise(self, wav, lens=None, v=0.1):
+        """``HifiGAN.denoise``: the spectral-subtraction filter through the same ``Spectral`` (and context); lens in frames"""
+        if not (wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 2 and wav.shape[1] % self.hop == 0):
+            raise abi.DttsError(f"denoise: wav of shape {tuple(wav.shape)}, forward_batch gives [B, T * {self.hop}] float32 cuda tensors")
+        if lens is not None:
+            lens = lens.to(device=wav.device, dtype=torch.int32) * self.hop
+        return self.spectral.denoise(wav, lens, v)
+
+    def to_int16(self, wav, lens=None, norm=False):
+        """save_wav's sample conversion (utils/audio.py:11-16) with torch ops: wav [B, T * hop] float32 tensor, lens [B] valid frames ->
+        int16 [B, T * hop], zeros past each utterance; norm divides every utterance by its own peak; the cast truncates, as astype does"""
+        assert wav.dtype == torch.float32 and wav.dim() == 2 and wav.shape[1] % self.hop == 0
+        if lens is not None:
+            keep = torch.arange(wav.shape[1], device=wav.device)[None, :] < (lens.to(wav.device).to(torch.int64) * self.hop)[:, None]
+            wav = torch.where(keep, wav, torch.zeros_like(wav))
+        if norm:
+            wav = wav / wav.abs().amax(dim=1, keepdim=True)
+        return (wav * 32767).to(torch.int16)

@@ -176,7 +176,8 @@ DTTS_API int dtts_load_weight(dtts_handle h, const char* name, const void* host_
 /* STFT -> magnitude edit -> inverse STFT (DTTS_OUT_SPECTRAL below): ONE plan from "istft.window" [n_fft], the analysis AND synthesis window as
  * torch.stft / torch.istft apply it (the win_length samples zero padded and centred to n_fft, as "stft.<i>.window" is).  n_fft is the tensor's
  * length (512 / 1024 / 2048, else DTTS_E_INVAL naming it).  Rebuilt by EVERY call that names it, like DTTS_PART_MELSPEC.  DTTS_E_NOENT
- * without "istft.window". */
+ * without "istft.window".  Optional: "istft.inv_mel_basis" [n_fft / 2 + 1][n_mels <= 128], the pseudo-inverse of the mel filterbank that
+ * DTTS_OUT_GRIFFIN_LIM's mel input goes through (another shape or a non-finite entry: DTTS_E_INVAL); a plan finalised without it has none. */
 #define DTTS_PART_ISTFT 32
 /* Fold, repack into MFMA fragment order and upload.  Fails with DTTS_E_NOENT naming the first missing tensor. */
 DTTS_API int dtts_finalize_weights(dtts_handle h, int parts);
@@ -411,6 +412,48 @@ typedef struct dtts_spectral_args {
     float* out_dev;               /* INVERSE */
     int32_t* out_lens_dev;        /* INVERSE, or NULL */
 } dtts_spectral_args;
+/*
+ * DTTS_OUT_GRIFFIN_LIM: not a copy, needs NO encode — the reference's checkpoint-free way from magnitudes to a waveform, griffin_lim /
+ * griffin_lim_torch (utils/audio.py:35-42, 136-158; griffin_lim_iters, egs/egs_bases/tts/base.yaml:57) with _mel_to_linear
+ * (utils/audio.py:91-95) in front of it for mel input, for a batch: dst = (dtts_griffinlim_args*), args->size = sizeof(*args).  The
+ * transforms are exactly DTTS_OUT_SPECTRAL's, with the window and n_fft of dtts_finalize_weights(DTTS_PART_ISTFT).  Per utterance b of
+ * T_b = frames_dev[b] frames (clamped to [0, spec_cap]; NULL = spec_cap), bins = n_fft / 2 + 1:
+ *   A      = |mag_dev[b][t][k]|, or from a log10-mel: max(1e-10, sum_j P[k][j] 10^mel_dev[b][t][j]) with P = "istft.inv_mel_basis"
+ *            [bins][n_mels] (the pseudo-inverse of the mel filterbank, computed by the caller; loaded before the finalise; one fp32 FMA chain
+ *            in ascending j per output)
+ *   S      = A init (two fp32 products per bin; init_dev NULL = zero phase, S = A); y = INVERSE(S), hop (T_b - 1) samples
+ *   n_iter times:  X = FORWARD(y) (T_b frames again);  S = A X / |X| (S = A where |X| = 0, as np.angle(0) = 0; bins 0 and n_fft / 2 are
+ *            real and become +A or -A by the sign of X, +A for zero);  y = INVERSE(S)
+ *   out_dev[b][0 .. hop (T_b - 1)) = y, samples past it untouched; out_lens_dev[b] = hop (T_b - 1); spec_out_dev (optional) receives
+ *   the S that y was inverted from, rows >= T_b untouched.  No momentum (the reference has none).
+ *   mag_dev f32 [B][spec_cap][bins] or mel_dev f32 [B][spec_cap][n_mels] (exactly one) · init_dev f32 [B][spec_cap][bins][2] interleaved
+ *   re, im, 8-byte aligned, or NULL · frames_dev i32 [B] or NULL · out_dev f32 [B][wav_ld], wav_ld >= hop (spec_cap - 1) · out_lens_dev i32 [B]
+ *   or NULL · spec_out_dev f32 [B][spec_cap][bins][2], 8-byte aligned, or NULL.
+ * 1 + 2 + 3 n_iter launches on `stream` (target and start; frames' inverse DFT and overlap-add; per iteration the forward contraction with the
+ * projection as its epilogue and the two of the inverse); no host synchronisation unless the workspace grows (it is DTTS_OUT_SPECTRAL's: A,
+ * S, the windowed frames and the waveform between the iterations); no atomics.  Every utterance's result is bit-identical alone and inside
+ * any batch; n_iter = 0 is DTTS_SPECTRAL_INVERSE of A init, bit for bit.  DTTS_E_STATE without a finalised plan, or with mel_dev and no
+ * "istft.inv_mel_basis" in that plan (naming the tensor); DTTS_E_INVAL (naming the value) for a wrong size, B <= 0, spec_cap <= 0,
+ * n_iter < 0, both or neither of mag_dev / mel_dev, an n_mels that is not the loaded basis's, a hop outside 1 .. n_fft or one that fails
+ * DTTS_OUT_SPECTRAL's envelope criterion, wav_ld < hop (spec_cap - 1), a NULL out_dev with samples to write, or a misaligned pointer.
+ */
+#define DTTS_OUT_GRIFFIN_LIM 13
+typedef struct dtts_griffinlim_args {
+    int32_t size;                 /* sizeof(dtts_griffinlim_args) */
+    int32_t B, spec_cap;          /* spec_cap: rows per utterance of every [B][spec_cap][..] tensor */
+    int32_t hop;                  /* any integer in 1 .. n_fft that meets the envelope criterion */
+    int32_t n_iter;               /* >= 0; the reference's griffin_lim_iters is 60 */
+    int32_t wav_ld;               /* samples per row of out_dev, >= hop (spec_cap - 1) */
+    int32_t n_mels;               /* with mel_dev: columns of mel_dev = columns of "istft.inv_mel_basis"; ignored with mag_dev */
+    int32_t reserved;             /* 0 */
+    const float* mag_dev;         /* target magnitudes, or NULL */
+    const float* mel_dev;         /* log10-mel, or NULL: exactly one of the two */
+    const float* init_dev;        /* the start's complex factor (e^(i phase) for Griffin-Lim proper), or NULL = 1 */
+    const int32_t* frames_dev;    /* or NULL = spec_cap for all */
+    float* out_dev;
+    int32_t* out_lens_dev;        /* or NULL */
+    float* spec_out_dev;          /* or NULL */
+} dtts_griffinlim_args;
 DTTS_API int dtts_text2mel_fetch(dtts_handle h, int what, void* dst_dev, dtts_stream stream);
 
 /*
