@@ -75,7 +75,7 @@ struct S2paArgs {
 hipError_t s2pa_launch(const S2paArgs& a, hipStream_t s);
 hipError_t max_i64_launch(const int64_t* x, long long n, int* out, hipStream_t s);
 // table mode: out = max over rows of the entry's max pinyin_map (t_pmmax[e]; 1 for entry -1, 0 for -2)
-hipError_t max_entry_pm_launch(const int* entry, const int* t_pmmax, long long n, int* out, hipStream_t s);
+hipError_t max_entry_pm_launch(const int* entry, const int* t_pmmax, const int* t_off, const int* t_poff, long long n, int* out /* [3] */, hipStream_t s);
 
 // y = a + b (elementwise, n floats, n % 4 == 0)
 hipError_t add_launch(const float* a, const float* b, float* y, long long n, hipStream_t s);

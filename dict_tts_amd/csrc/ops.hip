@@ -1258,21 +1258,34 @@ __global__ void max_i64_kernel(const int64_t* x, long long n, int* out) {
     for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o, 64));
     if ((threadIdx.x & 63) == 0) atomicMax(out, m);
 }
-__global__ void max_entry_pm_kernel(const int* entry, const int* t_pmmax, long long n, int* out) {
-    int m = 0;
+// out[0]: the batch's largest sense index; out[1] / out[2]: the gloss rows / pinyin slots of its longest table entry (what L_k / P must hold)
+__global__ void max_entry_pm_kernel(const int* entry, const int* t_pmmax, const int* t_off, const int* t_poff, long long n, int* out) {
+    int m = 0, ml = 0, mp = 0;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const int e = entry[i];
         m = max(m, e >= 0 ? t_pmmax[e] : (e == -1 ? 1 : 0));
+        if (e >= 0) {
+            ml = max(ml, t_off[e + 1] - t_off[e]);
+            mp = max(mp, t_poff[e + 1] - t_poff[e]);
+        }
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o, 64));
-    if ((threadIdx.x & 63) == 0) atomicMax(out, m);
+    for (int o = 32; o > 0; o >>= 1) {
+        m = max(m, __shfl_xor(m, o, 64));
+        ml = max(ml, __shfl_xor(ml, o, 64));
+        mp = max(mp, __shfl_xor(mp, o, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        atomicMax(out, m);
+        atomicMax(out + 1, ml);
+        atomicMax(out + 2, mp);
+    }
 }
-hipError_t max_entry_pm_launch(const int* entry, const int* t_pmmax, long long n, int* out, hipStream_t s) {
-    hipError_t e = hipMemsetAsync(out, 0, sizeof(int), s);
+hipError_t max_entry_pm_launch(const int* entry, const int* t_pmmax, const int* t_off, const int* t_poff, long long n, int* out, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(out, 0, 3 * sizeof(int), s);
     if (e != hipSuccess) return e;
     const int blocks = (int)((n + 255) / 256 > 256 ? 256 : (n + 255) / 256);
-    hipLaunchKernelGGL(max_entry_pm_kernel, dim3(blocks), dim3(256), 0, s, entry, t_pmmax, n, out);
+    hipLaunchKernelGGL(max_entry_pm_kernel, dim3(blocks), dim3(256), 0, s, entry, t_pmmax, t_off, t_poff, n, out);
     return hipGetLastError();
 }
 hipError_t max_i64_launch(const int64_t* x, long long n, int* out, hipStream_t s) {

@@ -280,7 +280,7 @@ static int encode_impl(dtts_handle h, const int64_t* word_tokens, const float* k
     int* ilens = A.alloc<int>(B);
     int* starts = A.alloc<int>((size_t)B * (T_w + 1));
     h->mel_lens = A.alloc<int>(B);
-    int* pm_max = A.alloc<int>(1);
+    int* pm_max = A.alloc<int>(3);   // [0] largest sense index; id path: [1] / [2] rows / slots of the longest entry
     if (!x || !hb || !qkv || !att || !ff || !enc1 || !q || !qk || !wv || !v || !pron || !h->context || !h->weo || !h->dur ||
         !h->pron_attn || !h->dict_attn || !d0 || !d1 || !h->lens || !ilens || !starts || !h->mel_lens || !pm_max)
         return fail(h, DTTS_E_NOMEM, "encoder workspace");
@@ -308,7 +308,7 @@ static int encode_impl(dtts_handle h, const int64_t* word_tokens, const float* k
             p = base_params(q, C, B, T_w, T_w, qk, D);
             LAUNCH(conv1d_launch(h->s2_kT, p, s));
         }
-        if (entry_ids) LAUNCH(max_entry_pm_launch(entry_ids, h->t_pmmax, (long long)rows, pm_max, s));
+        if (entry_ids) LAUNCH(max_entry_pm_launch(entry_ids, h->t_pmmax, h->t_off, h->t_poff, (long long)rows, pm_max, s));
         else LAUNCH(max_i64_launch(pinyin_map, (long long)rows * P, pm_max, s));
         S2paArgs a;
         memset(&a, 0, sizeof a);
@@ -380,14 +380,18 @@ static int encode_impl(dtts_handle h, const int64_t* word_tokens, const float* k
     if (!mel2word) {
         LAUNCH(durations_launch(h->dur, ilens, starts, h->mel_lens, B, T_w, s));
         std::vector<int> tot(B);
-        int pm_host = 0;
+        int pm_host3[3] = {0, 0, 0};
+        int& pm_host = pm_host3[0];
         unsigned long long spk_bad[2] = {0ull, 0ull};
         HIPCHK(hipMemcpyAsync(tot.data(), h->mel_lens, sizeof(int) * B, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(&pm_host, pm_max, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(pm_host3, pm_max, sizeof(int) * (entry_ids ? 3 : 1), hipMemcpyDeviceToHost, s));
         if (spk) HIPCHK(hipMemcpyAsync(spk_bad, h->spk_flag, sizeof spk_bad, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));  // the one host sync of the path: T_mel sizes every later buffer
         if (pm_host > DTTS_MAX_SENSES)   // the S2PA kernel keeps DTTS_MAX_SENSES sense slots; larger indices would silently get weight 0
             return fail(h, DTTS_E_INVAL, "pinyin_map holds sense index %d; at most %d senses per word are supported", pm_host, DTTS_MAX_SENSES);
+        if (pm_host3[1] > L_k || pm_host3[2] > P)   // s2pa_row clamps an entry to L_k rows / P slots: the rest would be dropped silently
+            return fail(h, DTTS_E_INVAL, "dtts_text2mel_encode_ids: the batch holds a table entry of %d gloss rows and one of %d pinyin slots; L_k=%d P=%d must be the batch maxima",
+                        pm_host3[1], pm_host3[2], L_k, P);
         if (spk_bad[0])   // nn.Embedding raises on such an id; the gather wrote a zero row instead of reading out of range
             return fail(h, DTTS_E_INVAL, "speaker id %lld of utterance %llu is out of range: spk_embed_proj has %d rows (num_spk)",
                         (long long)spk_bad[1], spk_bad[0] - 1, h->spk_n);

@@ -217,6 +217,12 @@ DTTS_API int dtts_dict_table_upload(dtts_handle h, int n_entries, const int32_t*
  * -1 the BOS / last row the collater pads onto every sentence (zero vectors, key_map = pinyin_map = 1), -2 batch
  * padding.  L_k / P are the batch maxima the collated tensors would have had (they size dict_attn / pron_attn).
  * Results are identical to dtts_text2mel_encode on the tensors collated from the same table.
+ * An entry with more gloss rows than L_k or more pinyin slots than P would lose the rest silently (the kernel clamps): with
+ * predicted durations such a batch is rejected (DTTS_E_INVAL, naming both maxima) at the T_mel synchronisation; with
+ * teacher-forced mel2word there is no synchronisation and NO check: the caller guarantees that L_k / P are the batch maxima
+ * (and, on both APIs, that no sense index exceeds DTTS_MAX_SENSES, see there).  The maxima are taken over EVERY slot with an
+ * entry id >= 0, also those of words past their utterance's end (word_tokens == 0), whose rows never reach an output: the
+ * collated tensors would have been sized for them too.  Entry ids must be < n_entries; they are not checked.
  */
 DTTS_API int dtts_text2mel_encode_ids(dtts_handle h, const int64_t* word_tokens_dev, const int32_t* entry_ids_dev,
                              const int64_t* pron_modified_dev, const int64_t* mel2word_dev, int T_m2w, int B, int T_w, int L_k,

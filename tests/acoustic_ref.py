@@ -192,6 +192,46 @@ BOUNDS = {
 KL_REL = 1.4e-5                                                           # |kl - kl64| / |kl64|: 4.8e-6
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# shared by tests/test_text2mel_kernels_gpu.py, tests/test_s2pa_cpu.py and tests/test_s2pa_gpu.py
+_SD = {}
+
+
+def sd_np(hp):
+    key = tuple(sorted(hp.items()))
+    if key not in _SD:
+        _SD[key] = synth.dict_tts_state_dict(SEED, acoustic=hp)
+    return _SD[key]
+
+
+def shape_hp(name):
+    return {} if name == "default" else CONFIGS[name]
+
+
+def as_rows(k, x, word_mask):
+    """-> [B, rows, ...] float64 numpy with rows on axis 1; the S2PA context only on valid words (the reference masks it)"""
+    x = x.detach().cpu().double()
+    if k == "dict_attn":
+        x = x[:, 0].transpose(1, 2)           # [B, 1, L_k, T_w] -> [B, T_w, L_k]
+    if k == "dur":
+        x = x[..., None]
+    if k == "context":
+        x = x * word_mask[..., None]
+    return x.numpy()
+
+
+def compare(case, got, want, keys, fails, batch=None, sel=None, mel="mel"):
+    """append the exceeded bounds of got vs want to fails; sel: an index into [B, rows] (e.g. (slice(b, b + 1), slice(0, n))), all rows by
+    default; mel: the BOUNDS entry of mel_out"""
+    word_mask = torch.from_numpy(batch["word_tokens"] > 0).double() if batch is not None else None
+    for k in keys:
+        g, w = as_rows(k, got[k], word_mask), as_rows(k, want[k], word_mask)
+        if sel is not None:
+            g, w = g[sel], w[sel]
+        bk = mel if k == "mel_out" else k
+        fails += [f"{case}: {f}" for f in check(case, k, g, w, BOUNDS[bk])]
+
+
 def bf16_halo(sd, site, layer, row, halo_rows):
     """a planted kernel defect for forward(hook=...): the tile whose first output row is `row` reads its halo rows `halo_rows` of layer
     `layer` of WaveNet `site` rounded to bf16 (the low half of a split-bf16 operand dropped at the seam)"""

@@ -40,6 +40,7 @@ import pytest
 import torch
 
 import acoustic_ref as ar
+from acoustic_ref import as_rows, compare, sd_np, shape_hp   # (shared with the CPU suites: they live beside the bounds)
 import posterior_ref as pr
 from dict_tts_amd import abi, synth
 from oracle import dict_tts_ref as ref
@@ -47,7 +48,6 @@ from oracle import dict_tts_ref as ref
 pytestmark = pytest.mark.gpu
 T = lambda a: torch.from_numpy(np.ascontiguousarray(a))
 ENC = ("word_encoder_out", "context", "dur", "dict_attn", "pron_attn")
-_SD = {}
 
 
 @pytest.fixture(autouse=True, scope="module")
@@ -56,13 +56,6 @@ def _threads():
     torch.set_num_threads(16)
     yield
     torch.set_num_threads(n)
-
-
-def sd_np(hp):
-    key = tuple(sorted(hp.items()))
-    if key not in _SD:
-        _SD[key] = synth.dict_tts_state_dict(ar.SEED, acoustic=hp)
-    return _SD[key]
 
 
 def make_model(hp, **extra):
@@ -82,10 +75,6 @@ def table_model(name):
         m.upload_dict_table(synth.dict_table(ar.SEED))
         _MODELS[name] = m
     return _MODELS[name]
-
-
-def shape_hp(name):
-    return {} if name == "default" else ar.CONFIGS[name]
 
 
 @pytest.fixture(scope="module")
@@ -121,30 +110,6 @@ def reference(hp, batch, m2w=None, z=None):
     """the float64 restatement; z: the same prior sample the GPU gets"""
     return ar.forward(ar.state(sd_np(hp), torch.float64), hp, *ar.inputs(batch, torch.float64),
                       mel2word=None if m2w is None else T(m2w), z_p=z)
-
-
-def as_rows(k, x, word_mask):
-    """-> [B, rows, ...] float64 numpy with rows on axis 1; the S2PA context only on valid words (the reference masks it)"""
-    x = x.detach().cpu().double()
-    if k == "dict_attn":
-        x = x[:, 0].transpose(1, 2)           # [B, 1, L_k, T_w] -> [B, T_w, L_k]
-    if k == "dur":
-        x = x[..., None]
-    if k == "context":
-        x = x * word_mask[..., None]
-    return x.numpy()
-
-
-def compare(case, got, want, keys, fails, batch=None, sel=None, mel="mel"):
-    """append the exceeded bounds of got vs want to fails; sel: an index into [B, rows] (e.g. (slice(b, b + 1), slice(0, n))), all rows by
-    default; mel: the BOUNDS entry of mel_out"""
-    word_mask = torch.from_numpy(batch["word_tokens"] > 0).double() if batch is not None else None
-    for k in keys:
-        g, w = as_rows(k, got[k], word_mask), as_rows(k, want[k], word_mask)
-        if sel is not None:
-            g, w = g[sel], w[sel]
-        bk = mel if k == "mel_out" else k
-        fails += [f"{case}: {f}" for f in ar.check(case, k, g, w, ar.BOUNDS[bk])]
 
 
 def near_ties(want):
