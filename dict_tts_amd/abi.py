@@ -24,6 +24,9 @@ OUT_MELSPEC = 10     # not a copy, needs no encode: wav -> log-mel, dst = a Mels
 OUT_STFT_DISTANCE = 11   # not a copy, needs no encode: a pair of waveform batches -> the sums behind sc / mag, dst = a StftArgs block
 OUT_SPECTRAL = 12    # not a copy, needs no encode: STFT / edit / inverse STFT of a batch of waveforms, dst = a SpectralArgs block
 OUT_GRIFFIN_LIM = 13   # not a copy, needs no encode: magnitudes (or log10-mels) -> waveforms by Griffin-Lim, dst = a GriffinLimArgs block
+OUT_LOSSES = 14   # not a copy, needs no encode: the sums behind validation_step's mel (l1 / mse / ssim) and word-duration losses, dst = a LossArgs block
+LOSS_TILE_ROWS = 32   # DTTS_LOSS_TILE_ROWS: frames per tile of the mel half (the shape cases of tests/losses_shapes.py derive from it)
+LOSS_MAX_WORDS = 16384   # DTTS_LOSS_MAX_WORDS
 SPECTRAL_FORWARD, SPECTRAL_INVERSE = 1, 2   # dtts_spectral_args.mode bits; both = the reference's denoise
 SPK_EMBED, SPK_ID = 1, 2   # dtts_text2mel_speakers kinds: fp32 [B,256] (use_spk_embed) / int64 [B] (use_spk_id)
 TIMER_VOC_CONV, TIMER_S2PA = 1, 2
@@ -69,6 +72,15 @@ class GriffinLimArgs(C.Structure):
     _fields_ = [("size", C.c_int32), ("B", C.c_int32), ("spec_cap", C.c_int32), ("hop", C.c_int32), ("n_iter", C.c_int32), ("wav_ld", C.c_int32),
                 ("n_mels", C.c_int32), ("reserved", C.c_int32), ("mag_dev", C.c_void_p), ("mel_dev", C.c_void_p), ("init_dev", C.c_void_p),
                 ("frames_dev", C.c_void_p), ("out_dev", C.c_void_p), ("out_lens_dev", C.c_void_p), ("spec_out_dev", C.c_void_p)]
+
+
+class LossArgs(C.Structure):
+    """dtts_loss_args (include/dicttts_hip.h): the argument block of dtts_text2mel_fetch(DTTS_OUT_LOSSES)"""
+    _fields_ = [("size", C.c_int32), ("B", C.c_int32), ("T", C.c_int32), ("n_mel", C.c_int32), ("pred_ld", C.c_int32), ("tgt_ld", C.c_int32),
+                ("bias", C.c_float), ("T_w", C.c_int32), ("T_mel", C.c_int32), ("m2w_ld", C.c_int32), ("dur_scale", C.c_int32), ("reserved", C.c_int32),
+                ("pred_dev", C.c_void_p), ("tgt_dev", C.c_void_p), ("mel_sums_dev", C.c_void_p), ("mel_count_dev", C.c_void_p),
+                ("ssim_map_dev", C.c_void_p), ("dur_pred_dev", C.c_void_p), ("mel2word_dev", C.c_void_p), ("word_len_dev", C.c_void_p),
+                ("dur_sums_dev", C.c_void_p), ("dur_gt_dev", C.c_void_p)]
 
 
 class DttsConfig(C.Structure):
@@ -283,6 +295,18 @@ class Context:
         a = GriffinLimArgs(C.sizeof(GriffinLimArgs), int(B), int(spec_cap), int(hop), int(n_iter), int(wav_ld), int(n_mels), 0, mag or None, mel or None,
                            init or None, frames or None, out or None, out_lens or None, spec_out or None)
         self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_GRIFFIN_LIM, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_GRIFFIN_LIM)")
+
+    def losses(self, B, stream, pred=None, tgt=None, T=0, n_mel=0, mel_sums=None, mel_count=None, pred_ld=0, tgt_ld=0, bias=6.0, ssim_map=None,
+               dur_pred=None, mel2word=None, word_len=None, T_w=0, T_mel=0, m2w_ld=0, dur_scale=0, dur_sums=None, dur_gt=None):
+        """the sums behind validation_step's losses of B utterances (dtts_text2mel_fetch(DTTS_OUT_LOSSES); needs no weights and no encode).
+        Device pointers.  Mel half (runs iff mel_sums is given): pred f32 [B, pred_ld, n_mel], tgt f32 [B, tgt_ld, n_mel] (leading dimensions
+        0 = T), mel_sums f64 [B, 3] out (sum w |p - t|, sum w (p - t)^2, sum w (1 - ssim)), mel_count i64 [B] out, ssim_map f32 [B, T, n_mel]
+        out or None.  Duration half (runs iff dur_sums is given): dur_pred f32 [B, T_w], mel2word i64 [B, m2w_ld] with T_mel columns used,
+        word_len i32 [B], dur_scale 0 = log / 1 = linear, dur_sums f64 [B, 5] out, dur_gt i32 [B, T_w] out or None."""
+        a = LossArgs(C.sizeof(LossArgs), int(B), int(T), int(n_mel), int(pred_ld), int(tgt_ld), float(bias), int(T_w), int(T_mel), int(m2w_ld),
+                     int(dur_scale), 0, pred or None, tgt or None, mel_sums or None, mel_count or None, ssim_map or None, dur_pred or None,
+                     mel2word or None, word_len or None, dur_sums or None, dur_gt or None)
+        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_LOSSES, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_LOSSES)")
 
     def fetch(self, what, dst, stream):
         self._chk(self.lib.dtts_text2mel_fetch(self.h, what, dst, stream), "dtts_text2mel_fetch")

@@ -29,6 +29,7 @@
 #include "melspec.h"
 #include "stftdist.h"
 #include "istft.h"
+#include "losses.h"
 
 // dtts_config.tune_flags: the bits the library honours are listed at TUNE_RELEASE_MASK (context.hip)
 #define DTTS_TUNE(h, bit) (((h)->tune & (bit)) != 0)
@@ -244,6 +245,10 @@ struct dtts_ctx {
     float* is_pinv = nullptr;                           // "istft.inv_mel_basis" transposed, [n_mels][n_fft / 2 + 1], or null (griffinlim.hip)
     int is_pinv_mels = 0;
     dtts::Arena a_spec;
+    // ---- validation losses (dtts_text2mel_fetch(DTTS_OUT_LOSSES); losses.hip): the SSIM window in fp64 (uploaded by the first call) and the
+    // workspace of the per-tile sums
+    double* loss_win = nullptr;
+    dtts::Arena a_loss;
 };
 
 namespace dtts {
@@ -350,5 +355,6 @@ int build_istft(dtts_ctx* h);     // istft.hip
 int spectral_forward(dtts_ctx* h, const dtts_spectral_args* a, hipStream_t stream);
 int check_envelope(dtts_ctx* h, const char* me, int hop);   // istft.hip: the inverse's criterion on (window, hop) or the one refusal (0 = met)
 int griffin_lim(dtts_ctx* h, const dtts_griffinlim_args* a, hipStream_t stream);   // griffinlim.hip
+int losses_forward(dtts_ctx* h, const dtts_loss_args* a, hipStream_t stream);     // losses.hip
 
 } // namespace dtts

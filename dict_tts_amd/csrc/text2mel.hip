@@ -771,6 +771,7 @@ int dtts_text2mel_fetch(dtts_handle h, int what, void* dst, dtts_stream stream) 
     if (what == DTTS_OUT_STFT_DISTANCE) return stft_forward(h, (const dtts_stft_args*)dst, (hipStream_t)stream);   // nor does this
     if (what == DTTS_OUT_SPECTRAL) return spectral_forward(h, (const dtts_spectral_args*)dst, (hipStream_t)stream);      // nor this
     if (what == DTTS_OUT_GRIFFIN_LIM) return griffin_lim(h, (const dtts_griffinlim_args*)dst, (hipStream_t)stream);      // nor this
+    if (what == DTTS_OUT_LOSSES) return losses_forward(h, (const dtts_loss_args*)dst, (hipStream_t)stream);                // nor this
     if (!h->encoded) return fail(h, DTTS_E_STATE, "dtts_text2mel_fetch before encode");
     if (what == DTTS_OUT_POSTERIOR) {   // the posterior pass; dst is the host argument block
         const dtts_posterior_args* a = (const dtts_posterior_args*)dst;

@@ -460,6 +460,66 @@ typedef struct dtts_griffinlim_args {
     int32_t* out_lens_dev;        /* or NULL */
     float* spec_out_dev;          /* or NULL */
 } dtts_griffinlim_args;
+/*
+ * DTTS_OUT_LOSSES: not a copy, needs NO encode — the sums behind the figures the reference's validation_step reports for the acoustic
+ * model (tasks/tts/dict_tts.py:44-79,127-136): the masked mel losses l1 / mse / ssim of add_mel_loss (tasks/tts/tts_base.py:182-222,
+ * modules/commons/ssim.py) and the word-duration losses of add_dur_loss in eval mode (tasks/tts/ps_flow.py:99-139), for a batch:
+ * dst = (dtts_loss_args*), args->size = sizeof(*args).  Two halves, each optional: the MEL half runs iff mel_sums_dev is not NULL, the
+ * DURATION half iff dur_sums_dev is not NULL (neither: DTTS_E_INVAL).  No gradients.
+ *   MEL half, on the batch tensors as given: pred_dev f32 [B][pred_ld][n_mel] (mel_out), tgt_dev f32 [B][tgt_ld][n_mel] (the ground truth),
+ *   T frames of each used (the leading dimensions >= T; 0 = exactly T), n_mel in 1 .. 128.  A frame's weight w is 1 iff its TARGET row is
+ *   not all zero (weights_nonzero_speech: decided by the values, not by a length; a silent frame in mid-utterance has weight 0).  SSIM is
+ *   the reference's: the 11 x 11 window of create_window (the float32 Gaussian of sigma 1.5, normalised in float32, its float32 outer
+ *   product; built on the host), applied to the images pred + bias and tgt + bias, which are ZERO outside [0, T) x [0, n_mel) while the
+ *   pad rows inside [0, T) are read as they are (after the bias they hold 6.0, not 0); C1 = 0.01^2, C2 = 0.03^2.  So an utterance's sums
+ *   depend on T and on its own rows only: they are bit-identical whatever else the batch holds at the same T — and they are NOT what the
+ *   utterance gives alone at a shorter T (there the window meets zeros where it meets 6.0 here).  That is the reference's definition.
+ *     mel_sums_dev  f64 [B][3]: sum w |p - t|, sum w (p - t)^2, sum w (1 - ssim) over the utterance's T n_mel values;
+ *     mel_count_dev i64 [B]:    sum w (weighted frames times n_mel); the reference's batch figure is sum_b sums / sum_b count;
+ *     ssim_map_dev  f32 [B][T][n_mel] or NULL: the unweighted SSIM map (tests and diagnosis).
+ *   The bias is added in fp64, the five window moments (x, y, x^2, y^2, xy; 121 taps each, rows then columns ascending) and the quotient
+ *   are fp64: the float32 path of the reference forms E[x^2] - E[x]^2 of values near 6 against C2 = 9e-4 and loses the figure for close
+ *   predictions.  One workgroup per utterance and tile of DTTS_LOSS_TILE_ROWS frames, then one launch that adds an utterance's tiles in
+ *   index order; the weights multiply (a NaN in a frame of weight 0 reaches the sum, as in the reference).
+ *   DURATION half: dur_pred_dev f32 [B][T_w] (ret['dur'], log domain for dur_scale 0), mel2word_dev i64 [B][m2w_ld] with T_mel columns
+ *   used (m2w_ld >= T_mel; 0 = exactly T_mel), word_len_dev i32 [B], dur_scale 0 = log, 1 = linear.  Per utterance, for w = 1 .. T_w:
+ *   d_w = frames with mel2word == w (mel2ph_to_dur; index 0 = padding and every value outside 0 .. T_w are IGNORED, where the reference's
+ *   scatter_add fails); n_w = [w <= word_len]; dp = dur_pred n; g = log(d + 1) n (log) or d n (linear); then the second logarithm the
+ *   reference applies when not training: dp2 = log(dp + 1), g2 = log(g + 1) for log scale, dp2 = dp, g2 = g for linear.
+ *     dur_sums_dev f64 [B][5]: sum n |dp - g|, sum n, sum [g2 > 0] |dp2 - g2|, sum [g2 > 0], sum dp2 - sum g2 (signed; added per word as dp2 - g2), so that
+ *                  wdur (eval) = sums[2] / sums[3] and sdur = mean_b |sums[4]| over a batch (add the sums first), sums[0] / sums[1] the
+ *                  training-mode wdur;
+ *     dur_gt_dev   i32 [B][T_w] or NULL: the counts d_w.
+ *   Logarithms and sums are fp64, in a fixed order (the histogram uses integer LDS atomics, which no order can change); the logarithm of
+ *   a non-positive argument follows IEEE (NaN / -inf), as the reference's does.
+ * Two launches (MEL) plus one (DURATION) on `stream`; no host synchronisation unless the workspace of the tile sums grows; no atomics on
+ * floating-point values: the same inputs give the same bits.  DTTS_E_INVAL (naming the value) for a wrong size, B <= 0, T <= 0, n_mel
+ * outside 1 .. 128, a bias that is not finite, a leading dimension below its extent, T_w outside 1 .. DTTS_LOSS_MAX_WORDS, T_mel < 0,
+ * dur_scale outside {0, 1}, a NULL input of a requested half, or a misaligned pointer.
+ */
+#define DTTS_OUT_LOSSES 14
+#define DTTS_LOSS_TILE_ROWS 32      /* frames per tile of the MEL half.  FIXED: an utterance's tile sums are joined in tile order */
+#define DTTS_LOSS_MAX_WORDS 16384   /* T_w of the DURATION half: the histogram of one utterance lives in LDS */
+typedef struct dtts_loss_args {
+    int32_t size;                 /* sizeof(dtts_loss_args) */
+    int32_t B;
+    int32_t T, n_mel;             /* MEL: frames of the batch tensor (the image height), mel bins 1 .. 128 */
+    int32_t pred_ld, tgt_ld;      /* MEL: frames per utterance of pred_dev / tgt_dev, >= T; 0 = T */
+    float bias;                   /* MEL: added to both images (the reference: 6.0) */
+    int32_t T_w, T_mel, m2w_ld;   /* DURATION: words per utterance, columns of mel2word used, columns per row (>= T_mel; 0 = T_mel) */
+    int32_t dur_scale;            /* DURATION: 0 = log, 1 = linear */
+    int32_t reserved;             /* 0 */
+    const float* pred_dev;        /* MEL */
+    const float* tgt_dev;         /* MEL */
+    double* mel_sums_dev;         /* MEL, or NULL: skip the half */
+    int64_t* mel_count_dev;       /* MEL */
+    float* ssim_map_dev;          /* MEL, or NULL */
+    const float* dur_pred_dev;    /* DURATION */
+    const int64_t* mel2word_dev;  /* DURATION */
+    const int32_t* word_len_dev;  /* DURATION */
+    double* dur_sums_dev;         /* DURATION, or NULL: skip the half */
+    int32_t* dur_gt_dev;          /* DURATION, or NULL */
+} dtts_loss_args;
 DTTS_API int dtts_text2mel_fetch(dtts_handle h, int what, void* dst_dev, dtts_stream stream);
 
 /*
