@@ -27,6 +27,10 @@ OUT_GRIFFIN_LIM = 13   # not a copy, needs no encode: magnitudes (or log10-mels)
 OUT_LOSSES = 14   # not a copy, needs no encode: the sums behind validation_step's mel (l1 / mse / ssim) and word-duration losses, dst = a LossArgs block
 LOSS_TILE_ROWS = 32   # DTTS_LOSS_TILE_ROWS: frames per tile of the mel half (the shape cases of tests/losses_shapes.py derive from it)
 LOSS_MAX_WORDS = 16384   # DTTS_LOSS_MAX_WORDS
+OUT_DTW = 15   # not a copy, needs no encode: dynamic time warping of a batch of sequence pairs (distance, path, F0 moments), dst = a DtwArgs block
+DTW_STRIP_ROWS = 1024   # DTTS_DTW_STRIP_ROWS: rows one pass of the wave covers (the shape cases of tests/dtw_shapes.py derive from it)
+DTW_LANE_ROWS = 16      # rows of a strip one lane owns (DTW_STRIP_ROWS / 64)
+DTW_MAX_LEN = 8192      # DTTS_DTW_MAX_LEN
 SPECTRAL_FORWARD, SPECTRAL_INVERSE = 1, 2   # dtts_spectral_args.mode bits; both = the reference's denoise
 SPK_EMBED, SPK_ID = 1, 2   # dtts_text2mel_speakers kinds: fp32 [B,256] (use_spk_embed) / int64 [B] (use_spk_id)
 TIMER_VOC_CONV, TIMER_S2PA = 1, 2
@@ -81,6 +85,21 @@ class LossArgs(C.Structure):
                 ("pred_dev", C.c_void_p), ("tgt_dev", C.c_void_p), ("mel_sums_dev", C.c_void_p), ("mel_count_dev", C.c_void_p),
                 ("ssim_map_dev", C.c_void_p), ("dur_pred_dev", C.c_void_p), ("mel2word_dev", C.c_void_p), ("word_len_dev", C.c_void_p),
                 ("dur_sums_dev", C.c_void_p), ("dur_gt_dev", C.c_void_p)]
+
+
+class DtwArgs(C.Structure):
+    """dtts_dtw_args (include/dicttts_hip.h): the argument block of dtts_text2mel_fetch(DTTS_OUT_DTW)"""
+    _fields_ = [("size", C.c_int32), ("B", C.c_int32), ("F", C.c_int32), ("dtype", C.c_int32), ("x_ld", C.c_int32), ("y_ld", C.c_int32),
+                ("window", C.c_int32), ("path_ld", C.c_int32), ("slope", C.c_double), ("x_dev", C.c_void_p), ("y_dev", C.c_void_p),
+                ("x_lens_dev", C.c_void_p), ("y_lens_dev", C.c_void_p), ("dist_dev", C.c_void_p), ("path_dev", C.c_void_p),
+                ("path_len_dev", C.c_void_p), ("acc_dev", C.c_void_p), ("moments_dev", C.c_void_p)]
+
+
+def dtw_args(B, x, y, x_ld, y_ld, dist, F=1, dtype=0, window=-1, slope=1.0, x_lens=None, y_lens=None, path=None, path_ld=0, path_len=None,
+             acc=None, moments=None):
+    """a filled DtwArgs block (device pointers as integers, 0 / None = NULL)"""
+    return DtwArgs(C.sizeof(DtwArgs), int(B), int(F), int(dtype), int(x_ld), int(y_ld), int(window), int(path_ld), float(slope), x or None,
+                   y or None, x_lens or None, y_lens or None, dist or None, path or None, path_len or None, acc or None, moments or None)
 
 
 class DttsConfig(C.Structure):
@@ -307,6 +326,14 @@ class Context:
                      int(dur_scale), 0, pred or None, tgt or None, mel_sums or None, mel_count or None, ssim_map or None, dur_pred or None,
                      mel2word or None, word_len or None, dur_sums or None, dur_gt or None)
         self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_LOSSES, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_LOSSES)")
+
+    def dtw(self, B, stream, **kw):
+        """dynamic time warping of B pairs (dtts_text2mel_fetch(DTTS_OUT_DTW); needs no weights and no encode).  Keywords: those of
+        ``dtw_args`` — x [B, x_ld, F] and y [B, y_ld, F] of dtype 0 = f32 / 1 = f64, x_lens / y_lens i32 [B] or None, window (< 0: no
+        band), slope, dist f64 [B] out, path i32 [B, 2, path_ld] + path_len i32 [B] out or None, acc f64 [B, x_ld, y_ld] out or None,
+        moments f64 [B, 2, 4] out or None (F = 1)."""
+        a = dtw_args(B, **kw)
+        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_DTW, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_DTW)")
 
     def fetch(self, what, dst, stream):
         self._chk(self.lib.dtts_text2mel_fetch(self.h, what, dst, stream), "dtts_text2mel_fetch")

@@ -30,6 +30,7 @@
 #include "stftdist.h"
 #include "istft.h"
 #include "losses.h"
+#include "dtw.h"
 
 // dtts_config.tune_flags: the bits the library honours are listed at TUNE_RELEASE_MASK (context.hip)
 #define DTTS_TUNE(h, bit) (((h)->tune & (bit)) != 0)
@@ -249,6 +250,8 @@ struct dtts_ctx {
     // workspace of the per-tile sums
     double* loss_win = nullptr;
     dtts::Arena a_loss;
+    // ---- dynamic time warping (dtts_text2mel_fetch(DTTS_OUT_DTW); dtw.hip): the workspace of the direction codes and of the costs (F > 1)
+    dtts::Arena a_dtw;
 };
 
 namespace dtts {
@@ -356,5 +359,6 @@ int spectral_forward(dtts_ctx* h, const dtts_spectral_args* a, hipStream_t strea
 int check_envelope(dtts_ctx* h, const char* me, int hop);   // istft.hip: the inverse's criterion on (window, hop) or the one refusal (0 = met)
 int griffin_lim(dtts_ctx* h, const dtts_griffinlim_args* a, hipStream_t stream);   // griffinlim.hip
 int losses_forward(dtts_ctx* h, const dtts_loss_args* a, hipStream_t stream);     // losses.hip
+int dtw_forward(dtts_ctx* h, const dtts_dtw_args* a, hipStream_t stream);          // dtw.hip (h may be null: the block is checked first)
 
 } // namespace dtts

@@ -520,6 +520,66 @@ typedef struct dtts_loss_args {
     double* dur_sums_dev;         /* DURATION, or NULL: skip the half */
     int32_t* dur_gt_dev;          /* DURATION, or NULL */
 } dtts_loss_args;
+/*
+ * DTTS_OUT_DTW: not a copy, needs NO encode and no weights — dynamic time warping of B pairs of sequences, the reference's
+ * utils/dtw.py::dtw (driven by scripts/pitch_dtw.py with the cost |x - y|) and accelerated_dtw with the cityblock cost, plus the F0
+ * moments pitch_dtw.py prints: dst = (dtts_dtw_args*), args->size = sizeof(*args).  Free-running inference predicts its own durations,
+ * so its mels and pitch tracks do not line up with the recordings frame for frame; this is the alignment the reference evaluates them by.
+ *   Pair b: x = x_dev[b] [N][F], y = y_dev[b] [M][F] (x_ld / y_ld rows per utterance; N = x_lens_dev[b], M = y_lens_dev[b], a NULL lens
+ *   pointer = the leading dimension), dtype 0 = f32, 1 = f64, F in 1 .. 128.
+ *   COST.  F = 1: c(i, j) = |x_i - y_j| in the input's own precision (f32 inputs: a float32 subtract, then widened; f64: a float64
+ *   subtract), which is what np.abs(x[i] - y[j]) gives for arrays of either dtype.  F > 1: the cityblock distance, each term
+ *   |double(x_ik) - double(y_jk)| added in fp64 with k ascending (scipy's cdist).
+ *   BAND.  window < 0: none (w = inf).  Otherwise cell (i, j) is live iff max(0, i - w) <= j <= min(M, i + w), every other cell is +inf.
+ *   RECURRENCE, fp64: D[i][j] = c(i, j) + min(D[i-1][j-1], s D[i][j-1], s D[i-1][j]) with D[-1][-1] = 0 and the rest of row -1 and
+ *   column -1 +inf; s = slope > 0 (the product is rounded before the min, as the reference's is; s = 1 issues no multiply).  One add of
+ *   an exact minimum per cell: the result does not depend on the order in which the cells are visited, and equals the reference's in
+ *   every bit.
+ *   PATH.  The reference's _traceback from (N - 1, M - 1): the FIRST minimum of the UNSCALED (D[i-1][j-1], D[i-1][j], D[i][j-1]), i.e.
+ *   diagonal, then i - 1, then j - 1 on ties (F0 tracks are full of exact ties: unvoiced frames are 0), until (0, 0); forward order.
+ *     dist_dev     f64 [B]: D[N-1][M-1];
+ *     path_dev     i32 [B][2][path_ld] or NULL: the row indices, then the column indices; path_ld >= x_ld + y_ld - 1; the entries
+ *                  [path_len, path_ld) of both rows are written as -1;
+ *     path_len_dev i32 [B], required with path_dev;
+ *     acc_dev      f64 [B][x_ld][y_ld] or NULL: the whole accumulated-cost matrix D (tests and diagnosis); cells outside [0, N) x [0, M)
+ *                  are left untouched;
+ *     moments_dev  f64 [B][2][4] or NULL (F = 1 only): mean, population standard deviation, skewness m3 / m2^1.5 and Fisher kurtosis
+ *                  m4 / m2^2 - 3 of x, then of y (np.std, scipy.stats.skew / kurtosis with bias=True): two passes in fp64, per lane in
+ *                  index order, then a fixed tree.  Zero variance gives NaN for the last two.
+ *   A BAD PAIR — a length <= 0 or above its leading dimension, or 0 <= window < |N - M| (the reference asserts) — cannot be refused on the
+ *   host, the lengths live on the device: it gets dist = NaN, path_len = 0 (its path rows all -1) and NaN moments; its neighbours are
+ *   unaffected.  Non-finite input values give unspecified numbers, but the traceback takes at most N + M - 2 moves, each decrementing an
+ *   index that is > 0: it ends and stays inside its buffers whatever the data.
+ * One wave per pair: a lane owns 16 consecutive rows, 64 lanes a strip of DTTS_DTW_STRIP_ROWS rows, and the wave sweeps the strip's
+ * anti-diagonals; a second small launch follows the recorded 2-bit directions backwards; for F > 1 a launch before them fills the cost
+ * workspace.  No host synchronisation unless a workspace grows; no floating-point atomics; a pair's outputs are bit-identical alone and
+ * in any batch, at any leading dimension.  DTTS_E_INVAL (naming the value) for a wrong size, B <= 0, F outside 1 .. 128, a dtype outside
+ * {0, 1}, a slope that is not finite and positive, a leading dimension outside 1 .. DTTS_DTW_MAX_LEN, path_ld < x_ld + y_ld - 1,
+ * moments with F > 1, a NULL x_dev / y_dev / dist_dev, path_dev without path_len_dev, or a misaligned pointer.  The argument block is
+ * checked before the handle, so that these refusals (reported through dtts_last_error(NULL) when h is NULL) can be exercised without a GPU.
+ */
+#define DTTS_OUT_DTW 15
+#define DTTS_DTW_STRIP_ROWS 1024    /* rows one pass of the wave covers: 64 lanes of 16 rows */
+#define DTTS_DTW_MAX_LEN 8192       /* largest x_ld / y_ld */
+typedef struct dtts_dtw_args {
+    int32_t size;                 /* sizeof(dtts_dtw_args) */
+    int32_t B;
+    int32_t F;                    /* features per row, 1 .. 128 */
+    int32_t dtype;                /* 0 = f32, 1 = f64 (x_dev and y_dev) */
+    int32_t x_ld, y_ld;           /* rows per utterance of x_dev / y_dev, 1 .. DTTS_DTW_MAX_LEN */
+    int32_t window;               /* < 0: no band */
+    int32_t path_ld;              /* entries per row of path_dev, >= x_ld + y_ld - 1 (ignored without path_dev) */
+    double slope;                 /* s, finite and > 0 */
+    const void* x_dev;            /* [B][x_ld][F] */
+    const void* y_dev;            /* [B][y_ld][F] */
+    const int32_t* x_lens_dev;    /* [B], or NULL = x_ld */
+    const int32_t* y_lens_dev;    /* [B], or NULL = y_ld */
+    double* dist_dev;             /* [B] */
+    int32_t* path_dev;            /* [B][2][path_ld], or NULL */
+    int32_t* path_len_dev;        /* [B], with path_dev */
+    double* acc_dev;              /* [B][x_ld][y_ld], or NULL */
+    double* moments_dev;          /* [B][2][4], or NULL */
+} dtts_dtw_args;
 DTTS_API int dtts_text2mel_fetch(dtts_handle h, int what, void* dst_dev, dtts_stream stream);
 
 /*
