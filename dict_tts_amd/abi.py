@@ -31,7 +31,11 @@ OUT_DTW = 15   # not a copy, needs no encode: dynamic time warping of a batch of
 DTW_STRIP_ROWS = 1024   # DTTS_DTW_STRIP_ROWS: rows one pass of the wave covers (the shape cases of tests/dtw_shapes.py derive from it)
 DTW_LANE_ROWS = 16      # rows of a strip one lane owns (DTW_STRIP_ROWS / 64)
 DTW_MAX_LEN = 8192      # DTTS_DTW_MAX_LEN
-SPECTRAL_FORWARD, SPECTRAL_INVERSE = 1, 2   # dtts_spectral_args.mode bits; both = the reference's denoise
+OUT_PITCH = 16   # not a copy, needs no encode: F0 tracks of a batch of waveforms (Praat's autocorrelation method), dst = a PitchArgs block
+PITCH_CANDIDATES = 15     # DTTS_PITCH_CANDIDATES
+PITCH_MAX_WINDOW = 2048   # DTTS_PITCH_MAX_WINDOW
+PITCH_MAX_FRAMES = 8192   # DTTS_PITCH_MAX_FRAMES
+SPECTRAL_FORWARD, SPECTRAL_INVERSE = 1, 2  # dtts_spectral_args.mode bits; both = the reference's denoise
 SPK_EMBED, SPK_ID = 1, 2   # dtts_text2mel_speakers kinds: fp32 [B,256] (use_spk_embed) / int64 [B] (use_spk_id)
 TIMER_VOC_CONV, TIMER_S2PA = 1, 2
 TIMER_STAGE_ENCODER, TIMER_STAGE_DICT_ENCODER, TIMER_STAGE_FVAE, TIMER_STAGE_HIFIGAN = 3, 4, 5, 6   # the reference's profile_infer names
@@ -100,6 +104,25 @@ def dtw_args(B, x, y, x_ld, y_ld, dist, F=1, dtype=0, window=-1, slope=1.0, x_le
     """a filled DtwArgs block (device pointers as integers, 0 / None = NULL)"""
     return DtwArgs(C.sizeof(DtwArgs), int(B), int(F), int(dtype), int(x_ld), int(y_ld), int(window), int(path_ld), float(slope), x or None,
                    y or None, x_lens or None, y_lens or None, dist or None, path or None, path_len or None, acc or None, moments or None)
+
+
+class PitchArgs(C.Structure):
+    """dtts_pitch_args (include/dicttts_hip.h): the argument block of dtts_text2mel_fetch(DTTS_OUT_PITCH)"""
+    _fields_ = [("size", C.c_int32), ("B", C.c_int32), ("wav_ld", C.c_int32), ("frames_ld", C.c_int32), ("sample_rate", C.c_int32), ("hop", C.c_int32),
+                ("pitch_floor", C.c_double), ("pitch_ceiling", C.c_double), ("voicing_threshold", C.c_double), ("silence_threshold", C.c_double),
+                ("octave_cost", C.c_double), ("octave_jump_cost", C.c_double), ("voiced_unvoiced_cost", C.c_double),
+                ("wav_dev", C.c_void_p), ("lens_dev", C.c_void_p), ("f0_dev", C.c_void_p), ("n_frames_dev", C.c_void_p), ("acf_dev", C.c_void_p),
+                ("cand_dev", C.c_void_p), ("n_cand_dev", C.c_void_p), ("intensity_dev", C.c_void_p), ("selected_dev", C.c_void_p)]
+
+
+def pitch_args(B, wav, wav_ld, frames_ld, f0, n_frames, sample_rate=22050, hop=256, pitch_floor=80.0, pitch_ceiling=750.0, voicing_threshold=0.6,
+               silence_threshold=0.03, octave_cost=0.01, octave_jump_cost=0.35, voiced_unvoiced_cost=0.14, lens=None, acf=None, cand=None,
+               n_cand=None, intensity=None, selected=None):
+    """a filled PitchArgs block (device pointers as integers, 0 / None = NULL; the defaults are the reference's and Praat's)"""
+    return PitchArgs(C.sizeof(PitchArgs), int(B), int(wav_ld), int(frames_ld), int(sample_rate), int(hop), float(pitch_floor), float(pitch_ceiling),
+                     float(voicing_threshold), float(silence_threshold), float(octave_cost), float(octave_jump_cost), float(voiced_unvoiced_cost),
+                     wav or None, lens or None, f0 or None, n_frames or None, acf or None, cand or None, n_cand or None, intensity or None,
+                     selected or None)
 
 
 class DttsConfig(C.Structure):
@@ -334,6 +357,14 @@ class Context:
         moments f64 [B, 2, 4] out or None (F = 1)."""
         a = dtw_args(B, **kw)
         self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_DTW, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_DTW)")
+
+    def pitch(self, B, stream, **kw):
+        """F0 tracks of B waveforms (dtts_text2mel_fetch(DTTS_OUT_PITCH); needs no weights and no encode).  Keywords: those of
+        ``pitch_args`` — wav f32 [B, wav_ld], lens i32 [B] or None, the analysis parameters, f0 f64 [B, frames_ld] and n_frames i32 [B] out,
+        and the optional stage outputs acf f64 [B, frames_ld, n_lag], cand f64 [B, frames_ld, 15, 2], n_cand i32 [B, frames_ld], intensity
+        f64 [B, frames_ld], selected i32 [B, frames_ld]."""
+        a = pitch_args(B, **kw)
+        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_PITCH, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_PITCH)")
 
     def fetch(self, what, dst, stream):
         self._chk(self.lib.dtts_text2mel_fetch(self.h, what, dst, stream), "dtts_text2mel_fetch")

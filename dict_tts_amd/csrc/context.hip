@@ -130,7 +130,7 @@ int dtts_create(const dtts_config* cfg, dtts_handle* out) {
     if (hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || h->n_cu <= 0) h->n_cu = 256;
     h->debug_rz = cfg->debug_redzone != 0;
     h->debug_misorder = cfg->debug_redzone == 2;
-    h->a_fft.debug = h->a_enc.debug = h->a_dec.debug = h->a_voc.debug = h->a_spk.debug = h->a_post.debug = h->a_stft.debug = h->a_spec.debug = h->a_loss.debug = h->a_dtw.debug = h->debug_rz;
+    h->a_fft.debug = h->a_enc.debug = h->a_dec.debug = h->a_voc.debug = h->a_spk.debug = h->a_post.debug = h->a_stft.debug = h->a_spec.debug = h->a_loss.debug = h->a_dtw.debug = h->a_pitch.debug = h->debug_rz;
     *out = h;
     return DTTS_OK;
 }
@@ -155,6 +155,7 @@ void dtts_destroy(dtts_handle h) {
     h->a_spec.release();
     h->a_loss.release();
     h->a_dtw.release();
+    h->a_pitch.release();
     for (auto& t : h->timers)
         for (auto e : t.pool) (void)hipEventDestroy(e);
     delete h;
@@ -261,7 +262,7 @@ int dtts_debug_poke(dtts_handle h, dtts_stream stream) {
     if (!h) return DTTS_E_INVAL;
     if (!h->debug_rz) return fail(h, DTTS_E_STATE, "dtts_debug_poke: the context was not created with dtts_config.debug_redzone = 1");
     char* target = nullptr;
-    for (Arena* a : {&h->a_voc, &h->a_enc, &h->a_dec, &h->a_fft, &h->a_spk, &h->a_post, &h->a_stft, &h->a_spec, &h->a_loss, &h->a_dtw})
+    for (Arena* a : {&h->a_voc, &h->a_enc, &h->a_dec, &h->a_fft, &h->a_spk, &h->a_post, &h->a_stft, &h->a_spec, &h->a_loss, &h->a_dtw, &h->a_pitch})
         if (!target && a->base && !a->bufs.empty()) target = a->base + a->bufs[0].start + a->bufs[0].bytes;
     if (!target && !h->rz_static.empty()) target = h->rz_static[0].p + h->rz_static[0].bytes;
     if (!target) return fail(h, DTTS_E_STATE, "dtts_debug_poke: nothing allocated yet");
@@ -282,7 +283,7 @@ int dtts_debug_check(dtts_handle h, int64_t* damaged_bytes, dtts_stream stream) 
         zones.push_back({(const unsigned char*)p0, (unsigned)n, (unsigned)names.size()});
         names.push_back(name);
     };
-    const std::pair<const char*, Arena*> arenas[] = {{"encode workspace", &h->a_enc}, {"decode workspace", &h->a_dec}, {"vocoder workspace", &h->a_voc}, {"fft workspace", &h->a_fft}, {"speaker workspace", &h->a_spk}, {"posterior workspace", &h->a_post}, {"stft workspace", &h->a_stft}, {"spectral workspace", &h->a_spec}, {"loss workspace", &h->a_loss}, {"dtw workspace", &h->a_dtw}};
+    const std::pair<const char*, Arena*> arenas[] = {{"encode workspace", &h->a_enc}, {"decode workspace", &h->a_dec}, {"vocoder workspace", &h->a_voc}, {"fft workspace", &h->a_fft}, {"speaker workspace", &h->a_spk}, {"posterior workspace", &h->a_post}, {"stft workspace", &h->a_stft}, {"spectral workspace", &h->a_spec}, {"loss workspace", &h->a_loss}, {"dtw workspace", &h->a_dtw}, {"pitch workspace", &h->a_pitch}};
     for (const auto& a : arenas) {
         const auto& bufs = a.second->bufs;
         const char* base = a.second->base;

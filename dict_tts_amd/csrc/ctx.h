@@ -31,6 +31,7 @@
 #include "istft.h"
 #include "losses.h"
 #include "dtw.h"
+#include "pitch.h"
 
 // dtts_config.tune_flags: the bits the library honours are listed at TUNE_RELEASE_MASK (context.hip)
 #define DTTS_TUNE(h, bit) (((h)->tune & (bit)) != 0)
@@ -252,6 +253,10 @@ struct dtts_ctx {
     dtts::Arena a_loss;
     // ---- dynamic time warping (dtts_text2mel_fetch(DTTS_OUT_DTW); dtw.hip): the workspace of the direction codes and of the costs (F > 1)
     dtts::Arena a_dtw;
+    // ---- F0 extraction (dtts_text2mel_fetch(DTTS_OUT_PITCH); pitch.hip): the window tables of every window length nsw seen so far (w [nsw], then
+    // wr [n_lag], fp64, made on the host) and the workspace of the stages between the launches
+    std::map<int, double*> pitch_tabs;
+    dtts::Arena a_pitch;
 };
 
 namespace dtts {
@@ -360,5 +365,6 @@ int check_envelope(dtts_ctx* h, const char* me, int hop);   // istft.hip: the in
 int griffin_lim(dtts_ctx* h, const dtts_griffinlim_args* a, hipStream_t stream);   // griffinlim.hip
 int losses_forward(dtts_ctx* h, const dtts_loss_args* a, hipStream_t stream);     // losses.hip
 int dtw_forward(dtts_ctx* h, const dtts_dtw_args* a, hipStream_t stream);          // dtw.hip (h may be null: the block is checked first)
+int pitch_forward(dtts_ctx* h, const dtts_pitch_args* a, hipStream_t stream);      // pitch.hip (the same)
 
 } // namespace dtts

@@ -4,8 +4,9 @@ dict_tts_amd/csrc/dtw.hip (dtts_text2mel_fetch(DTTS_OUT_DTW)).  Free-running inf
 tracks do not line up with the recordings frame for frame; these are the figures the reference evaluates them by.
 
 The recurrence is one add of an exact minimum per cell, so the device result equals the reference's in every bit — distance, accumulated
-cost and path, including the tie order of ``_traceback`` (diagonal, then i - 1, then j - 1 on the unscaled values).  F0 extraction itself
-(Praat / pyworld) stays outside: tracks come in as arrays, as the reference's ``f0/*.npy`` files do.
+cost and path, including the tie order of ``_traceback`` (diagonal, then i - 1, then j - 1 on the unscaled values).  Tracks come in as
+arrays, as the reference's ``f0/*.npy`` files do, or straight from the device's own F0 extraction (dict_tts_amd/pitch.py: Praat's
+autocorrelation method; ``pitch.pitch_dtw_from_wavs`` chains the two without a host round trip).  pyworld's extractors stay outside.
 """
 import math
 import os
@@ -158,22 +159,24 @@ def mel_dtw(mel_pred, mel_gt, pred_lens=None, gt_lens=None, ctx=None):
     return out
 
 
-def pair_f0_files(names):
+def pair_f0_files(names, ext=".npy"):
     """The file names of a reference ``f0/`` directory -> [(prediction, recording)] sorted by name: ``NAME_gt.npy`` is the recording of
     ``NAME.npy``.  (scripts/pitch_dtw.py pairs the two glob lists by position, which holds only while both happen to come back in the same
-    order.)  A recording without its prediction, or a prediction without its recording, is an error."""
-    names = sorted(os.path.basename(n) for n in names if n.endswith(".npy"))
-    gts = [n for n in names if n.endswith(GT_SUFFIX)]
-    preds = set(n for n in names if not n.endswith(GT_SUFFIX))
+    order.)  A recording without its prediction, or a prediction without its recording, is an error.  ext=".wav": the same rule for a
+    directory of waveforms (``NAME.wav`` / ``NAME_gt.wav``)."""
+    gt_suffix = "_gt" + ext
+    names = sorted(os.path.basename(n) for n in names if n.endswith(ext))
+    gts = [n for n in names if n.endswith(gt_suffix)]
+    preds = set(n for n in names if not n.endswith(gt_suffix))
     pairs = []
     for g in gts:
-        p = g[:-len(GT_SUFFIX)] + ".npy"
+        p = g[:-len(gt_suffix)] + ext
         if p not in preds:
             raise FileNotFoundError(f"{g} has no prediction {p}")
         preds.discard(p)
         pairs.append((p, g))
     if preds:
-        raise FileNotFoundError(f"{sorted(preds)[0]} has no recording {sorted(preds)[0][:-4] + GT_SUFFIX}")
+        raise FileNotFoundError(f"{sorted(preds)[0]} has no recording {sorted(preds)[0][:-len(ext)] + gt_suffix}")
     if not pairs:
-        raise FileNotFoundError("no *_gt.npy track found")
+        raise FileNotFoundError(f"no *{gt_suffix} track found")
     return pairs

@@ -580,6 +580,81 @@ typedef struct dtts_dtw_args {
     double* acc_dev;              /* [B][x_ld][y_ld], or NULL */
     double* moments_dev;          /* [B][2][4], or NULL */
 } dtts_dtw_args;
+/*
+ * DTTS_OUT_PITCH: not a copy, needs NO encode and no weights — F0 tracks of B waveforms by Boersma's autocorrelation method (Praat's
+ * "Sound: To Pitch (ac)" with the Hanning window), what the reference's data_gen_utils.py::get_pitch asks parselmouth for:
+ * dst = (dtts_pitch_args*), args->size = sizeof(*args).  The tracks are what DTTS_OUT_DTW consumes (f64, with n_frames as the lengths).
+ * All arithmetic is fp64; the float32 samples are widened on load.  Indices are 0-based; dx = 1 / sample_rate, dt = hop / sample_rate,
+ * L = lens_dev[b] (NULL = wav_ld), floor = pitch_floor, ceiling = min(pitch_ceiling, sample_rate / 2).
+ *   GEOMETRY.  q = (3.0 * sample_rate) / floor (one fp64 expression); nsw0 = floor(q), half = nsw0 / 2 - 1, nsw = 2 half (824 at
+ *   22050 Hz, 80 Hz); nper = floor(sample_rate / floor), halfper = nper / 2 + 1; maxlag = min(nsw / 3 + 2, nsw); brent_ixmax = nsw / 2;
+ *   n_lag = brent_ixmax + 1.  Frames: nF = (L - ceil(q)) div hop + 1 for L >= ceil(q), else none (= floor((L dx - 3 / floor) / dt) + 1,
+ *   from integers).  Frame k is centred at the fractional sample c_k = (L - nF hop + hop - 1) / 2 + k hop; left = floor(c_k) (2 c_k is
+ *   an integer), right = left + 1.
+ *   FRAME.  localMean = the mean of x[max(0, right - nper) .. min(L - 1, left + nper)]; g[j] = x[right - half + j] - localMean for
+ *   j = 0 .. nsw - 1; localPeak = max |g[j]| over j in [max(0, half - halfper), min(nsw, half + halfper)); intensity = localPeak >
+ *   globalPeak ? 1 : localPeak / globalPeak, where globalPeak = max |x - mean(x)| over the utterance; f[j] = g[j] w[j] with
+ *   w[j] = 0.5 - 0.5 cos(2 pi (j + 1) / (nsw + 1)); ac[l] = sum_j f[j] f[j + l] (j ascending, one accumulator per lag, whatever the
+ *   batch); r[0] = 1, r[l] = ac[l] / (ac[0] wr[l]) with wr the window's own normalised autocorrelation (made on the host in float64).
+ *   A frame with localPeak == 0 has r[l] = 0 for l >= 1 and only the unvoiced candidate.
+ *   CANDIDATES (15 slots; slot 0 is the unvoiced candidate (0, 0)).  For l = 2 .. min(maxlag, brent_ixmax) - 1 ascending, a maximum is
+ *   r[l] > voicing_threshold / 2 && r[l] > r[l-1] && r[l] >= r[l+1]; x0 = l + 0.5 (r[l+1] - r[l-1]) / (2 r[l] - r[l-1] - r[l+1]);
+ *   first-pass frequency sample_rate / x0 and strength sinc30(x0), reflected (s > 1: 1 / s).  A free slot takes it; with none free it
+ *   replaces the first slot >= 1 of the smallest s - octave_cost log2(floor / f) if its own figure is strictly larger.  Then every voiced
+ *   slot is refined: x* = the maximiser of sinc70 near its integer lag l, inside [l - 1, l + 1] (where the interpolant's analytic
+ *   derivative changes sign from + to -: a zero between two integer lags, or a kink on one, since the term set changes there; bracketed
+ *   around the parabolic vertex and closed in on by a regula falsi to 1e-12 samples); frequency =
+ *   sample_rate / x*, strength = sinc70(x*), reflected.  sincD(x) is Praat's NUM_interpolate_sinc of depth D on r taken symmetrically
+ *   over -brent_ixmax .. brent_ixmax, D clipped to the samples on either side (never at brent_ixmax - maxlag >= 70).
+ *   PATH.  corr = 0.01 / dt; a slot is voiced iff 0 < f < ceiling.  Local score: voicing_threshold + max(0, 2 - intensity (1 +
+ *   voicing_threshold) / silence_threshold) for an unvoiced slot, strength - octave_cost log2(ceiling / f) for a voiced one.
+ *   Transition cost: 0 between unvoiced slots, voiced_unvoiced_cost corr between a voiced and an unvoiced one, octave_jump_cost corr
+ *   |log2(f1 / f2)| between voiced ones (the kernel takes one log2 per slot and uses differences: log2(ceiling) - log2 f, |log2 f1 -
+ *   log2 f2|).  delta[k][c2] = max_c1 (delta[k-1][c1] - cost) + local[k][c2]; the first maximum in slot order
+ *   wins every tie, the last frame's first maximum starts the backtrack.
+ *     f0_dev        f64 [B][frames_ld]: the chosen slot's frequency, 0 where it is unvoiced by the rule above; 0 behind n_frames;
+ *     n_frames_dev  i32 [B];
+ *     acf_dev       f64 [B][frames_ld][n_lag] or NULL: r[0 .. brent_ixmax];
+ *     cand_dev      f64 [B][frames_ld][15][2] or NULL: frequency and strength per slot (the raw frequency, over-ceiling ones
+ *                   included), unused slots (0, 0);
+ *     n_cand_dev    i32 [B][frames_ld] or NULL;
+ *     intensity_dev f64 [B][frames_ld] or NULL;
+ *     selected_dev  i32 [B][frames_ld] or NULL: the slot the path chose, -1 behind n_frames.
+ *   frames_ld >= the frame count of a wav_ld-sample utterance.  Behind n_frames[b] the optional float outputs and n_cand are left
+ *   untouched.  An utterance whose length is outside 1 .. wav_ld, or too short for one frame (Praat raises there), cannot be refused on
+ *   the host: it gets n_frames = 0 and a zero row.  Non-finite samples give unspecified numbers; nothing is read behind an utterance's
+ *   own length.
+ * Four launches (utterance statistics; the autocorrelation, one workgroup per frame with the frame in LDS; the candidates, one wave per
+ * frame; the path, one wave per utterance), no atomics, no host synchronisation unless the workspace grows or a new window length
+ * uploads its tables; an utterance's outputs are bit-identical alone and in any batch, at any leading dimension.
+ * SUPPORTED: sample_rate 8000 .. 48000, hop 1 .. 4096, pitch_floor >= 10 with nsw in 32 .. DTTS_PITCH_MAX_WINDOW (floor above 32.3 Hz at
+ * 22050 Hz, above 70.3 Hz at 48000 Hz), pitch_ceiling > pitch_floor, voicing_threshold and silence_threshold > 0, the three costs >= 0, all
+ * finite; wav_ld 1 .. 2^26, frames_ld <= DTTS_PITCH_MAX_FRAMES.  DTTS_E_INVAL (naming the field) for anything else, a wrong size, B <= 0,
+ * a NULL wav_dev / f0_dev / n_frames_dev, or a misaligned pointer.  The argument block is checked before the handle, as DTTS_OUT_DTW's is.
+ */
+#define DTTS_OUT_PITCH 16
+#define DTTS_PITCH_CANDIDATES 15     /* Praat's default; fixed */
+#define DTTS_PITCH_MAX_WINDOW 2048   /* largest nsw (samples of one analysis window) */
+#define DTTS_PITCH_MAX_FRAMES 8192   /* largest frames_ld (= DTTS_DTW_MAX_LEN, the consumer's limit) */
+typedef struct dtts_pitch_args {
+    int32_t size;                 /* sizeof(dtts_pitch_args) */
+    int32_t B;
+    int32_t wav_ld;               /* samples per row of wav_dev */
+    int32_t frames_ld;            /* frames per row of the outputs */
+    int32_t sample_rate, hop;     /* the time step is hop / sample_rate s */
+    double pitch_floor, pitch_ceiling;                          /* Hz (the reference: 80, 750) */
+    double voicing_threshold, silence_threshold;                /* (0.6; Praat's 0.03) */
+    double octave_cost, octave_jump_cost, voiced_unvoiced_cost; /* (Praat's 0.01, 0.35, 0.14) */
+    const float* wav_dev;         /* [B][wav_ld] */
+    const int32_t* lens_dev;      /* [B], or NULL = wav_ld */
+    double* f0_dev;               /* [B][frames_ld] */
+    int32_t* n_frames_dev;        /* [B] */
+    double* acf_dev;              /* [B][frames_ld][n_lag], or NULL */
+    double* cand_dev;             /* [B][frames_ld][15][2], or NULL */
+    int32_t* n_cand_dev;          /* [B][frames_ld], or NULL */
+    double* intensity_dev;        /* [B][frames_ld], or NULL */
+    int32_t* selected_dev;        /* [B][frames_ld], or NULL */
+} dtts_pitch_args;
 DTTS_API int dtts_text2mel_fetch(dtts_handle h, int what, void* dst_dev, dtts_stream stream);
 
 /*
