@@ -35,6 +35,13 @@ OUT_PITCH = 16   # not a copy, needs no encode: F0 tracks of a batch of waveform
 PITCH_CANDIDATES = 15     # DTTS_PITCH_CANDIDATES
 PITCH_MAX_WINDOW = 2048   # DTTS_PITCH_MAX_WINDOW
 PITCH_MAX_FRAMES = 8192   # DTTS_PITCH_MAX_FRAMES
+DTTS_F64 = 2          # dtts_load_weight takes it for the "resample." tensors only
+PART_RESAMPLE = 64    # the band-limited resampler: "resample.filter" [n_win] f64 + "resample.num_table" [1] f64; rebuilt by every finalize that names it
+OUT_RESAMPLE = 17     # not a copy, needs no encode: resampy's kaiser-windowed sinc interpolation of a batch of waveforms, dst = a ResampleArgs block
+RESAMPLE_TILE = 256   # DTTS_RESAMPLE_TILE: consecutive outputs of one workgroup (the shape cases of tests/wavprep_shapes.py derive from it)
+OUT_LOUDNESS = 18     # not a copy, needs no encode or weights: BS.1770 integrated loudness and normalisation, dst = a LoudnessArgs block
+LOUD_SEGMENT = 256    # DTTS_LOUD_SEGMENT: samples of one segment of the K-weighting recurrence
+LOUD_TOO_SHORT, LOUD_SILENT, LOUD_PEAK = 1, 2, 4   # dtts_loudness_args status bits
 SPECTRAL_FORWARD, SPECTRAL_INVERSE = 1, 2  # dtts_spectral_args.mode bits; both = the reference's denoise
 SPK_EMBED, SPK_ID = 1, 2   # dtts_text2mel_speakers kinds: fp32 [B,256] (use_spk_embed) / int64 [B] (use_spk_id)
 TIMER_VOC_CONV, TIMER_S2PA = 1, 2
@@ -123,6 +130,37 @@ def pitch_args(B, wav, wav_ld, frames_ld, f0, n_frames, sample_rate=22050, hop=2
                      float(voicing_threshold), float(silence_threshold), float(octave_cost), float(octave_jump_cost), float(voiced_unvoiced_cost),
                      wav or None, lens or None, f0 or None, n_frames or None, acf or None, cand or None, n_cand or None, intensity or None,
                      selected or None)
+
+
+class ResampleArgs(C.Structure):
+    """dtts_resample_args (include/dicttts_hip.h): the argument block of dtts_text2mel_fetch(DTTS_OUT_RESAMPLE)"""
+    _fields_ = [("size", C.c_int32), ("B", C.c_int32), ("wav_ld", C.c_int32), ("out_ld", C.c_int32), ("sr_in", C.c_int32), ("sr_out", C.c_int32),
+                ("wav_dev", C.c_void_p), ("lens_dev", C.c_void_p), ("out_dev", C.c_void_p), ("out_lens_dev", C.c_void_p), ("out64_dev", C.c_void_p)]
+
+
+def resample_args(B, wav, wav_ld, out, out_ld, out_lens, sr_in, sr_out, lens=None, out64=None):
+    """a filled ResampleArgs block (device pointers as integers, 0 / None = NULL)"""
+    return ResampleArgs(C.sizeof(ResampleArgs), int(B), int(wav_ld), int(out_ld), int(sr_in), int(sr_out), wav or None, lens or None, out or None,
+                        out_lens or None, out64 or None)
+
+
+def resample_filter_key(half_window, num_table):
+    """what identifies a resampling filter: (n_win, num_table, hash of the table's bytes)"""
+    a = np.ascontiguousarray(np.asarray(half_window, np.float64).reshape(-1))
+    return (a.shape[0], int(num_table), hash(a.tobytes()))
+
+
+class LoudnessArgs(C.Structure):
+    """dtts_loudness_args (include/dicttts_hip.h): the argument block of dtts_text2mel_fetch(DTTS_OUT_LOUDNESS)"""
+    _fields_ = [("size", C.c_int32), ("B", C.c_int32), ("wav_ld", C.c_int32), ("blocks_ld", C.c_int32), ("sample_rate", C.c_int32), ("mode", C.c_int32),
+                ("target_lufs", C.c_double), ("wav_dev", C.c_void_p), ("lens_dev", C.c_void_p), ("lufs_dev", C.c_void_p), ("gain_dev", C.c_void_p),
+                ("status_dev", C.c_void_p), ("out_dev", C.c_void_p), ("z_dev", C.c_void_p), ("n_blocks_dev", C.c_void_p)]
+
+
+def loudness_args(B, wav, wav_ld, blocks_ld, sample_rate, lufs, gain, status, mode=0, target_lufs=-22.0, lens=None, out=None, z=None, n_blocks=None):
+    """a filled LoudnessArgs block (device pointers as integers, 0 / None = NULL; -22 LUFS is the reference's loud_norm target)"""
+    return LoudnessArgs(C.sizeof(LoudnessArgs), int(B), int(wav_ld), int(blocks_ld), int(sample_rate), int(mode), float(target_lufs), wav or None,
+                        lens or None, lufs or None, gain or None, status or None, out or None, z or None, n_blocks or None)
 
 
 class DttsConfig(C.Structure):
@@ -365,6 +403,32 @@ class Context:
         f64 [B, frames_ld], selected i32 [B, frames_ld]."""
         a = pitch_args(B, **kw)
         self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_PITCH, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_PITCH)")
+
+    def load_resample_filter(self, half_window, num_table):
+        """the resampler's plan: half_window f64 [n_win] (the right half of the windowed sinc, n_win - 1 a multiple of num_table) and its
+        table precision -> "resample.filter" / "resample.num_table" in fp64, then dtts_finalize_weights(DTTS_PART_RESAMPLE).  A context holds
+        ONE filter; ``resample_filter_key`` says which (units that share a context compare it before a call)"""
+        self.resample_filter_key = None
+        for name, v in (("resample.filter", half_window), ("resample.num_table", [num_table])):
+            a = np.ascontiguousarray(np.asarray(v, np.float64).reshape(-1))
+            shape = (C.c_int64 * 1)(a.shape[0])
+            self._chk(self.lib.dtts_load_weight(self.h, name.encode(), a.ctypes.data_as(C.c_void_p), shape, 1, DTTS_F64), f"dtts_load_weight({name})")
+        self.finalize(PART_RESAMPLE)
+        self.resample_filter_key = resample_filter_key(half_window, num_table)
+
+    def resample(self, B, stream, **kw):
+        """band-limited resampling of B waveforms (dtts_text2mel_fetch(DTTS_OUT_RESAMPLE); needs PART_RESAMPLE finalised, no encode).
+        Keywords: those of ``resample_args`` — wav f32 [B, wav_ld], lens i32 [B] or None, sr_in, sr_out, out f32 [B, out_ld] and out_lens
+        i32 [B] out, out64 f64 [B, out_ld] or None: the accumulators before their one rounding."""
+        a = resample_args(B, **kw)
+        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_RESAMPLE, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_RESAMPLE)")
+
+    def loudness(self, B, stream, **kw):
+        """BS.1770 integrated loudness of B waveforms and, with mode=1, their normalisation (dtts_text2mel_fetch(DTTS_OUT_LOUDNESS); needs no
+        weights and no encode).  Keywords: those of ``loudness_args`` — wav f32 [B, wav_ld], lens i32 [B] or None, sample_rate, target_lufs,
+        lufs f64 [B], gain f64 [B] and status i32 [B] out, out f32 [B, wav_ld] (mode 1), z f64 [B, blocks_ld] and n_blocks i32 [B] or None."""
+        a = loudness_args(B, **kw)
+        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_LOUDNESS, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_LOUDNESS)")
 
     def fetch(self, what, dst, stream):
         self._chk(self.lib.dtts_text2mel_fetch(self.h, what, dst, stream), "dtts_text2mel_fetch")

@@ -32,6 +32,8 @@
 #include "losses.h"
 #include "dtw.h"
 #include "pitch.h"
+#include "resample.h"
+#include "loudness.h"
 
 // dtts_config.tune_flags: the bits the library honours are listed at TUNE_RELEASE_MASK (context.hip)
 #define DTTS_TUNE(h, bit) (((h)->tune & (bit)) != 0)
@@ -40,6 +42,7 @@ namespace dtts {
 
 struct HostTensor {
     std::vector<float> f;
+    std::vector<double> d;   // the "resample." tensors arrive as DTTS_F64 and keep their precision (f is empty then)
     std::vector<int64_t> shape;
     int64_t numel() const {
         int64_t n = 1;
@@ -257,6 +260,16 @@ struct dtts_ctx {
     // wr [n_lag], fp64, made on the host) and the workspace of the stages between the launches
     std::map<int, double*> pitch_tabs;
     dtts::Arena a_pitch;
+    // ---- band-limited resampling (dtts_text2mel_fetch(DTTS_OUT_RESAMPLE); resample.hip): the plan of the last
+    // dtts_finalize_weights(DTTS_PART_RESAMPLE): the pairs (win[i], interp_delta[i]) in fp64.  The unit has no workspace
+    bool resample_ready = false;
+    const double2* rs_tab = nullptr;
+    int rs_n_win = 0, rs_num_table = 0;
+    // ---- BS.1770 loudness (dtts_text2mel_fetch(DTTS_OUT_LOUDNESS); loudness.hip): the block bounds (lo_j, hi_j) of the rate of the last
+    // call, as far as any call needed them, and the workspace of the segment states and partial sums
+    const int2* loud_bounds = nullptr;
+    int loud_bounds_rate = 0, loud_bounds_n = 0;
+    dtts::Arena a_loud;
 };
 
 namespace dtts {
@@ -366,5 +379,8 @@ int griffin_lim(dtts_ctx* h, const dtts_griffinlim_args* a, hipStream_t stream);
 int losses_forward(dtts_ctx* h, const dtts_loss_args* a, hipStream_t stream);     // losses.hip
 int dtw_forward(dtts_ctx* h, const dtts_dtw_args* a, hipStream_t stream);          // dtw.hip (h may be null: the block is checked first)
 int pitch_forward(dtts_ctx* h, const dtts_pitch_args* a, hipStream_t stream);      // pitch.hip (the same)
+int build_resample(dtts_ctx* h);  // resample.hip
+int resample_forward(dtts_ctx* h, const dtts_resample_args* a, hipStream_t stream);   // resample.hip (the same)
+int loudness_forward(dtts_ctx* h, const dtts_loudness_args* a, hipStream_t stream);   // loudness.hip (the same)
 
 } // namespace dtts

@@ -20,6 +20,8 @@ from .hparams import HIFIGAN_DEFAULTS, fill_abi_config, load_config_chain
 
 VOCODERS = {}
 _MELSPEC_CACHE = {}   # HifiGAN.wav2spec: one MelSpectrogram (with a context of its own) per front-end configuration
+_RESAMPLER_CACHE = {}   # HifiGAN.wav2spec(resample=True): one wavprep.Resampler per (file rate, audio_sample_rate)
+_LOUDNESS_CACHE = {}    # HifiGAN.wav2spec with hparams['loud_norm']: one wavprep.Loudness per audio_sample_rate
 
 
 def register_vocoder(cls):
@@ -159,26 +161,37 @@ class HifiGAN:
         return self.forward_batch(c, check=True).view(-1).cpu().numpy()
 
     @staticmethod
-    def wav2spec(wav_fn, return_linear=False):
-        """vocoders/base_vocoder.py:36-53 (process_utterance with vocoder='pwg'; loud_norm and trim_long_sil are not implemented) on the
-        device: wav_fn = a float waveform array, or the path of a 16-bit / float PCM wav at hparams['audio_sample_rate'] (nothing here
-        resamples) -> (wav padded to T * hop_size samples, log10-mel [T, n_mels]) as host numpy, the reference's return convention
-        (data_gen/tts/data_gen_utils.py:138-140)."""
+    def wav2spec(wav_fn, return_linear=False, resample=False):
+        """vocoders/base_vocoder.py:36-53 (process_utterance with vocoder='pwg'; trim_long_sil is not implemented) on the device:
+        wav_fn = a float waveform array, or the path of a 16-bit / float PCM wav -> (wav padded to T * hop_size samples, log10-mel
+        [T, n_mels]) as host numpy, the reference's return convention (data_gen/tts/data_gen_utils.py:138-140).  A file at another rate
+        than hparams['audio_sample_rate'] is refused unless resample=True, which loads it as the reference's librosa.load does
+        (wavprep.load_wav: kaiser_best on the device).  hparams['loud_norm'] normalises to -22 LUFS and applies the peak rule on the
+        device (wavprep.Loudness), as process_utterance does; the returned wav is the conditioned one."""
         if return_linear:
             raise NotImplementedError("wav2spec(return_linear=True): the linear-spectrogram branch of process_utterance "
                                       "(data_gen/tts/data_gen_utils.py:144-147) is not implemented on the HIP path")
         from . import melspec
         hp = {**hparams_mod.BIAOBEI_DEFAULTS, **hparams_mod.hparams}
-        if hp.get("loud_norm"):
-            raise NotImplementedError("wav2spec: loud_norm=True (pyloudnorm normalisation) is not implemented on the HIP path")
+        sr = int(hp["audio_sample_rate"])
         if isinstance(wav_fn, (str, os.PathLike)):
-            wav = melspec.read_wav(wav_fn, int(hp["audio_sample_rate"]))
+            if resample:
+                from . import wavprep
+                wav = wavprep.load_wav(wav_fn, sr, resampler_cache=_RESAMPLER_CACHE)
+            else:
+                wav = melspec.read_wav(wav_fn, sr)
         else:
             wav = np.asarray(wav_fn, dtype=np.float32).reshape(-1)
         key = tuple(hp[k] for k in ("fft_size", "hop_size", "win_size", "audio_num_mel_bins", "fmin", "fmax", "audio_sample_rate"))
         ms = _MELSPEC_CACHE.get(key)
         if ms is None:
             ms = _MELSPEC_CACHE[key] = melspec.MelSpectrogram(hp)
+        if hp.get("loud_norm"):
+            from . import wavprep
+            ln = _LOUDNESS_CACHE.get(sr)
+            if ln is None:
+                ln = _LOUDNESS_CACHE[sr] = wavprep.Loudness(sr, ctx=ms.ctx)
+            wav = ln.normalize(torch.from_numpy(np.ascontiguousarray(wav))[None], target=-22.0)[0][0].cpu().numpy()
         mel, _ = ms(wav)
         mel = mel[0].cpu().numpy()
         out = np.zeros(mel.shape[0] * ms.hop, np.float32)   # librosa_pad_lr(wav, fft_size, hop_size, 1): zeros up to the next multiple of hop

@@ -43,6 +43,7 @@ typedef void* dtts_stream; /* hipStream_t */
 
 #define DTTS_F32 0
 #define DTTS_I64 1
+#define DTTS_F64 2 /* dtts_load_weight takes it for the "resample." tensors only */
 
 /* Largest sense index (key_map / pinyin_map value) a word may carry: the S2PA kernel keeps 16 sense slots, index 0 = "no
  * sense".  zh-dict.json holds at most 6 pronunciations per character.  Larger indices are rejected (DTTS_E_INVAL) by dtts_dict_table_upload and, on the
@@ -179,6 +180,13 @@ DTTS_API int dtts_load_weight(dtts_handle h, const char* name, const void* host_
  * without "istft.window".  Optional: "istft.inv_mel_basis" [n_fft / 2 + 1][n_mels <= 128], the pseudo-inverse of the mel filterbank that
  * DTTS_OUT_GRIFFIN_LIM's mel input goes through (another shape or a non-finite entry: DTTS_E_INVAL); a plan finalised without it has none. */
 #define DTTS_PART_ISTFT 32
+/* The band-limited resampler (DTTS_OUT_RESAMPLE below): the right half of a windowed sinc, "resample.filter" [n_win] and the table
+ * precision "resample.num_table" [1] (samples per zero crossing), both loaded as DTTS_F64 (the only names dtts_load_weight takes that
+ * dtype for).  resampy's kaiser_best is n_win = 32769, num_table = 512.  n_win - 1 must be a multiple of num_table; supported: num_table a
+ * power of two <= 1024, n_win <= 2^17, finite entries, else DTTS_E_INVAL naming the value.  The plan is the table and
+ * interp_delta[i] = win[i + 1] - win[i] (the last entry 0), made here on the host in fp64 with one subtraction per entry and uploaded as
+ * pairs (win[i], interp_delta[i]).  Rebuilt by EVERY call that names it, like DTTS_PART_MELSPEC.  DTTS_E_NOENT without either tensor. */
+#define DTTS_PART_RESAMPLE 64
 /* Fold, repack into MFMA fragment order and upload.  Fails with DTTS_E_NOENT naming the first missing tensor. */
 DTTS_API int dtts_finalize_weights(dtts_handle h, int parts);
 
@@ -655,6 +663,113 @@ typedef struct dtts_pitch_args {
     double* intensity_dev;        /* [B][frames_ld], or NULL */
     int32_t* selected_dev;        /* [B][frames_ld], or NULL */
 } dtts_pitch_args;
+/*
+ * DTTS_OUT_RESAMPLE: not a copy, needs NO encode — band-limited resampling of B waveforms from sr_in to sr_out, librosa 0.9.2's
+ * resample(res_type = 'kaiser_best') = resampy 0.4.2's resample_f, with the filter of dtts_finalize_weights(DTTS_PART_RESAMPLE):
+ * dst = (dtts_resample_args*), args->size = sizeof(*args).  All arithmetic is fp64 on the float32 samples; win / delta are the plan's
+ * tables of n_win entries, num_table its precision, L = lens_dev[b] (NULL = wav_ld).
+ *   ratio = (double)sr_out / sr_in; n_out = (int)(L ratio); scale = min(1, ratio); inc = 1 / ratio; index_step = (int)(scale num_table)
+ *   (TRUNCATED, as resampy does: 235 for 48000 -> 22050, where scale num_table = 235.2).  For ratio < 1 every table entry is used
+ *   times ratio: win_s[i] = win[i] ratio, delta_s[i] = delta[i] ratio (one multiplication each; ratio >= 1: the entries themselves).
+ *   Output t = 0 .. n_out - 1:  tr = t inc; n = (int)tr; frac = scale (tr - n).
+ *     LEFT WING   f = frac num_table; off = (int)f; eta = f - off; for i = 0 .. min(n + 1, (n_win - off) / index_step) - 1 ascending:
+ *                 w = win_s[off + i index_step] + eta delta_s[off + i index_step]; acc += w x[n - i];
+ *     RIGHT WING  frac' = scale - frac; f, off, eta from frac' in the same way; for k = 0 .. min(L - n - 1, (n_win - off) / index_step) - 1
+ *                 ascending: w likewise; acc += w x[n + k + 1].
+ *   One fp64 accumulator per output, starting at 0, the left wing first, whatever the batch or the leading dimensions.  tr, frac, f, eta
+ *   and w are separate IEEE multiplications, subtractions and additions (never contracted: n and off are truncations of them); the tap
+ *   product acc += w x is one fma.  out[t] = (float)acc: ONE rounding, where the reference rounds its float32 y[t] after every tap
+ *   (the deliberate deviation).  out_lens[b] = ceil(L ratio), librosa's fix_length: the sample at index n_out is 0 when ceil > int, and
+ *   so is everything behind out_lens[b] in the row.
+ *     out_dev       f32 [B][out_ld];
+ *     out_lens_dev  i32 [B];
+ *     out64_dev     f64 [B][out_ld] or NULL: acc before its rounding (0 behind n_out).
+ *   An utterance whose length is outside 1 .. wav_ld, or whose out_lens would exceed out_ld, gets out_lens = 0 and a zero row.  Nothing
+ *   is read behind an utterance's own length.
+ * One launch: a workgroup owns DTTS_RESAMPLE_TILE consecutive outputs of one utterance (a lane one output) and stages the input span
+ * they read in LDS as fp64; the tables are read through L2.  No atomics, no workspace, no host synchronisation; an utterance's outputs
+ * are bit-identical alone and in any batch, at any leading dimension.
+ * SUPPORTED: sr_in, sr_out 8000 .. 48000, sr_in != sr_out, index_step >= 1, (n_win - 1) / index_step <= 2048 taps per wing,
+ * wav_ld 1 .. 2^26, out_ld >= 1.  DTTS_E_INVAL (naming the field) for anything else, a wrong size, B outside 1 .. 65535, a NULL wav_dev /
+ * out_dev / out_lens_dev or a misaligned pointer; the argument block is checked before the handle, as DTTS_OUT_DTW's is.  DTTS_E_NOENT
+ * without a finalised filter.
+ */
+#define DTTS_OUT_RESAMPLE 17
+#define DTTS_RESAMPLE_TILE 256 /* consecutive outputs of one workgroup (the shape cases of tests/wavprep_shapes.py derive from it) */
+typedef struct dtts_resample_args {
+    int32_t size;                 /* sizeof(dtts_resample_args) */
+    int32_t B;
+    int32_t wav_ld;               /* samples per row of wav_dev */
+    int32_t out_ld;               /* samples per row of out_dev / out64_dev */
+    int32_t sr_in, sr_out;
+    const float* wav_dev;         /* [B][wav_ld] */
+    const int32_t* lens_dev;      /* [B], or NULL = wav_ld */
+    float* out_dev;               /* [B][out_ld] */
+    int32_t* out_lens_dev;        /* [B] */
+    double* out64_dev;            /* [B][out_ld], or NULL */
+} dtts_resample_args;
+/*
+ * DTTS_OUT_LOUDNESS: not a copy, needs NO encode and no weights — ITU-R BS.1770 integrated loudness of B mono waveforms and, with
+ * mode = 1, their normalisation to target_lufs: pyloudnorm 0.1.1's Meter.integrated_loudness and normalize.loudness, then the reference's
+ * peak rule (data_gen_utils.py::process_utterance: loud_norm to -22 LUFS; `if abs(wav).max() > 1: wav = wav / abs(wav).max()`):
+ * dst = (dtts_loudness_args*), args->size = sizeof(*args).  All of it is fp64 on the float32 samples, without contraction; rate =
+ * sample_rate, L = lens_dev[b] (NULL = wav_ld; a length outside 0 .. wav_ld counts as 0).
+ *   K-WEIGHTING.  Two biquads whose coefficients are made on the host in fp64, the high shelf first:
+ *     w0 = 2 pi (fc / rate), alpha = sin w0 / (2 Q), c = cos w0;
+ *     high shelf (G = 4.0 dB, Q = 1 / sqrt 2, fc = 1500 Hz), A = 10^(G / 40), r = sqrt A:
+ *       b = A ((A + 1) + (A - 1) c + 2 r alpha), -2 A ((A - 1) + (A + 1) c), A ((A + 1) + (A - 1) c - 2 r alpha)
+ *       a = (A + 1) - (A - 1) c + 2 r alpha, 2 ((A - 1) - (A + 1) c), (A + 1) - (A - 1) c - 2 r alpha;
+ *     high pass (Q = 0.5, fc = 38 Hz): b = (1 + c) / 2, -(1 + c), (1 + c) / 2;  a = 1 + alpha, -2 c, 1 - alpha;
+ *     both divided by their a0 (passband gain 1).  Each runs in the transposed direct form II from a zero state, as scipy's lfilter does:
+ *     y = z1 + b0 x; z1 = (z2 + b1 x) - a1 y; z2 = b2 x - a2 y.
+ *   BLOCKS.  T = L / rate; n_blocks = (int)(rint((T - 0.4) / (0.4 0.25)) + 1), round half even.  Block j covers [lo_j, min(hi_j, L)),
+ *   lo_j = (int)(0.4 (j 0.25) rate), hi_j = (int)(0.4 (j 0.25 + 1) rate) (a host-made table); z_j = (sum of y^2 over it) / (0.4 rate):
+ *   the divisor is the full block even where the end of the utterance cuts the last one.
+ *   GATING.  l_j = -0.691 + 10 log10 z_j; absolute gate l_j >= -70; Gamma_r = -0.691 + 10 log10(mean of the gated z_j) - 10; the final
+ *   set is l_j > Gamma_r && l_j > -70; LUFS = -0.691 + 10 log10(mean of z_j over the final set).  Both means run over ascending j with
+ *   one accumulator.
+ *   STATUS.  bit 0 (DTTS_LOUD_TOO_SHORT): L < 0.4 rate, where pyloudnorm raises: lufs = NaN, gain = 1, n_blocks = 0, the row is copied
+ *   unchanged.  bit 1 (DTTS_LOUD_SILENT): no block passes the gates, where pyloudnorm returns -inf and its normalisation NaNs:
+ *   lufs = -inf, gain = 1, copied unchanged.  bit 2 (DTTS_LOUD_PEAK): the peak rule fired.
+ *   NORMALISE (mode 1).  gain = 10^((target_lufs - LUFS) / 20) in fp64; y = (float)gain x as ONE float32 multiplication (what numpy
+ *   1.23.5's value-based casting makes of float64 scalar * float32 array); p = max |y| over the utterance = (float)gain max |x| (the
+ *   product is monotone: no second pass); if p > 1: y = y / p, an IEEE float32 division.  Samples behind L are 0.
+ *     lufs_dev f64 [B]; gain_dev f64 [B]; status_dev i32 [B]; out_dev f32 [B][wav_ld] (mode 1; may be wav_dev itself);
+ *     z_dev f64 [B][blocks_ld] or NULL: the z_j (behind n_blocks untouched); n_blocks_dev i32 [B] or NULL.
+ * The cascade is a linear recurrence on four state values, s' = M s + g x.  Every utterance is cut into segments of DTTS_LOUD_SEGMENT
+ * samples anchored at its sample 0 (the cut never depends on the batch).  Launches: (1) a lane per segment runs it from a zero state and
+ * leaves its end state e_k and max |x|; (2) a wave per utterance chains the true start states in segment order, s_{k+1} = M^S s_k + e_k
+ * (M^S made on the host in fp64 by squaring M eight times), and joins the maxima; (3) a lane per segment runs it again from its true start state and
+ * leaves, for each of the at most six blocks it meets, the sum of y^2 over their common samples in ascending order; (4) a lane per block
+ * adds those partial sums in ascending segment order and divides, then a lane per utterance does the gating; (5, mode 1) an elementwise
+ * launch applies the gain.  No atomics; no host synchronisation unless the workspace grows or a longer block table is uploaded; an
+ * utterance's outputs are bit-identical alone and in any batch, at any leading dimension.
+ * SUPPORTED: sample_rate 8000 .. 48000, wav_ld 1 .. 2^26, mode 0 / 1, a finite target_lufs, blocks_ld >= max(1, the block count of a
+ * wav_ld-sample utterance).  DTTS_E_INVAL (naming the field) for anything else, a wrong size, B outside 1 .. 65535, a NULL wav_dev /
+ * lufs_dev / gain_dev / status_dev, a NULL out_dev in mode 1 or a misaligned pointer; the argument block is checked before the handle.
+ */
+#define DTTS_OUT_LOUDNESS 18
+#define DTTS_LOUD_SEGMENT 256 /* samples of one segment of the recurrence (the shape cases of tests/wavprep_shapes.py derive from it) */
+#define DTTS_LOUD_TOO_SHORT 1
+#define DTTS_LOUD_SILENT 2
+#define DTTS_LOUD_PEAK 4
+typedef struct dtts_loudness_args {
+    int32_t size;                 /* sizeof(dtts_loudness_args) */
+    int32_t B;
+    int32_t wav_ld;               /* samples per row of wav_dev and out_dev */
+    int32_t blocks_ld;            /* entries per row of z_dev */
+    int32_t sample_rate;
+    int32_t mode;                 /* 0 = measure only, 1 = measure and normalise */
+    double target_lufs;           /* (the reference: -22; trim_long_silences: -20) */
+    const float* wav_dev;         /* [B][wav_ld] */
+    const int32_t* lens_dev;      /* [B], or NULL = wav_ld */
+    double* lufs_dev;             /* [B] */
+    double* gain_dev;             /* [B] */
+    int32_t* status_dev;          /* [B] */
+    float* out_dev;               /* [B][wav_ld] (mode 1), or NULL */
+    double* z_dev;                /* [B][blocks_ld], or NULL */
+    int32_t* n_blocks_dev;        /* [B], or NULL */
+} dtts_loudness_args;
 DTTS_API int dtts_text2mel_fetch(dtts_handle h, int what, void* dst_dev, dtts_stream stream);
 
 /*

@@ -16,11 +16,16 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from dict_tts_amd import dtw  # noqa: E402
 
 
-def from_wavs(wav_dir, sample_rate, hop_size):
+def from_wavs(wav_dir, sample_rate, hop_size, resample=False):
     from dict_tts_amd import pitch
     from dict_tts_amd.melspec import read_wav
     pairs = dtw.pair_f0_files(os.listdir(wav_dir), ext=".wav")
-    load = lambda names: [read_wav(os.path.join(wav_dir, n), sample_rate) for n in names]
+    if resample:   # librosa.load: files at another rate are resampled on the device (kaiser_best)
+        from dict_tts_amd.wavprep import load_wav
+        cache = {}
+        load = lambda names: [load_wav(os.path.join(wav_dir, n), sample_rate, resampler_cache=cache) for n in names]
+    else:
+        load = lambda names: [read_wav(os.path.join(wav_dir, n), sample_rate) for n in names]
     pred, gt = load([p for p, _ in pairs]), load([g for _, g in pairs])
 
     def pad(wavs):
@@ -38,11 +43,12 @@ def main():
     ap.add_argument("dir", help="a generated_<steps>_ directory of the reference: its f0/ holds NAME.npy and NAME_gt.npy; with --wavs, a directory "
                                 "of NAME.wav and NAME_gt.wav")
     ap.add_argument("--wavs", action="store_true", help="DIR holds waveforms: extract the F0 tracks on the device first")
-    ap.add_argument("--sample-rate", type=int, default=22050, help="audio_sample_rate of the waveforms (--wavs; nothing is resampled)")
+    ap.add_argument("--sample-rate", type=int, default=22050, help="audio_sample_rate of the waveforms (--wavs; a file at another rate is refused unless --resample)")
+    ap.add_argument("--resample", action="store_true", help="with --wavs: resample files at another rate to --sample-rate on the device")
     ap.add_argument("--hop-size", type=int, default=256, help="hop_size: the tracker's time step in samples (--wavs)")
     args = ap.parse_args()
     if args.wavs:
-        res = from_wavs(args.dir, args.sample_rate, args.hop_size)
+        res = from_wavs(args.dir, args.sample_rate, args.hop_size, args.resample)
     else:
         f0 = os.path.join(args.dir, "f0")
         pairs = dtw.pair_f0_files(os.listdir(f0))

@@ -9,6 +9,7 @@ command on a machine that has the checkpoint and a GPU:
     python tools/validate_checkpoint.py /path/to/vocoder_ckpt_dir            # config.yaml + model_ckpt_steps_*.ckpt, or config.json + generator_v1
     python tools/validate_checkpoint.py /path/to/dir --mel-npy a.npy b.npy   # real mels [T,80] instead of synthetic ones
     python tools/validate_checkpoint.py /path/to/dir --wavs DIR              # mels made on the device from the recordings DIR/*.wav (HifiGAN.wav2spec)
+    python tools/validate_checkpoint.py /path/to/dir --wavs DIR --resample   # the same from recordings at any rate (resampled on the device)
     python tools/validate_checkpoint.py --synthetic                           # the repo's seeded generator (what CI can run)
 
 It prints, in this order:
@@ -110,6 +111,8 @@ def main():
     ap.add_argument("--frames", type=int, default=200)
     ap.add_argument("--mel-npy", nargs="*", default=[], help="real mels, each [T,80] float32 (.npy)")
     ap.add_argument("--wavs", help="directory of recordings (*.wav at audio_sample_rate): the mels are made from them on the device (HifiGAN.wav2spec)")
+    ap.add_argument("--resample", action="store_true", help="with --wavs: recordings at another rate are resampled to audio_sample_rate on the device "
+                                                            "(librosa.load's kaiser_best; wavprep.load_wav) instead of being refused")
     ap.add_argument("--gate", type=int, default=3, help="mels compared with the CPU oracle (fp32 torch; ~1 s per 100 frames)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -133,7 +136,7 @@ def main():
         files = sorted(glob.glob(os.path.join(a.wavs, "*.wav")))
         if not files:
             sys.exit(f"--wavs {a.wavs}: no *.wav files")
-        recordings, wav_mels = zip(*[vocoder.HifiGAN.wav2spec(fn) for fn in files])   # (the recording padded to whole hops, its mel)
+        recordings, wav_mels = zip(*[vocoder.HifiGAN.wav2spec(fn, resample=a.resample) for fn in files])   # (the recording padded to whole hops, its mel)
     mels = list(wav_mels) or [np.load(f).astype(np.float32) for f in a.mel_npy] or [synth.random_mel(100 + i, a.frames, f"val{i}") for i in range(a.mels)]
     print(f"checkpoint: {src}\n  upsample_rates {full_cfg['upsample_rates']}  initial channels {full_cfg['upsample_initial_channel']}  "
           f"resblock kernels {full_cfg['resblock_kernel_sizes']}\n  {len(mels)} mels, {sum(m.shape[0] for m in mels)} frames, "
