@@ -42,6 +42,16 @@ RESAMPLE_TILE = 256   # DTTS_RESAMPLE_TILE: consecutive outputs of one workgroup
 OUT_LOUDNESS = 18     # not a copy, needs no encode or weights: BS.1770 integrated loudness and normalisation, dst = a LoudnessArgs block
 LOUD_SEGMENT = 256    # DTTS_LOUD_SEGMENT: samples of one segment of the K-weighting recurrence
 LOUD_TOO_SHORT, LOUD_SILENT, LOUD_PEAK = 1, 2, 4   # dtts_loudness_args status bits
+PART_DISC = 128       # HifiGAN's discriminators: "disc.mpd.<i>.*" / "disc.msd.<i>.*", plain (folded) weights; built once per context
+OUT_DISC = 19         # not a copy, needs no encode: the sums behind a_p / a_s, r_* / f_*, fm_* of a batch of waveform pairs, dst = a DiscArgs block
+DISC_MPD, DISC_MSD, DISC_FM = 1, 2, 4   # dtts_disc_args.which bits
+DISC_DENSE_GROUPED = 8   # DTTS_DISC_DENSE_GROUPED: measurement aid, the grouped layers as block-diagonal dense layers
+DISC_N = 8            # DTTS_DISC_N: discriminators (5 periods, then 3 scales)
+DISC_MAX_FMAPS = 8    # DTTS_DISC_MAX_FMAPS
+DISC_MIN_LEN = 6      # DTTS_DISC_MIN_LEN: the shortest waveform the reference's discriminators accept
+DISC_TOO_SHORT = 1    # DTTS_DISC_TOO_SHORT (status bit)
+DISC_DENSE_TILE, DISC_GROUP_TILE, DISC_GROUP_TILE_WIDE = 32, 128, 64   # DTTS_DISC_*_TILE (the shape cases of tests/disc_shapes.py derive from them)
+DISC_PERIODS = (2, 3, 5, 7, 11)
 SPECTRAL_FORWARD, SPECTRAL_INVERSE = 1, 2  # dtts_spectral_args.mode bits; both = the reference's denoise
 SPK_EMBED, SPK_ID = 1, 2   # dtts_text2mel_speakers kinds: fp32 [B,256] (use_spk_embed) / int64 [B] (use_spk_id)
 TIMER_VOC_CONV, TIMER_S2PA = 1, 2
@@ -161,6 +171,24 @@ def loudness_args(B, wav, wav_ld, blocks_ld, sample_rate, lufs, gain, status, mo
     """a filled LoudnessArgs block (device pointers as integers, 0 / None = NULL; -22 LUFS is the reference's loud_norm target)"""
     return LoudnessArgs(C.sizeof(LoudnessArgs), int(B), int(wav_ld), int(blocks_ld), int(sample_rate), int(mode), float(target_lufs), wav or None,
                         lens or None, lufs or None, gain or None, status or None, out or None, z or None, n_blocks or None)
+
+
+class DiscArgs(C.Structure):
+    """dtts_disc_args (include/dicttts_hip.h): the argument block of dtts_text2mel_fetch(DTTS_OUT_DISC)"""
+    _fields_ = [("size", C.c_int32), ("B", C.c_int32), ("wav_ld", C.c_int32), ("which", C.c_int32), ("d_ld", C.c_int32), ("reserved", C.c_int32),
+                ("y_dev", C.c_void_p), ("y_hat_dev", C.c_void_p), ("lens_dev", C.c_void_p), ("sums_dev", C.c_void_p), ("counts_dev", C.c_void_p),
+                ("fm_dev", C.c_void_p), ("fm_counts_dev", C.c_void_p), ("d_dev", C.c_void_p), ("status_dev", C.c_void_p)]
+
+
+def disc_d_ld(wav_ld):
+    """entries per row of d_dev that dtts_disc_args asks for at wav_ld samples"""
+    return (int(wav_ld) + 63) // 64 + 16
+
+
+def disc_args(B, y, y_hat, wav_ld, sums, counts, status, which=DISC_MPD | DISC_MSD, lens=None, fm=None, fm_counts=None, d=None, d_ld=0):
+    """a filled DiscArgs block (device pointers as integers, 0 / None = NULL)"""
+    return DiscArgs(C.sizeof(DiscArgs), int(B), int(wav_ld), int(which), int(d_ld), 0, y or None, y_hat or None, lens or None, sums or None,
+                    counts or None, fm or None, fm_counts or None, d or None, status or None)
 
 
 class DttsConfig(C.Structure):
@@ -395,6 +423,13 @@ class Context:
         moments f64 [B, 2, 4] out or None (F = 1)."""
         a = dtw_args(B, **kw)
         self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_DTW, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_DTW)")
+
+    def disc(self, B, stream, **kw):
+        """HifiGAN's discriminators on B waveform pairs (dtts_text2mel_fetch(DTTS_OUT_DISC); needs PART_DISC finalised, no encode).  Keywords:
+        those of ``disc_args`` — y, y_hat f32 [B, wav_ld], lens i32 [B] or None, which (DISC_MPD | DISC_MSD | DISC_FM), sums f64 [B, 8, 4],
+        counts i64 [B, 8], status i32 [B] out, fm f64 [B, 8, 8] + fm_counts i64 [B, 8, 8] out (DISC_FM), d f32 [8, 2, B, d_ld] out or None."""
+        a = disc_args(B, **kw)
+        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_DISC, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_DISC)")
 
     def pitch(self, B, stream, **kw):
         """F0 tracks of B waveforms (dtts_text2mel_fetch(DTTS_OUT_PITCH); needs no weights and no encode).  Keywords: those of

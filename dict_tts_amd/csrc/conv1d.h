@@ -55,6 +55,8 @@ struct ConvParams {
     ConvSeg seg[2];
     const float* row_mask; // optional [B][T_out] per-row factor applied last to seg[0] only (the FVAE posterior's x_mask: a WaveNet layer's
                            // (x + res) * mask, the last layer's skip sum * mask, a plain conv * mask); null = no multiply (unchanged arithmetic)
+    int fixed_order;       // 1: an ENG_F32 layer never takes the few-rows fp32 kernel, whose use depends on the batch size and which sums a
+                           // row in parts: a row's bits then depend on the layer alone (disc.hip); 0 = the policy every other caller has
 };
 
 // Host-side description of a packed layer

@@ -780,7 +780,7 @@ static hipError_t launch_engine(const PackedConv& L, const ConvParams& p, hipStr
             q.w_lo2 = L.x6[2];
             if (launch_short_policy<ENG_BF16X6>(q, stream, &err)) return err;
         }
-        if (launch_short_policy<ENG_F32>(p, stream, &err)) return err;
+        if (!p.fixed_order && launch_short_policy<ENG_F32>(p, stream, &err)) return err;
         if (p.T_out <= 64 && !p.gate_H) return launch_cfg<ENGINE, 1, 1, 1, 4, CK>(p, stream);   // 32 t x 128 co
         if (p.T_out <= 64) return launch_cfg<ENGINE, 1, 2, 1, 4, CK>(p, stream);                // 32 t x 256 co
         return launch_cfg<ENGINE, 1, 2, 4, 1, CK>(p, stream);                                    // 128 t x 64 co

@@ -34,6 +34,7 @@
 #include "pitch.h"
 #include "resample.h"
 #include "loudness.h"
+#include "disc.h"
 
 // dtts_config.tune_flags: the bits the library honours are listed at TUNE_RELEASE_MASK (context.hip)
 #define DTTS_TUNE(h, bit) (((h)->tune & (bit)) != 0)
@@ -270,6 +271,12 @@ struct dtts_ctx {
     const int2* loud_bounds = nullptr;
     int loud_bounds_rate = 0, loud_bounds_n = 0;
     dtts::Arena a_loud;
+    // ---- HifiGAN's discriminators (dtts_text2mel_fetch(DTTS_OUT_DISC); disc.hip, gconv.hip): the packs of dtts_finalize_weights(DTTS_PART_DISC)
+    // and the one workspace every discriminator reuses (two activation buffers, the D outputs, the partial feature sums, the row tables)
+    bool disc_ready = false;
+    dtts::DiscMpd mpd[5];
+    dtts::DiscMsd msd[3];
+    dtts::Arena a_disc;
 };
 
 namespace dtts {
@@ -382,5 +389,7 @@ int pitch_forward(dtts_ctx* h, const dtts_pitch_args* a, hipStream_t stream);   
 int build_resample(dtts_ctx* h);  // resample.hip
 int resample_forward(dtts_ctx* h, const dtts_resample_args* a, hipStream_t stream);   // resample.hip (the same)
 int loudness_forward(dtts_ctx* h, const dtts_loudness_args* a, hipStream_t stream);   // loudness.hip (the same)
+int build_disc(dtts_ctx* h);      // disc.hip
+int disc_forward(dtts_ctx* h, const dtts_disc_args* a, hipStream_t stream);           // disc.hip (the same)
 
 } // namespace dtts

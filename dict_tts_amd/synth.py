@@ -259,6 +259,60 @@ def hifigan_state_dict(seed=1234, weight_norm=True, cfg=None):
     return sd
 
 
+# MultiPeriodDiscriminator / MultiScaleDiscriminator (modules/hifigan/hifigan.py:154-298): (C_out, C_in, k, stride, groups) per convolution
+DISC_PERIODS = (2, 3, 5, 7, 11)
+DISC_MPD_CONVS = ((32, 1, 5, 3, 1), (128, 32, 5, 3, 1), (512, 128, 5, 3, 1), (1024, 512, 5, 3, 1), (1024, 1024, 5, 1, 1))
+DISC_MSD_CONVS = ((128, 1, 15, 1, 1), (128, 128, 41, 2, 4), (256, 128, 41, 2, 16), (512, 256, 41, 4, 16), (1024, 512, 41, 4, 16),
+                  (1024, 1024, 41, 1, 16), (1024, 1024, 5, 1, 1))
+DISC_POST = (1, 1024, 3, 1, 1)
+
+
+def _disc_conv(sd, seed, name, spec, conv2d, norm, gain):
+    """one discriminator convolution in the checkpoint's form: weight_norm -> weight_g / weight_v, spectral_norm -> weight_orig /
+    weight_u / weight_v (u, v from power iterations on the matrix, so that u . (W v) IS its spectral norm, as after training)."""
+    cout, cin, k, _, groups = spec
+    shape = (cout, cin // groups, k, 1) if conv2d else (cout, cin // groups, k)
+    fan_in = (cin // groups) * k
+    w = randn(seed, name + ".w", shape, gain * np.sqrt(2.0 / fan_in))
+    ones = (1,) * (len(shape) - 1)
+    if norm == "weight":
+        nrm = np.sqrt((w.reshape(cout, -1).astype(np.float64) ** 2).sum(1)).reshape((cout,) + ones)
+        sd[name + ".weight_g"] = (nrm * (1.0 + 0.1 * randn(seed, name + ".g", (cout,) + ones))).astype(np.float32)
+        sd[name + ".weight_v"] = (w * np.float32(1.7)).astype(np.float32)
+    else:
+        m = w.reshape(cout, -1).astype(np.float64)
+        v = _rng(seed, name + ".v").standard_normal(m.shape[1])
+        for _ in range(8):
+            u = m @ v
+            u /= np.linalg.norm(u) + 1e-12
+            v = m.T @ u
+            v /= np.linalg.norm(v) + 1e-12
+        sd[name + ".weight_orig"] = w
+        sd[name + ".weight_u"] = u.astype(np.float32)
+        sd[name + ".weight_v"] = v.astype(np.float32)
+    sd[name + ".bias"] = randn(seed, name + ".b", (cout,), 0.05)
+
+
+def hifigan_disc_state_dict(seed=1234):
+    """numpy state dict of the vocoder task's ``model_disc`` (``state_dict.model_disc`` of a HifiGAN checkpoint with use_cond_disc and
+    use_spec_disc off): ``mpd.discriminators.<i>`` (weight norm) and ``msd.discriminators.<i>`` (the first under spectral norm, the others
+    under weight norm), He-scaled per layer.  A spectrally normalised layer has gain 1 whatever its stored scale, so the first scale
+    discriminator's outputs are driven by its biases; the others keep the input's scale."""
+    sd = {}
+    for i in range(len(DISC_PERIODS)):
+        p = f"mpd.discriminators.{i}"
+        for j, spec in enumerate(DISC_MPD_CONVS):
+            _disc_conv(sd, seed, f"{p}.convs.{j}", spec, True, "weight", 1.0)
+        _disc_conv(sd, seed, f"{p}.conv_post", DISC_POST, True, "weight", 0.7)
+    for i in range(3):
+        p = f"msd.discriminators.{i}"
+        norm = "spectral" if i == 0 else "weight"
+        for j, spec in enumerate(DISC_MSD_CONVS):
+            _disc_conv(sd, seed, f"{p}.convs.{j}", spec, False, norm, 1.0)
+        _disc_conv(sd, seed, f"{p}.conv_post", DISC_POST, False, norm, 0.7)
+    return sd
+
+
 # ----------------------------------------------------------------------------------------------------------
 # inputs
 # ----------------------------------------------------------------------------------------------------------

@@ -60,6 +60,19 @@ def find_vocoder_checkpoint(base_dir):
     raise FileNotFoundError(f"neither config.yaml nor config.json under vocoder_ckpt={base_dir!r}")
 
 
+def find_vocoder_discriminators(base_dir):
+    """-> (config dict, ``state_dict.model_disc`` of the newest model_ckpt_steps_*.ckpt, or None when the checkpoint carries none — a
+    ``generator_v1`` export never does).  The child ``find_vocoder_checkpoint`` leaves behind; dict_tts_amd/discriminators.py scores with it."""
+    config_path = f"{base_dir}/config.yaml"
+    if not os.path.exists(config_path):
+        return None, None
+    ckpts = sorted(glob.glob(f"{base_dir}/model_ckpt_steps_*.ckpt"), key=lambda x: int(re.findall(r"model_ckpt_steps_(\d+)\.ckpt", x)[0]))
+    if not ckpts:
+        raise FileNotFoundError(f"no model_ckpt_steps_*.ckpt under {base_dir}")
+    ckpt = torch.load(ckpts[-1], map_location="cpu", weights_only=False)
+    return load_config_chain(config_path), ckpt["state_dict"].get("model_disc")
+
+
 @register_vocoder
 class HifiGAN:
     """Same contract as the reference class: ``spec2wav(mel[T,80], **ignored) -> np.float32[T*hop]``."""
@@ -239,6 +252,31 @@ class HifiGAN:
             lens = lens.to(device=mels.device, dtype=torch.int32)
         wav = self.forward_batch(mels, lens)
         return mr(wav, wavs, None if lens is None else lens * self.hop)
+
+    def load_discriminators(self, path_or_state, hparams=None):
+        """the ``model_disc`` child of a vocoder checkpoint (path, loaded checkpoint, ``state_dict`` or the child itself) into this vocoder's
+        context, for ``adversarial_scores``.  hparams: the vocoder task's (use_cond_disc / use_spec_disc are refused by name)."""
+        from . import discriminators
+        self._disc = discriminators.Discriminators.from_checkpoint(path_or_state, hparams=hparams, ctx=self.ctx)
+        return self._disc
+
+    def adversarial_scores(self, mels, wavs, lens=None, feature_matching=False):
+        """spec2wav(mel) scored against the recording by HifiGAN's discriminators without leaving the device: ``a_p`` / ``a_s`` of the
+        reference's vocoder validation (tasks/vocoder/hifigan.py), and ``r_*`` / ``f_*`` (with feature_matching=True ``fm_f`` / ``fm_s``).
+        mels [B, T, n_mels] float32 cuda tensor, wavs [B, T * hop] float32 cuda tensor (the recordings: y), lens [B] valid frames or None
+        -> the dict of ``discriminators.Discriminators.scores``.  Needs ``load_discriminators`` first."""
+        disc = getattr(self, "_disc", None)
+        if disc is None or disc.ctx is not self.ctx:
+            raise abi.DttsError("adversarial_scores: no discriminators loaded into this vocoder's context (HifiGAN.load_discriminators(checkpoint))")
+        B, T, _ = mels.shape
+        if tuple(wavs.shape) != (B, T * self.hop):
+            raise abi.DttsError(f"adversarial_scores: wavs of shape {tuple(wavs.shape)}, the mels give {(B, T * self.hop)}")
+        if lens is not None:
+            lens = torch.as_tensor(lens)
+            frames = lens.to(device=mels.device, dtype=torch.int32)
+            samples = lens.to(torch.int32) * self.hop       # stays where the caller keeps it: host lengths are checked on the host
+        wav = self.forward_batch(mels, None if lens is None else frames)
+        return disc.scores(wavs, wav, None if lens is None else samples, feature_matching=feature_matching)
 
     def denoise(self, wav, lens=None, v=0.1):
         """the reference's post-filter ``denoise(wav, v)`` (vocoders/vocoder_utils.py:7-15: STFT, max(|S| - v, 0) with the phase kept,

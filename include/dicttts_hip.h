@@ -187,6 +187,14 @@ DTTS_API int dtts_load_weight(dtts_handle h, const char* name, const void* host_
  * interp_delta[i] = win[i + 1] - win[i] (the last entry 0), made here on the host in fp64 with one subtraction per entry and uploaded as
  * pairs (win[i], interp_delta[i]).  Rebuilt by EVERY call that names it, like DTTS_PART_MELSPEC.  DTTS_E_NOENT without either tensor. */
 #define DTTS_PART_RESAMPLE 64
+/* HifiGAN's discriminators (DTTS_OUT_DISC below; state_dict['model_disc'] of a vocoder checkpoint): "disc.mpd.<i>.convs.<j>.{weight,bias}"
+ * (i = 0 .. 4, j = 0 .. 4) and "disc.mpd.<i>.conv_post.{weight,bias}" = MultiPeriodDiscriminator.discriminators[i] (Conv2d weights
+ * [C_out][C_in][k][1]), "disc.msd.<i>.convs.<j>.*" (i = 0 .. 2, j = 0 .. 6) and "disc.msd.<i>.conv_post.*" = MultiScaleDiscriminator's
+ * (Conv1d weights [C_out][C_in / groups][k]).  The weights arrive PLAIN: weight norm and the first scale's spectral norm are folded by the
+ * caller (dict_tts_amd/discriminators.py).  Channel widths, kernels, strides, groups and the periods 2, 3, 5, 7, 11 are those of
+ * modules/hifigan/hifigan.py and not configurable: DTTS_E_INVAL naming the layer on any other shape, DTTS_E_NOENT naming the first missing
+ * tensor.  Built once per context. */
+#define DTTS_PART_DISC 128
 /* Fold, repack into MFMA fragment order and upload.  Fails with DTTS_E_NOENT naming the first missing tensor. */
 DTTS_API int dtts_finalize_weights(dtts_handle h, int parts);
 
@@ -770,6 +778,67 @@ typedef struct dtts_loudness_args {
     double* z_dev;                /* [B][blocks_ld], or NULL */
     int32_t* n_blocks_dev;        /* [B], or NULL */
 } dtts_loudness_args;
+/*
+ * DTTS_OUT_DISC: not a copy, needs NO encode — the sums behind what tasks/vocoder/hifigan.py logs for a vocoder (a_p / a_s, r_p / f_p /
+ * r_s / f_s, fm_f / fm_s; modules/hifigan/hifigan.py: generator_loss, discriminator_loss, feature_loss) for B waveform pairs, with the
+ * discriminators of dtts_finalize_weights(DTTS_PART_DISC): dst = (dtts_disc_args*), args->size = sizeof(*args).  y is the recording, y_hat
+ * the generated waveform; pair b has L = lens_dev[b] samples of both (NULL = wav_ld).  Every utterance is scored AS IF ALONE AT ITS OWN
+ * LENGTH: nothing of a neighbour, of the padding behind L or of the batch enters, and its sums are bit-identical alone and in any batch.
+ *   Discriminator d = 0 .. 4: MultiPeriodDiscriminator.discriminators[d] (periods 2, 3, 5, 7, 11): the waveform reflect padded on the right
+ *   to a multiple of p (index L + k reads sample L - 2 - k), folded to [rows][p]; per column Conv(1 -> 32 -> 128 -> 512 -> 1024, k = 5,
+ *   stride 3, pad 2), Conv(1024 -> 1024, k = 5, pad 2), each followed by leaky_relu(0.1), then conv_post (1024 -> 1, k = 3, pad 1).
+ *   d = 5 .. 7: MultiScaleDiscriminator.discriminators[d - 5] on the waveform pooled d - 5 times by AvgPool1d(4, 2, padding = 1) (the edges
+ *   divide by 4 too): Conv1d 1 -> 128 (k = 15), 128 -> 128 (k = 41, s 2, g 4), 128 -> 256 (k = 41, s 2, g 16), 256 -> 512 (k = 41, s 4,
+ *   g 16), 512 -> 1024 (k = 41, s 4, g 16), 1024 -> 1024 (k = 41, g 16), 1024 -> 1024 (k = 5), leaky_relu(0.1) after each, conv_post
+ *   (1024 -> 1, k = 3).  All of it in fp32 with exact fp32 products; D is the flattened conv_post output.
+ *     sums_dev f64 [B][8][4]: sum (1 - D(y))^2, sum D(y)^2, sum (1 - D(y_hat))^2, sum D(y_hat)^2 over the n outputs of discriminator d;
+ *     counts_dev i64 [B][8]: n.  fm_dev f64 [B][8][8] / fm_counts_dev i64 [B][8][8] (DTTS_DISC_FM): per feature map l (the activated
+ *     output of convolution l, conv_post's output last; 6 maps for d < 5, 8 for d >= 5, the rest untouched) sum |fmap(y) - fmap(y_hat)|
+ *     and its element count.  d_dev f32 [8][2][B][d_ld] or NULL: the D outputs themselves (y, then y_hat), in the reference's flattened
+ *     order.  status_dev i32 [B]: DTTS_DISC_TOO_SHORT where L is outside DTTS_DISC_MIN_LEN .. wav_ld (the reference's reflect padding
+ *     raises below 6 samples): that pair's counts are 0 and its sums 0.  Rows of discriminators `which` leaves out stay untouched.
+ * The host forms mean (1 - D)^2 = sums / counts per discriminator and averages over the discriminators (a_*, r_*, f_*), and
+ * fm = 2 * sum over d and l of fm / fm_counts; pooled figures divide the sums over the batch by the counts over the batch, which equals the
+ * reference's batch means when all lengths are equal.  All fp64 sums run in a fixed order without atomics.  The discriminators run one after
+ * another on `stream` over one reused workspace, the batch in chunks of utterances that keep it below DTTS_DISC_WS_BYTES (a single
+ * utterance may exceed it); no host synchronisation unless the workspace grows.
+ * DTTS_E_INVAL (naming the field): a wrong size, B outside 1 .. 65535, wav_ld outside DTTS_DISC_MIN_LEN .. 2^24, `which` without
+ * DTTS_DISC_MPD or DTTS_DISC_MSD or with unknown bits, DTTS_DISC_FM without fm_dev / fm_counts_dev, d_dev with d_ld below
+ * (wav_ld + 63) / 64 + 16 entries (abi.disc_d_ld), a NULL y_dev / y_hat_dev / sums_dev / counts_dev / status_dev, a misaligned pointer; the
+ * argument block is checked before the handle, as DTTS_OUT_DTW's is.  DTTS_E_STATE before dtts_finalize_weights(DTTS_PART_DISC).
+ */
+#define DTTS_OUT_DISC 19
+#define DTTS_DISC_MPD 1
+#define DTTS_DISC_MSD 2
+#define DTTS_DISC_FM 4
+#define DTTS_DISC_DENSE_GROUPED 8 /* measurement aid (tools/disc_bench.py): the scale discriminators' grouped layers run as block-diagonal DENSE layers
+                                   * on the dense kernels (16 x / 4 x the work), the form the library had before its grouped kernel; same results up
+                                   * to summation order.  The first such call packs those layers on the host and synchronises. */
+#define DTTS_DISC_N 8            /* discriminators: 5 periods, then 3 scales */
+#define DTTS_DISC_MAX_FMAPS 8    /* feature maps of a scale discriminator (a period discriminator has 6) */
+#define DTTS_DISC_MIN_LEN 6      /* shortest waveform the reference's MultiPeriodDiscriminator accepts (period 11 pads 5 samples by reflection) */
+#define DTTS_DISC_TOO_SHORT 1
+#define DTTS_DISC_DENSE_TILE 32  /* output rows per tile of the dense layers; DTTS_DISC_GROUP_TILE: of the grouped kernel's narrow / wide form */
+#define DTTS_DISC_GROUP_TILE 128
+#define DTTS_DISC_GROUP_TILE_WIDE 64
+#define DTTS_DISC_WS_BYTES (3ll << 30)
+typedef struct dtts_disc_args {
+    int32_t size;                 /* sizeof(dtts_disc_args) */
+    int32_t B;
+    int32_t wav_ld;               /* samples per row of y_dev / y_hat_dev */
+    int32_t which;                /* DTTS_DISC_MPD | DTTS_DISC_MSD | DTTS_DISC_FM */
+    int32_t d_ld;                 /* entries per row of d_dev */
+    int32_t reserved;             /* 0 */
+    const float* y_dev;           /* [B][wav_ld] */
+    const float* y_hat_dev;       /* [B][wav_ld] */
+    const int32_t* lens_dev;      /* [B], or NULL = wav_ld */
+    double* sums_dev;             /* [B][8][4] */
+    int64_t* counts_dev;          /* [B][8] */
+    double* fm_dev;               /* [B][8][8], or NULL */
+    int64_t* fm_counts_dev;       /* [B][8][8], or NULL */
+    float* d_dev;                 /* [8][2][B][d_ld], or NULL */
+    int32_t* status_dev;          /* [B] */
+} dtts_disc_args;
 DTTS_API int dtts_text2mel_fetch(dtts_handle h, int what, void* dst_dev, dtts_stream stream);
 
 /*

@@ -11,6 +11,7 @@ command on a machine that has the checkpoint and a GPU:
     python tools/validate_checkpoint.py /path/to/dir --wavs DIR              # mels made on the device from the recordings DIR/*.wav (HifiGAN.wav2spec)
     python tools/validate_checkpoint.py /path/to/dir --wavs DIR --resample   # the same from recordings at any rate (resampled on the device)
     python tools/validate_checkpoint.py --synthetic                           # the repo's seeded generator (what CI can run)
+    python tools/validate_checkpoint.py /path/to/dir --wavs DIR --disc       # + a_p / a_s, r_* / f_* of the checkpoint's own discriminators
 
 It prints, in this order:
   1. the static decision at load time (dict_tts_amd.vocoder.HifiGAN, AUTO): worst-case bound and propagated-RMS estimate of the fp16
@@ -27,6 +28,10 @@ It prints, in this order:
   4c. the multi-resolution STFT distance sc / mag (HifiGAN.stft_distance, the other pair of figures of that validation, every bin of three
      resolutions instead of 80 pooled ones) of the fp16 waveform against the bf16x3 waveform of the same mels — the ERROR of the fp16 mode on
      this checkpoint, measured on the device without an oracle — and, with --wavs, of the vocoder's output against the recordings;
+  4d. with --disc: what the training log shows next to ``mel`` — a_p / a_s (generator_loss of the MultiPeriodDiscriminator /
+     MultiScaleDiscriminator outputs on the vocoder's waveform), r_p / f_p / r_s / f_s (discriminator_loss) and fm_f / fm_s, from the
+     checkpoint's ``state_dict.model_disc`` (dict_tts_amd/discriminators.py); against the recordings with --wavs, else against the bf16x3
+     waveform of the same mels.  Says so when the checkpoint carries no model_disc (a generator_v1 export never does);
   5. the verdict: the mode HifiGAN(precision=None) runs this checkpoint in, and whether that mode met the gate.
 Exit code 0 = the mode AUTO chose meets the gate with a clean guard; 1 otherwise.
 """
@@ -113,6 +118,7 @@ def main():
     ap.add_argument("--wavs", help="directory of recordings (*.wav at audio_sample_rate): the mels are made from them on the device (HifiGAN.wav2spec)")
     ap.add_argument("--resample", action="store_true", help="with --wavs: recordings at another rate are resampled to audio_sample_rate on the device "
                                                             "(librosa.load's kaiser_best; wavprep.load_wav) instead of being refused")
+    ap.add_argument("--disc", action="store_true", help="also score the waveforms with the checkpoint's discriminators (state_dict.model_disc): a_p / a_s, r_*, f_*, fm_*")
     ap.add_argument("--gate", type=int, default=3, help="mels compared with the CPU oracle (fp32 torch; ~1 s per 100 frames)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -124,9 +130,11 @@ def main():
         if a.scale_resblocks != 1.0:
             sd = {k: (v * a.scale_resblocks if k.startswith("resblocks.") and k.endswith("weight_g") else v) for k, v in sd.items()}
         src = f"synthetic generator (seed 1234, ResBlock gains x{a.scale_resblocks:g})"
+        model_disc, disc_hp = (synth.hifigan_disc_state_dict(1234) if a.disc else None), None
     elif a.ckpt_dir:
         cfg, sd = vocoder.find_vocoder_checkpoint(a.ckpt_dir)
         src = a.ckpt_dir
+        disc_hp, model_disc = vocoder.find_vocoder_discriminators(a.ckpt_dir) if a.disc else (None, None)
     else:
         ap.error("give a checkpoint directory or --synthetic")
     full_cfg = {**vocoder.HIFIGAN_DEFAULTS, **(cfg or {})}
@@ -232,6 +240,26 @@ def main():
             rec[:min(n, len(recordings[i]))] = recordings[i][:n]
             line += f"  {VOC_NAMES.get(auto.precision, auto.precision)} against the recording: {fmt(auto.stft_distance(mel, T_(rec[None]).cuda()))}"
         print(line)
+
+    if a.disc:
+        print("\n4d. discriminator scores (a = mean (1 - D(y_hat))^2, r = mean (1 - D(y))^2, f = mean D(y_hat)^2; p = multi-period, s = multi-scale)"
+              + (" (synthetic weights: the values mean nothing)" if a.synthetic else ""))
+        if model_disc is None:
+            print("   this checkpoint carries no model_disc (state_dict.model_disc): nothing to score with")
+        else:
+            auto.load_discriminators(model_disc, hparams=disc_hp)
+            for i, m in enumerate(mels[:max(a.gate, 1)]):
+                mel = T_(m[None]).cuda()
+                n = m.shape[0] * auto.hop
+                if recordings:
+                    rec = np.zeros(n, np.float32)
+                    rec[:min(n, len(recordings[i]))] = recordings[i][:n]
+                    y, against = T_(rec[None]).cuda(), "the recording"
+                else:
+                    y, against = exact.forward_batch(mel), "the bf16x3 waveform"
+                r = auto.adversarial_scores(mel, y, feature_matching=True)
+                print(f"   mel {i} ({m.shape[0]} frames) against {against}:  " + "  ".join(
+                    f"{k} {float(r[k][0]):.6f}" for k in ("a_p", "a_s", "r_p", "f_p", "r_s", "f_s", "fm_f", "fm_s")))
 
     chosen = VOC_NAMES.get(auto.precision, str(auto.precision))
     chosen_key = "f16" if auto.precision == abi.VOC_F16 else "bf16x3"
