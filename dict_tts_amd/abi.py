@@ -52,6 +52,13 @@ DISC_MIN_LEN = 6      # DTTS_DISC_MIN_LEN: the shortest waveform the reference's
 DISC_TOO_SHORT = 1    # DTTS_DISC_TOO_SHORT (status bit)
 DISC_DENSE_TILE, DISC_GROUP_TILE, DISC_GROUP_TILE_WIDE = 32, 128, 64   # DTTS_DISC_*_TILE (the shape cases of tests/disc_shapes.py derive from them)
 DISC_PERIODS = (2, 3, 5, 7, 11)
+PART_SPKENC = 256     # the d-vector speaker encoder: "spkenc.<VoiceEncoder state-dict key>", "spkenc.mel_basis", "spkenc.window"; built once per context
+OUT_SPKENC = 20       # not a copy, needs no encode: utterance embeddings of a batch of recordings (or of mel sequences), dst = a SpkencArgs block
+SPKENC_FROM_WAV, SPKENC_FROM_MELS = 0, 1             # dtts_spkenc_args.mode
+SPKENC_PAD_CONSTANT, SPKENC_PAD_REFLECT = 0, 1       # dtts_spkenc_args.pad_mode
+SPKENC_TILE_M = 32    # DTTS_SPKENC_TILE_M: the most sequences per workgroup of the recurrent kernel (tile_m = 16 is the other form)
+SPKENC_MAX_T = 4096   # DTTS_SPKENC_MAX_T
+SPKENC_HOP, SPKENC_PART, SPKENC_MELS, SPKENC_DIM = 160, 160, 40, 256
 SPECTRAL_FORWARD, SPECTRAL_INVERSE = 1, 2  # dtts_spectral_args.mode bits; both = the reference's denoise
 SPK_EMBED, SPK_ID = 1, 2   # dtts_text2mel_speakers kinds: fp32 [B,256] (use_spk_embed) / int64 [B] (use_spk_id)
 TIMER_VOC_CONV, TIMER_S2PA = 1, 2
@@ -189,6 +196,34 @@ def disc_args(B, y, y_hat, wav_ld, sums, counts, status, which=DISC_MPD | DISC_M
     """a filled DiscArgs block (device pointers as integers, 0 / None = NULL)"""
     return DiscArgs(C.sizeof(DiscArgs), int(B), int(wav_ld), int(which), int(d_ld), 0, y or None, y_hat or None, lens or None, sums or None,
                     counts or None, fm or None, fm_counts or None, d or None, status or None)
+
+
+class SpkencArgs(C.Structure):
+    """dtts_spkenc_args (include/dicttts_hip.h): the argument block of dtts_text2mel_fetch(DTTS_OUT_SPKENC)"""
+    _fields_ = [("size", C.c_int32), ("B", C.c_int32), ("wav_ld", C.c_int32), ("mode", C.c_int32), ("frame_step", C.c_int32), ("pad_mode", C.c_int32),
+                ("tile_m", C.c_int32), ("reserved", C.c_int32), ("min_coverage", C.c_double), ("wav_dev", C.c_void_p), ("lens_dev", C.c_void_p),
+                ("embed_dev", C.c_void_p), ("n_partials_dev", C.c_void_p), ("partials_dev", C.c_void_p), ("mel_dev", C.c_void_p),
+                ("hseq_dev", C.c_void_p * 3)]
+
+
+def spkenc_max_partials(wav_ld, frame_step):
+    """dtts_spkenc_max_partials: partials of a wav_ld-sample utterance before the coverage rule = rows per utterance of partials / hseq"""
+    steps = max(1, (int(wav_ld) // SPKENC_HOP + 1) - SPKENC_PART + int(frame_step) + 1)
+    return (steps - 1) // int(frame_step) + 1
+
+
+def spkenc_frames_ld(wav_ld, frame_step):
+    """dtts_spkenc_frames_ld: mel frames per utterance of mel_dev at wav_ld samples"""
+    stop = SPKENC_HOP * ((spkenc_max_partials(wav_ld, frame_step) - 1) * int(frame_step) + SPKENC_PART)
+    return 1 + max(int(wav_ld), stop) // SPKENC_HOP
+
+
+def spkenc_args(B, wav, wav_ld, embed, n_partials, mode=SPKENC_FROM_WAV, frame_step=77, min_coverage=0.75, pad_mode=SPKENC_PAD_CONSTANT, tile_m=0,
+                lens=None, partials=None, mel=None, hseq=(None, None, None)):
+    """a filled SpkencArgs block (device pointers as integers, 0 / None = NULL)"""
+    return SpkencArgs(C.sizeof(SpkencArgs), int(B), int(wav_ld), int(mode), int(frame_step), int(pad_mode), int(tile_m), 0, float(min_coverage),
+                      wav or None, lens or None, embed or None, n_partials or None, partials or None, mel or None,
+                      (C.c_void_p * 3)(*[v or None for v in hseq]))
 
 
 class DttsConfig(C.Structure):
@@ -430,6 +465,14 @@ class Context:
         counts i64 [B, 8], status i32 [B] out, fm f64 [B, 8, 8] + fm_counts i64 [B, 8, 8] out (DISC_FM), d f32 [8, 2, B, d_ld] out or None."""
         a = disc_args(B, **kw)
         self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_DISC, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_DISC)")
+
+    def spkenc(self, B, stream, **kw):
+        """utterance embeddings of B recordings or mel sequences (dtts_text2mel_fetch(DTTS_OUT_SPKENC); needs PART_SPKENC finalised, no
+        encode).  Keywords: those of ``spkenc_args`` — wav f32 [B, wav_ld] (SPKENC_FROM_MELS: mels f32 [B, wav_ld, 40]), lens i32 [B] or
+        None, frame_step, min_coverage, pad_mode, tile_m, embed f32 [B, 256] and n_partials i32 [B] out, partials f32 [B, P, 256], mel f32
+        [B, F, 40], hseq 3 x f32 [B, P, T, 256] out or None (P = spkenc_max_partials, F = spkenc_frames_ld)."""
+        a = spkenc_args(B, **kw)
+        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_SPKENC, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_SPKENC)")
 
     def pitch(self, B, stream, **kw):
         """F0 tracks of B waveforms (dtts_text2mel_fetch(DTTS_OUT_PITCH); needs no weights and no encode).  Keywords: those of

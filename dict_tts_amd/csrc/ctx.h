@@ -35,6 +35,7 @@
 #include "resample.h"
 #include "loudness.h"
 #include "disc.h"
+#include "spkenc.h"
 
 // dtts_config.tune_flags: the bits the library honours are listed at TUNE_RELEASE_MASK (context.hip)
 #define DTTS_TUNE(h, bit) (((h)->tune & (bit)) != 0)
@@ -277,6 +278,13 @@ struct dtts_ctx {
     dtts::DiscMpd mpd[5];
     dtts::DiscMsd msd[3];
     dtts::Arena a_disc;
+    // ---- the d-vector speaker encoder (dtts_text2mel_fetch(DTTS_OUT_SPKENC); spkenc.hip): the packs of dtts_finalize_weights(DTTS_PART_SPKENC)
+    // and the one workspace of a chunk of utterances (tables, mel, the projection, two hidden sequences, the partials)
+    bool spkenc_ready = false;
+    dtts::SpkLayer spk_layer[3];
+    float *spk_lin_wt = nullptr, *spk_lin_b = nullptr;   // linear.weight transposed [k][o], linear.bias
+    float *spk_fb = nullptr, *spk_basis = nullptr;       // mel basis [40][201]; windowed DFT basis [400][402]
+    dtts::Arena a_spkenc;
 };
 
 namespace dtts {
@@ -391,5 +399,7 @@ int resample_forward(dtts_ctx* h, const dtts_resample_args* a, hipStream_t strea
 int loudness_forward(dtts_ctx* h, const dtts_loudness_args* a, hipStream_t stream);   // loudness.hip (the same)
 int build_disc(dtts_ctx* h);      // disc.hip
 int disc_forward(dtts_ctx* h, const dtts_disc_args* a, hipStream_t stream);           // disc.hip (the same)
+int build_spkenc(dtts_ctx* h);    // spkenc.hip
+int spkenc_forward(dtts_ctx* h, const dtts_spkenc_args* a, hipStream_t stream);       // spkenc.hip (the same)
 
 } // namespace dtts

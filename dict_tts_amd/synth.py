@@ -313,6 +313,21 @@ def hifigan_disc_state_dict(seed=1234):
     return sd
 
 
+def voice_encoder_state_dict(seed=1234, scale=1.0):
+    """numpy state dict of Resemblyzer's VoiceEncoder (``lstm = nn.LSTM(40, 256, 3, batch_first=True)``, ``linear = nn.Linear(256, 256)``)
+    with torch's default initialisation, U(-1/16, 1/16) for every tensor (1 / sqrt(hidden) = 1 / sqrt(in_features)), times ``scale``"""
+    sd = {}
+    u = lambda name, shape: (_rng(seed, "spkenc." + name).uniform(-1.0 / 16, 1.0 / 16, size=shape) * scale).astype(np.float32)
+    for k in range(3):
+        sd[f"lstm.weight_ih_l{k}"] = u(f"wih{k}", (1024, 40 if k == 0 else 256))
+        sd[f"lstm.weight_hh_l{k}"] = u(f"whh{k}", (1024, 256))
+        sd[f"lstm.bias_ih_l{k}"] = u(f"bih{k}", (1024,))
+        sd[f"lstm.bias_hh_l{k}"] = u(f"bhh{k}", (1024,))
+    sd["linear.weight"] = u("lw", (256, 256))
+    sd["linear.bias"] = u("lb", (256,))
+    return sd
+
+
 # ----------------------------------------------------------------------------------------------------------
 # inputs
 # ----------------------------------------------------------------------------------------------------------

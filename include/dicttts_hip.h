@@ -195,6 +195,14 @@ DTTS_API int dtts_load_weight(dtts_handle h, const char* name, const void* host_
  * modules/hifigan/hifigan.py and not configurable: DTTS_E_INVAL naming the layer on any other shape, DTTS_E_NOENT naming the first missing
  * tensor.  Built once per context. */
 #define DTTS_PART_DISC 128
+/* The d-vector speaker encoder (DTTS_OUT_SPKENC below; Resemblyzer's VoiceEncoder, the source of the reference's spk_embed):
+ * "spkenc.lstm.weight_ih_l<k>" [1024][40 | 256], "spkenc.lstm.weight_hh_l<k>" [1024][256], "spkenc.lstm.bias_ih_l<k>" / "bias_hh_l<k>" [1024]
+ * (k = 0 .. 2; torch.nn.LSTM's state-dict keys, gate order i, f, g, o), "spkenc.linear.weight" [256][256], "spkenc.linear.bias" [256],
+ * "spkenc.mel_basis" [40][201] (the Slaney filterbank 0 .. 8000 Hz at 16 kHz) and "spkenc.window" [400] (the periodic Hann window).  The
+ * architecture is fixed: DTTS_E_INVAL naming the tensor on any other shape, DTTS_E_NOENT naming the first missing tensor.  The windowed DFT
+ * basis is formed here on the host in fp64 and rounded once; W_hh is repacked into the operand order of the recurrent kernel.  Built once
+ * per context. */
+#define DTTS_PART_SPKENC 256
 /* Fold, repack into MFMA fragment order and upload.  Fails with DTTS_E_NOENT naming the first missing tensor. */
 DTTS_API int dtts_finalize_weights(dtts_handle h, int parts);
 
@@ -839,6 +847,65 @@ typedef struct dtts_disc_args {
     float* d_dev;                 /* [8][2][B][d_ld], or NULL */
     int32_t* status_dev;          /* [B] */
 } dtts_disc_args;
+/*
+ * DTTS_OUT_SPKENC: not a copy, needs NO encode — utterance embeddings (d-vectors) of B recordings with the encoder of
+ * dtts_finalize_weights(DTTS_PART_SPKENC): dst = (dtts_spkenc_args*), args->size = sizeof(*args).  What Resemblyzer 0.1.1's
+ * VoiceEncoder.embed_utterance computes, restated:
+ *   mode DTTS_SPKENC_FROM_WAV: utterance b is L = lens_dev[b] samples (NULL = wav_ld; clamped to 0 .. wav_ld) of wav_dev[b], taken AS 16 kHz.
+ *     Partials (compute_partial_slices): n_frames = L / 160 + 1, steps = max(1, n_frames - 160 + frame_step + 1), one partial of 160
+ *     frames = 25600 samples at frame i for i = 0, frame_step, 2 frame_step, ... < steps; the last one is dropped iff there is more than one
+ *     and (L - 160 i) / 25600 < min_coverage (fp64).  frame_step = round(16000 / rate / 160) is the caller's (77 at rate 1.3).  The
+ *     waveform is zero padded to the last partial's end, L' = max(L, 160 (i_last + 160)).
+ *     Mel (librosa.feature.melspectrogram(sr 16000, n_fft 400, hop 160, n_mels 40), POWER, no logarithm): 1 + L' / 160 centred frames;
+ *     frame f covers samples 160 f - 200 .. 160 f + 199 of the padded waveform, outside 0 .. L' - 1 zero (DTTS_SPKENC_PAD_CONSTANT) or
+ *     mirrored without repeating the edge (DTTS_SPKENC_PAD_REFLECT).  X[k] = sum_n (w[n] e^(-2 pi i k n / 400)) x[n] over a basis rounded
+ *     once from fp64, per component 16 fp32 fma chains of 25 consecutive n, added four by four in order and the four sums in order;
+ *     P[k] = re^2 + im^2; mel[m] = sum_k basis[m][k] P[k], one chain in k order.
+ *   mode DTTS_SPKENC_FROM_MELS: wav_dev holds B sequences of mels [B][wav_ld][40] (wav_ld = frames per sequence, 1 .. DTTS_SPKENC_MAX_T),
+ *     each its own utterance of one partial; lens_dev and mel_dev must be NULL, frame_step / min_coverage / pad_mode are not used.
+ *   Per partial (VoiceEncoder.forward): three LSTM layers of 256 units from zero state — gates = (W_hh h_{t-1}, one fp32 chain over k) +
+ *     (W_ih x_t + (b_ih + b_hh)), i, f, o = sigmoid from exp(-|x|), g = tanh from expm1(-2 |x|) with the sign restored (finite at saturation), c_t = f c + i g,
+ *     h_t = o tanh(c_t) — then relu(linear(h_T of layer 2)) divided by its L2 norm.  Per utterance: the mean over its partials (an fp64 sum
+ *     in partial order, rounded to fp32 once) divided by its L2 norm.  A ZERO vector divides to NaN, exactly as the reference's does (all
+ *     256 relu outputs dead): the NaN is the result, it is not hidden.
+ * Outputs: embed_dev f32 [B][256]; n_partials_dev i32 [B]; optionally, with P = dtts_spkenc_max_partials and F = dtts_spkenc_frames_ld
+ * of (wav_ld, frame_step) (FROM_MELS: P = 1), partials_dev f32 [B][P][256] (the unit embeddings of the partials), mel_dev f32 [B][F][40]
+ * and hseq_dev[l] f32 [B][P][T][256] (T = 160, FROM_MELS: wav_ld), every layer's hidden sequence; rows behind an utterance's partials or
+ * frames stay untouched.  Nothing is read behind lens_dev[b].  Every sequence's arithmetic is independent of the others: an utterance's
+ * embedding is bit-identical alone and in any batch, at tile_m = 16 and 32 (the sequences of one workgroup of the recurrent kernel;
+ * 0 = 16 while a chunk's sequences fit 16 per compute unit, DTTS_SPKENC_TILE_M beyond).  No atomics; a workgroup never waits on another.  The batch runs in chunks of utterances that keep the one
+ * workspace below DTTS_SPKENC_WS_BYTES (a single utterance may exceed it); no host synchronisation unless the workspace grows.
+ * DTTS_E_INVAL (naming the field): a wrong size, mode, B outside 1 .. 65535, wav_ld outside 1 .. 2^24 (FROM_MELS: 1 .. DTTS_SPKENC_MAX_T),
+ * frame_step outside 1 .. 4096, min_coverage outside (0, 1], pad_mode, tile_m, reserved != 0, a NULL wav_dev / embed_dev / n_partials_dev, a misaligned
+ * pointer; the argument block is checked before the handle, as DTTS_OUT_DTW's is.  DTTS_E_STATE before
+ * dtts_finalize_weights(DTTS_PART_SPKENC).
+ */
+#define DTTS_OUT_SPKENC 20
+#define DTTS_SPKENC_FROM_WAV 0
+#define DTTS_SPKENC_FROM_MELS 1
+#define DTTS_SPKENC_PAD_CONSTANT 0
+#define DTTS_SPKENC_PAD_REFLECT 1
+#define DTTS_SPKENC_TILE_M 32       /* the most sequences per workgroup of the recurrent kernel: the rows of its MFMA tile */
+#define DTTS_SPKENC_MAX_T 4096
+#define DTTS_SPKENC_WS_BYTES (1ll << 30)
+typedef struct dtts_spkenc_args {
+    int32_t size;                 /* sizeof(dtts_spkenc_args) */
+    int32_t B;
+    int32_t wav_ld;               /* samples per row of wav_dev (FROM_MELS: frames per sequence) */
+    int32_t mode;                 /* DTTS_SPKENC_FROM_WAV / DTTS_SPKENC_FROM_MELS */
+    int32_t frame_step;           /* frames between partials */
+    int32_t pad_mode;             /* DTTS_SPKENC_PAD_CONSTANT / DTTS_SPKENC_PAD_REFLECT */
+    int32_t tile_m;               /* 0, 16 or 32 */
+    int32_t reserved;             /* 0 */
+    double min_coverage;
+    const float* wav_dev;         /* [B][wav_ld] (FROM_MELS: [B][wav_ld][40]) */
+    const int32_t* lens_dev;      /* [B], or NULL = wav_ld */
+    float* embed_dev;             /* [B][256] */
+    int32_t* n_partials_dev;      /* [B] */
+    float* partials_dev;          /* [B][P][256], or NULL */
+    float* mel_dev;               /* [B][F][40], or NULL */
+    float* hseq_dev[3];           /* [B][P][T][256] each, or NULL */
+} dtts_spkenc_args;
 DTTS_API int dtts_text2mel_fetch(dtts_handle h, int what, void* dst_dev, dtts_stream stream);
 
 /*
