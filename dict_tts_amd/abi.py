@@ -59,6 +59,14 @@ SPKENC_PAD_CONSTANT, SPKENC_PAD_REFLECT = 0, 1       # dtts_spkenc_args.pad_mode
 SPKENC_TILE_M = 32    # DTTS_SPKENC_TILE_M: the most sequences per workgroup of the recurrent kernel (tile_m = 16 is the other form)
 SPKENC_MAX_T = 4096   # DTTS_SPKENC_MAX_T
 SPKENC_HOP, SPKENC_PART, SPKENC_MELS, SPKENC_DIM = 160, 160, 40, 256
+PART_MELDISC = 512    # the acoustic checkpoint's multi-window mel discriminator: "meldisc.<w>.*", plain (folded) weights; built once per context
+OUT_MELDISC = 21      # not a copy, needs no encode: D per clip and the sums behind a / r / f of a batch of mels, dst = a MeldiscArgs block
+MELDISC_STACK, MELDISC_SUM, MELDISC_NONE = 0, 1, 2   # dtts_meldisc_args.reduction
+MELDISC_REDUCTIONS = {"stack": MELDISC_STACK, "sum": MELDISC_SUM, "none": MELDISC_NONE}
+MELDISC_WITHIN_LEN = 1   # DTTS_MELDISC_WITHIN_LEN (flags): a slot is a clip only where it ends within the signal's own length
+MELDISC_BAD_LEN = 1      # DTTS_MELDISC_BAD_LEN (status bit)
+MELDISC_MELS, MELDISC_MAX_WIN, MELDISC_D_LD, MELDISC_MAX_HIDDEN = 80, 3, 16, 256
+MELDISC_WINS = (32, 64, 128)
 SPECTRAL_FORWARD, SPECTRAL_INVERSE = 1, 2  # dtts_spectral_args.mode bits; both = the reference's denoise
 SPK_EMBED, SPK_ID = 1, 2   # dtts_text2mel_speakers kinds: fp32 [B,256] (use_spk_embed) / int64 [B] (use_spk_id)
 TIMER_VOC_CONV, TIMER_S2PA = 1, 2
@@ -224,6 +232,22 @@ def spkenc_args(B, wav, wav_ld, embed, n_partials, mode=SPKENC_FROM_WAV, frame_s
     return SpkencArgs(C.sizeof(SpkencArgs), int(B), int(wav_ld), int(mode), int(frame_step), int(pad_mode), int(tile_m), 0, float(min_coverage),
                       wav or None, lens or None, embed or None, n_partials or None, partials or None, mel or None,
                       (C.c_void_p * 3)(*[v or None for v in hseq]))
+
+
+class MeldiscArgs(C.Structure):
+    """dtts_meldisc_args (include/dicttts_hip.h): the argument block of dtts_text2mel_fetch(DTTS_OUT_MELDISC)"""
+    _fields_ = [("size", C.c_int32), ("n_sig", C.c_int32), ("T_ld", C.c_int32), ("n_win", C.c_int32), ("reduction", C.c_int32), ("flags", C.c_int32),
+                ("clips_ld", C.c_int32), ("hop", C.c_int32 * 3), ("reserved", C.c_int32 * 2), ("mel_dev", C.c_void_p), ("lens_dev", C.c_void_p),
+                ("starts_dev", C.c_void_p), ("d_dev", C.c_void_p), ("sums_dev", C.c_void_p), ("counts_dev", C.c_void_p), ("status_dev", C.c_void_p),
+                ("h_dev", C.c_void_p * 9)]
+
+
+def meldisc_args(n_sig, mel, T_ld, n_win, clips_ld, sums, counts, status, reduction=MELDISC_STACK, flags=0, hop=(0, 0, 0), lens=None, starts=None,
+                 d=None, h=(None,) * 9):
+    """a filled MeldiscArgs block (device pointers as integers, 0 / None = NULL)"""
+    return MeldiscArgs(C.sizeof(MeldiscArgs), int(n_sig), int(T_ld), int(n_win), int(reduction), int(flags), int(clips_ld),
+                       (C.c_int32 * 3)(*[int(v) for v in hop]), (C.c_int32 * 2)(0, 0), mel or None, lens or None, starts or None, d or None, sums or None,
+                       counts or None, status or None, (C.c_void_p * 9)(*[v or None for v in h]))
 
 
 class DttsConfig(C.Structure):
@@ -465,6 +489,14 @@ class Context:
         counts i64 [B, 8], status i32 [B] out, fm f64 [B, 8, 8] + fm_counts i64 [B, 8, 8] out (DISC_FM), d f32 [8, 2, B, d_ld] out or None."""
         a = disc_args(B, **kw)
         self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_DISC, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_DISC)")
+
+    def meldisc(self, n_sig, stream, **kw):
+        """the multi-window mel discriminator on clips of n_sig mels (dtts_text2mel_fetch(DTTS_OUT_MELDISC); needs PART_MELDISC finalised, no
+        encode).  Keywords: those of ``meldisc_args`` — mel f32 [n_sig, T_ld, 80], lens i32 [n_sig] or None, n_win, clips_ld, starts i32
+        [n_win, n_sig, clips_ld] or None (then hop), reduction, flags, sums f64 [n_sig, 3, 2], counts i64 [n_sig, 3], status i32 [n_sig] out,
+        d f32 [n_win, n_sig, clips_ld, 16] out or None, h 9 x f32 [n_sig, clips_ld, t, f, H] out or None."""
+        a = meldisc_args(n_sig, **kw)
+        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_MELDISC, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_MELDISC)")
 
     def spkenc(self, B, stream, **kw):
         """utterance embeddings of B recordings or mel sequences (dtts_text2mel_fetch(DTTS_OUT_SPKENC); needs PART_SPKENC finalised, no

@@ -130,7 +130,7 @@ int dtts_create(const dtts_config* cfg, dtts_handle* out) {
     if (hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || h->n_cu <= 0) h->n_cu = 256;
     h->debug_rz = cfg->debug_redzone != 0;
     h->debug_misorder = cfg->debug_redzone == 2;
-    h->a_fft.debug = h->a_enc.debug = h->a_dec.debug = h->a_voc.debug = h->a_spk.debug = h->a_post.debug = h->a_stft.debug = h->a_spec.debug = h->a_loss.debug = h->a_dtw.debug = h->a_pitch.debug = h->a_loud.debug = h->a_disc.debug = h->a_spkenc.debug = h->debug_rz;
+    h->a_fft.debug = h->a_enc.debug = h->a_dec.debug = h->a_voc.debug = h->a_spk.debug = h->a_post.debug = h->a_stft.debug = h->a_spec.debug = h->a_loss.debug = h->a_dtw.debug = h->a_pitch.debug = h->a_loud.debug = h->a_disc.debug = h->a_spkenc.debug = h->a_meldisc.debug = h->debug_rz;
     *out = h;
     return DTTS_OK;
 }
@@ -159,6 +159,7 @@ void dtts_destroy(dtts_handle h) {
     h->a_loud.release();
     h->a_disc.release();
     h->a_spkenc.release();
+    h->a_meldisc.release();
     for (auto& t : h->timers)
         for (auto e : t.pool) (void)hipEventDestroy(e);
     delete h;
@@ -198,6 +199,7 @@ int dtts_finalize_weights(dtts_handle h, int parts) {
     if (rs) rc = build_resample(h);
     if (rc == DTTS_OK && (parts & DTTS_PART_DISC) && !h->disc_ready) rc = build_disc(h);
     if (rc == DTTS_OK && (parts & DTTS_PART_SPKENC) && !h->spkenc_ready) rc = build_spkenc(h);
+    if (rc == DTTS_OK && (parts & DTTS_PART_MELDISC) && !h->meldisc_ready) rc = build_meldisc(h);
     if (rc == DTTS_OK) {
         // host copies are no longer needed for finished parts
         for (auto it = h->w.begin(); it != h->w.end();) {
@@ -210,7 +212,8 @@ int dtts_finalize_weights(dtts_handle h, int parts) {
             const bool r = it->first.rfind("resample.", 0) == 0 && rs;
             const bool d = it->first.rfind("disc.", 0) == 0 && h->disc_ready;
             const bool e = it->first.rfind("spkenc.", 0) == 0 && h->spkenc_ready;
-            it = (a || v || f || m || s || i || r || d || e) ? h->w.erase(it) : std::next(it);
+            const bool g = it->first.rfind("meldisc.", 0) == 0 && h->meldisc_ready;
+            it = (a || v || f || m || s || i || r || d || e || g) ? h->w.erase(it) : std::next(it);
         }
     }
     return rc;
@@ -276,7 +279,7 @@ int dtts_debug_poke(dtts_handle h, dtts_stream stream) {
     if (!h) return DTTS_E_INVAL;
     if (!h->debug_rz) return fail(h, DTTS_E_STATE, "dtts_debug_poke: the context was not created with dtts_config.debug_redzone = 1");
     char* target = nullptr;
-    for (Arena* a : {&h->a_voc, &h->a_enc, &h->a_dec, &h->a_fft, &h->a_spk, &h->a_post, &h->a_stft, &h->a_spec, &h->a_loss, &h->a_dtw, &h->a_pitch, &h->a_loud, &h->a_disc, &h->a_spkenc})
+    for (Arena* a : {&h->a_voc, &h->a_enc, &h->a_dec, &h->a_fft, &h->a_spk, &h->a_post, &h->a_stft, &h->a_spec, &h->a_loss, &h->a_dtw, &h->a_pitch, &h->a_loud, &h->a_disc, &h->a_spkenc, &h->a_meldisc})
         if (!target && a->base && !a->bufs.empty()) target = a->base + a->bufs[0].start + a->bufs[0].bytes;
     if (!target && !h->rz_static.empty()) target = h->rz_static[0].p + h->rz_static[0].bytes;
     if (!target) return fail(h, DTTS_E_STATE, "dtts_debug_poke: nothing allocated yet");
@@ -297,7 +300,7 @@ int dtts_debug_check(dtts_handle h, int64_t* damaged_bytes, dtts_stream stream) 
         zones.push_back({(const unsigned char*)p0, (unsigned)n, (unsigned)names.size()});
         names.push_back(name);
     };
-    const std::pair<const char*, Arena*> arenas[] = {{"encode workspace", &h->a_enc}, {"decode workspace", &h->a_dec}, {"vocoder workspace", &h->a_voc}, {"fft workspace", &h->a_fft}, {"speaker workspace", &h->a_spk}, {"posterior workspace", &h->a_post}, {"stft workspace", &h->a_stft}, {"spectral workspace", &h->a_spec}, {"loss workspace", &h->a_loss}, {"dtw workspace", &h->a_dtw}, {"pitch workspace", &h->a_pitch}, {"loudness workspace", &h->a_loud}, {"discriminator workspace", &h->a_disc}, {"speaker encoder workspace", &h->a_spkenc}};
+    const std::pair<const char*, Arena*> arenas[] = {{"encode workspace", &h->a_enc}, {"decode workspace", &h->a_dec}, {"vocoder workspace", &h->a_voc}, {"fft workspace", &h->a_fft}, {"speaker workspace", &h->a_spk}, {"posterior workspace", &h->a_post}, {"stft workspace", &h->a_stft}, {"spectral workspace", &h->a_spec}, {"loss workspace", &h->a_loss}, {"dtw workspace", &h->a_dtw}, {"pitch workspace", &h->a_pitch}, {"loudness workspace", &h->a_loud}, {"discriminator workspace", &h->a_disc}, {"speaker encoder workspace", &h->a_spkenc}, {"mel discriminator workspace", &h->a_meldisc}};
     for (const auto& a : arenas) {
         const auto& bufs = a.second->bufs;
         const char* base = a.second->base;

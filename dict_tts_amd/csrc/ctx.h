@@ -36,6 +36,7 @@
 #include "loudness.h"
 #include "disc.h"
 #include "spkenc.h"
+#include "meldisc.h"
 
 // dtts_config.tune_flags: the bits the library honours are listed at TUNE_RELEASE_MASK (context.hip)
 #define DTTS_TUNE(h, bit) (((h)->tune & (bit)) != 0)
@@ -285,6 +286,14 @@ struct dtts_ctx {
     float *spk_lin_wt = nullptr, *spk_lin_b = nullptr;   // linear.weight transposed [k][o], linear.bias
     float *spk_fb = nullptr, *spk_basis = nullptr;       // mel basis [40][201]; windowed DFT basis [400][402]
     dtts::Arena a_spkenc;
+    // ---- the multi-window mel discriminator (dtts_text2mel_fetch(DTTS_OUT_MELDISC); meldisc.hip): the packs of
+    // dtts_finalize_weights(DTTS_PART_MELDISC) and the one workspace of a chunk of signals (clip table, three maps, statistics, D rows)
+    bool meldisc_ready = false, meldisc_per_row = false;   // per_row: disc_reduction none (a head per remaining time row)
+    int meldisc_H = 0, meldisc_nwin = 0;
+    dtts::MelDiscWin meldisc[DTTS_MELDISC_MAX_WIN];
+    const float2* meldisc_ident = nullptr;                 // (0, 1) [H]
+    const float* meldisc_zero = nullptr;                   // 0 [H]
+    dtts::Arena a_meldisc;
 };
 
 namespace dtts {
@@ -401,5 +410,7 @@ int build_disc(dtts_ctx* h);      // disc.hip
 int disc_forward(dtts_ctx* h, const dtts_disc_args* a, hipStream_t stream);           // disc.hip (the same)
 int build_spkenc(dtts_ctx* h);    // spkenc.hip
 int spkenc_forward(dtts_ctx* h, const dtts_spkenc_args* a, hipStream_t stream);       // spkenc.hip (the same)
+int build_meldisc(dtts_ctx* h);   // meldisc.hip
+int meldisc_forward(dtts_ctx* h, const dtts_meldisc_args* a, hipStream_t stream);     // meldisc.hip (the same)
 
 } // namespace dtts

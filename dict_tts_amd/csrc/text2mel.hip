@@ -772,6 +772,7 @@ int dtts_text2mel_fetch(dtts_handle h, int what, void* dst, dtts_stream stream) 
     if (what == DTTS_OUT_LOUDNESS && dst) return loudness_forward(h, (const dtts_loudness_args*)dst, (hipStream_t)stream);   // the same
     if (what == DTTS_OUT_DISC && dst) return disc_forward(h, (const dtts_disc_args*)dst, (hipStream_t)stream);   // the same
     if (what == DTTS_OUT_SPKENC && dst) return spkenc_forward(h, (const dtts_spkenc_args*)dst, (hipStream_t)stream);   // the same
+    if (what == DTTS_OUT_MELDISC && dst) return meldisc_forward(h, (const dtts_meldisc_args*)dst, (hipStream_t)stream);   // the same
     if (!h || !dst) return DTTS_E_INVAL;
     if (what == DTTS_OUT_MELSPEC) return melspec_forward(h, (const dtts_melspec_args*)dst, (hipStream_t)stream);   // needs no encode
     if (what == DTTS_OUT_STFT_DISTANCE) return stft_forward(h, (const dtts_stft_args*)dst, (hipStream_t)stream);   // nor does this

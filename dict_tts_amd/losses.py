@@ -66,9 +66,12 @@ class ValidationLosses:
 
     hparams: the reference's keys mel_loss, lambda_kl, lambda_sent_dur, dur_scale, dur_level (None: the global hparams when set, else
     the ps_flow.yaml values).  ctx: an existing ``abi.Context`` (e.g. the model's), or None for one of its own; it is created on the
-    first call, so that argument errors surface without a GPU."""
+    first call, so that argument errors surface without a GPU.  mel_disc: an optional ``mel_discriminator.MelDiscriminator`` (the
+    checkpoint's own multi-window discriminator); with it validation_step also reports ``a`` / ``r`` / ``f``, the adversarial terms of
+    ``_training_step`` (tasks/tts/dict_tts.py:96-118), outside total_loss, which stays the reference's validation total.  Without it every
+    output is what it was."""
 
-    def __init__(self, hparams=None, ctx=None):
+    def __init__(self, hparams=None, ctx=None, mel_disc=None):
         if hparams is None:
             hparams = hparams_mod.hparams or {}
         hp = {**LOSS_DEFAULTS, **{k: v for k, v in dict(hparams).items() if k in LOSS_DEFAULTS}}
@@ -84,6 +87,7 @@ class ValidationLosses:
             raise ValueError("lambda_sent_dur > 0 needs dur_scale = 'linear' (the reference asserts it, tasks/tts/ps_flow.py:111)")
         self.ctx = ctx
         self.device = None
+        self.mel_disc = mel_disc
 
     def _context(self):
         if self.device is None:
@@ -176,12 +180,26 @@ class ValidationLosses:
         losses["sdur"] = d["sdur"]
         return losses, output
 
+    def adversarial(self, mel_out, target, mel_lengths=None):
+        """the checkpoint's discriminator on the predicted mels next to the recordings': ``MelDiscriminator.scores(target, mel_out, lens)``
+        (clips at hop win / 2, every utterance at its own length; ``a_batch`` / ``r_batch`` / ``f_batch`` are what validation_step reports).
+        mel_lengths None: the frames of the target whose bins are not all zero, as the mel losses mask them."""
+        if self.mel_disc is None:
+            raise ValueError("ValidationLosses was built without mel_disc=")
+        target = torch.as_tensor(target)
+        if mel_lengths is None:
+            mel_lengths = target.abs().sum(-1).ne(0).sum(-1)
+        return self.mel_disc.scores(target, torch.as_tensor(mel_out), mel_lengths)
+
     def validation_step(self, model, sample):
         """-> {'losses': {name: float}, 'total_loss': float, 'nsamples': sample['nsamples'] (or the batch size)}: the first half of
         DictTTSTask.validation_step (tasks/tts/dict_tts.py:127-136), scalars on the host as utils.tensors_to_scalars leaves them"""
-        losses, _ = self.run_model(model, sample)
+        losses, output = self.run_model(model, sample)
         vals = torch.stack([v.reshape(()) for v in losses.values()]).cpu().tolist()   # one device-to-host copy
         out = {"losses": dict(zip(losses.keys(), vals)), "total_loss": float(sum(vals))}
+        if self.mel_disc is not None:
+            adv = self.adversarial(output["mel_out"], sample["mels"], sample.get("mel_lengths"))
+            out["losses"].update(zip(("a", "r", "f"), torch.stack([adv[k + "_batch"] for k in ("a", "r", "f")]).cpu().tolist()))
         n = sample.get("nsamples")
         out["nsamples"] = int(n) if n is not None else int(torch.as_tensor(sample["word_tokens"]).shape[0])
         return out

@@ -328,6 +328,52 @@ def voice_encoder_state_dict(seed=1234, scale=1.0):
     return sd
 
 
+def mel_disc_state_dict(seed=1234, norm="in", hidden=128, win_num=3, reduction="stack"):
+    """numpy state dict of the Dict-TTS task's ``mel_disc`` (``state_dict.mel_disc``; modules/fastspeech/multi_window_disc.py::Discriminator
+    without cond_disc): per window ``discriminator.conv_layers.<w>.model.<l>.0`` (the Conv2d; under ``sn`` as weight_orig / weight_u /
+    weight_v with u, v from power iterations, so that u . (W v) IS the spectral norm), ``model.<l>.3`` (l = 1, 2: InstanceNorm2d's affine
+    under ``in``; BatchNorm2d's affine and running statistics under ``bn``) and ``adv_layer``.  He-scaled; affine scales lie around 1, so
+    that no channel is dead."""
+    if norm not in ("in", "bn", "sn"):
+        raise ValueError(f"norm = {norm!r} (supported: 'in', 'bn', 'sn')")
+    if reduction not in ("stack", "sum", "none"):
+        raise ValueError(f"reduction = {reduction!r} (supported: 'stack', 'sum', 'none')")
+    H = int(hidden)
+    sd = {}
+    for w, win in enumerate((32, 64, 128)[:win_num]):
+        base = f"discriminator.conv_layers.{w}"
+        for l in range(3):
+            name = f"{base}.model.{l}.0"
+            cin = H if l else 1
+            wt = randn(seed, name + ".w", (H, cin, 3, 3), np.sqrt(2.0 / (cin * 9)))
+            if norm == "sn":
+                m = wt.reshape(H, -1).astype(np.float64)
+                v = _rng(seed, name + ".v").standard_normal(m.shape[1])
+                for _ in range(8):
+                    u = m @ v
+                    u /= np.linalg.norm(u) + 1e-12
+                    v = m.T @ u
+                    v /= np.linalg.norm(v) + 1e-12
+                sd[name + ".weight_orig"] = wt
+                sd[name + ".weight_u"] = u.astype(np.float32)
+                sd[name + ".weight_v"] = v.astype(np.float32)
+            else:
+                sd[name + ".weight"] = wt
+            sd[name + ".bias"] = randn(seed, name + ".b", (H,), 0.05)
+            if l and norm in ("in", "bn"):
+                n = f"{base}.model.{l}.3"
+                sd[n + ".weight"] = (1.0 + 0.1 * randn(seed, n + ".g", (H,))).astype(np.float32)
+                sd[n + ".bias"] = randn(seed, n + ".beta", (H,), 0.05)
+                if norm == "bn":
+                    sd[n + ".running_mean"] = randn(seed, n + ".rm", (H,), 0.1)
+                    sd[n + ".running_var"] = (0.5 + _rng(seed, n + ".rv").random(H)).astype(np.float32)
+                    sd[n + ".num_batches_tracked"] = np.array(1000, np.int64)
+        n_in = H * 10 * (1 if reduction == "none" else win // 8)
+        sd[f"{base}.adv_layer.weight"] = randn(seed, base + ".adv.w", (1, n_in), 1.0 / np.sqrt(n_in))
+        sd[f"{base}.adv_layer.bias"] = randn(seed, base + ".adv.b", (1,), 0.05)
+    return sd
+
+
 # ----------------------------------------------------------------------------------------------------------
 # inputs
 # ----------------------------------------------------------------------------------------------------------

@@ -203,6 +203,18 @@ DTTS_API int dtts_load_weight(dtts_handle h, const char* name, const void* host_
  * basis is formed here on the host in fp64 and rounded once; W_hh is repacked into the operand order of the recurrent kernel.  Built once
  * per context. */
 #define DTTS_PART_SPKENC 256
+/* The acoustic checkpoint's multi-window mel discriminator (DTTS_OUT_MELDISC below; state_dict['mel_disc'] of a Dict-TTS checkpoint,
+ * modules/fastspeech/multi_window_disc.py::Discriminator without cond_disc).  Window w = 0 .. n - 1 (32, 64, 128 frames), block l = 0 .. 2:
+ *   "meldisc.<w>.conv.<l>.weight" [H][1 | H][3][3] and ".bias" [H]: the Conv2d of block l, PLAIN (spectral norm folded by the caller);
+ *   "meldisc.<w>.norm.<l>.weight" / ".bias" [H] (l = 1, 2): InstanceNorm2d(H, affine=True), statistics taken per clip on the device; OR
+ *   "meldisc.<w>.affine.<l>.scale" / ".shift" [H] (l = 1, 2): BatchNorm2d in eval mode folded by the caller to x * scale + shift; neither
+ *   of the two = no norm (disc_norm: sn);
+ *   "meldisc.<w>.adv.weight" [1][H * (win / 8) * 10] (disc_reduction stack / sum, flattened as (c, t, f)) or [1][H * 10] (none, (c, f) per
+ *   time row), and ".bias" [1].
+ * H and the window count are read from the tensors.  DTTS_E_NOENT names the first missing tensor; DTTS_E_INVAL names a hidden size that is
+ * not a multiple of 32 in 32 .. DTTS_MELDISC_MAX_HIDDEN, a window count outside 1 .. 3 ("meldisc.3.*" present), a layer of another shape,
+ * and an adv_layer whose width does not match its window (or differs in kind between windows).  Built once per context. */
+#define DTTS_PART_MELDISC 512
 /* Fold, repack into MFMA fragment order and upload.  Fails with DTTS_E_NOENT naming the first missing tensor. */
 DTTS_API int dtts_finalize_weights(dtts_handle h, int parts);
 
@@ -906,6 +918,63 @@ typedef struct dtts_spkenc_args {
     float* mel_dev;               /* [B][F][40], or NULL */
     float* hseq_dev[3];           /* [B][P][T][256] each, or NULL */
 } dtts_spkenc_args;
+/*
+ * DTTS_OUT_MELDISC: not a copy, needs NO encode — the multi-window mel discriminator of dtts_finalize_weights(DTTS_PART_MELDISC) in eval
+ * mode (Dropout2d is the identity) on clips of n_sig mels, and the sums behind the a / r / f terms of tasks/tts/dict_tts.py::_training_step:
+ * dst = (dtts_meldisc_args*), args->size = sizeof(*args).  Signal s has L = lens_dev[s] frames (NULL = T_ld) of mel_dev[s]; frames at or
+ * behind L enter as ZEROS whatever the buffer holds there.  Window w (32 << w frames) has clips_ld clip slots per signal: slot j starts at
+ * starts_dev[w][s][j] (a negative entry = no clip) or, with starts_dev NULL, at j * hop[w].  A slot is a clip when start >= 0 and
+ * start + win <= L (DTTS_MELDISC_WITHIN_LEN: the measurement) or start + win <= T_ld (without the flag: the reference's forward, whose
+ * clips may run behind an utterance's own length).  Per clip, with H = mel_disc_hidden_size:
+ *   block 1: Conv2d(1 -> H, 3 x 3, stride 2, pad 1) on the clip [win][80], LeakyReLU(0.2);  blocks 2, 3: Conv2d(H -> H, the same),
+ *   LeakyReLU(0.2), then the norm (none / InstanceNorm2d, eps 1e-5, biased variance per (clip, channel) in fp64 by two passes / the folded
+ *   BatchNorm affine); maps (win / 2, 40), (win / 4, 20), (win / 8, 10); the zero padding of a block is padding of the NORMALISED map.
+ *   Blocks 2 and 3 contract over (channel chunk, tap, channel) on v_mfma_f32_32x32x2_f32 with exact fp32 products.  Head: stack / sum one
+ *   D = adv . flatten(c, t, f) + bias per clip; none one D per remaining time row (win / 8 of them) over (c, f).
+ * Outputs: sums_dev f64 [n_sig][3][2]: sum (1 - D)^2 and sum D^2 over the D of signal s's clips of window w; counts_dev i64 [n_sig][3] their
+ * number (0: no clip fits, sums 0; windows >= n_win untouched); status_dev i32 [n_sig]: DTTS_MELDISC_BAD_LEN where L is outside 0 .. T_ld
+ * (treated as 0 frames); d_dev f32 [n_win][n_sig][clips_ld][DTTS_MELDISC_D_LD] or NULL: the D of every clip (entry 0, or win / 8 entries
+ * for none; other entries and slots without a clip untouched); h_dev[3 w + l] f32 [n_sig][clips_ld][t][f][H] or NULL: the output of block l
+ * of window w as the reference's `h` holds it (after the norm), channels-last, for tests.  All sums run in fp64 in a fixed order without
+ * atomics; a signal's results are bit-identical alone and in any batch.  The windows run one after another on `stream` over one reused
+ * workspace, the signals in chunks that keep it below DTTS_MELDISC_WS_BYTES (one signal may exceed it); no host synchronisation unless the
+ * workspace grows.  `reduction` does not change D: the host adds (sum) or stacks the windows; it must agree with the loaded adv_layer
+ * (none <-> per-row heads).
+ * DTTS_E_INVAL (naming the field): a wrong size, n_sig outside 1 .. 65535, T_ld outside 1 .. 2^20, n_win outside 1 .. 3, an unknown
+ * reduction or flag, clips_ld outside 1 .. 65536 or n_sig * clips_ld above 2^24, starts_dev NULL with a hop[w] < 1 (w < n_win), a non-zero
+ * reserved word, a NULL mel_dev / sums_dev / counts_dev / status_dev, a misaligned pointer; the block is checked before the handle.
+ * DTTS_E_STATE before dtts_finalize_weights(DTTS_PART_MELDISC); DTTS_E_INVAL when n_win or the reduction's kind differs from the loaded model.
+ */
+#define DTTS_OUT_MELDISC 21
+#define DTTS_MELDISC_STACK 0
+#define DTTS_MELDISC_SUM 1
+#define DTTS_MELDISC_NONE 2
+#define DTTS_MELDISC_WITHIN_LEN 1   /* flags */
+#define DTTS_MELDISC_BAD_LEN 1      /* status bit */
+#define DTTS_MELDISC_MELS 80        /* freq_length: the only audio_num_mel_bins the reference's discriminator is built for */
+#define DTTS_MELDISC_MAX_WIN 3      /* windows of 32, 64, 128 frames */
+#define DTTS_MELDISC_D_LD 16        /* D entries per clip slot (128 / 8 time rows under disc_reduction: none) */
+#define DTTS_MELDISC_MAX_HIDDEN 256
+#define DTTS_MELDISC_WS_BYTES (1ll << 30)
+typedef struct dtts_meldisc_args {
+    int32_t size;                 /* sizeof(dtts_meldisc_args) */
+    int32_t n_sig;
+    int32_t T_ld;                 /* frames per row of mel_dev */
+    int32_t n_win;                /* windows (disc_win_num) */
+    int32_t reduction;            /* DTTS_MELDISC_STACK / SUM / NONE */
+    int32_t flags;                /* DTTS_MELDISC_WITHIN_LEN */
+    int32_t clips_ld;             /* clip slots per (window, signal) */
+    int32_t hop[3];               /* frames between the starts of window w (starts_dev NULL) */
+    int32_t reserved[2];          /* 0 */
+    const float* mel_dev;         /* [n_sig][T_ld][80] */
+    const int32_t* lens_dev;      /* [n_sig], or NULL = T_ld */
+    const int32_t* starts_dev;    /* [n_win][n_sig][clips_ld], or NULL = j * hop[w] */
+    float* d_dev;                 /* [n_win][n_sig][clips_ld][DTTS_MELDISC_D_LD], or NULL */
+    double* sums_dev;             /* [n_sig][3][2] */
+    int64_t* counts_dev;          /* [n_sig][3] */
+    int32_t* status_dev;          /* [n_sig] */
+    float* h_dev[9];              /* [3 w + l]: [n_sig][clips_ld][t][f][H], or NULL */
+} dtts_meldisc_args;
 DTTS_API int dtts_text2mel_fetch(dtts_handle h, int what, void* dst_dev, dtts_stream stream);
 
 /*
