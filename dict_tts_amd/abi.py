@@ -72,6 +72,8 @@ SPK_EMBED, SPK_ID = 1, 2   # dtts_text2mel_speakers kinds: fp32 [B,256] (use_spk
 TIMER_VOC_CONV, TIMER_S2PA = 1, 2
 TIMER_STAGE_ENCODER, TIMER_STAGE_DICT_ENCODER, TIMER_STAGE_FVAE, TIMER_STAGE_HIFIGAN = 3, 4, 5, 6   # the reference's profile_infer names
 
+OUT_NAMES = {v: "DTTS_" + k for k, v in list(globals().items()) if k.startswith("OUT_")}   # code -> "DTTS_OUT_X", as the library's messages spell it
+
 EXPORTS = ["dtts_default_config", "dtts_config_sizeof", "dtts_create", "dtts_destroy", "dtts_last_error", "dtts_load_weight",
            "dtts_finalize_weights", "dtts_dict_table_upload", "dtts_text2mel_encode", "dtts_text2mel_encode_ids", "dtts_text2mel_speakers", "dtts_text2mel_decode", "dtts_text2mel_fetch",
            "dtts_load_weights", "dtts_text2mel_plan", "dtts_text2mel_forward", "dtts_text2mel_forward_ids",
@@ -420,18 +422,22 @@ class Context:
     def text2mel_decode(self, z_p, mel_out, stream):
         self._chk(self.lib.dtts_text2mel_decode(self.h, z_p, mel_out, stream), "dtts_text2mel_decode")
 
+    def _fetch_block(self, what, block, stream):
+        """dtts_text2mel_fetch of an item whose dst is a host argument block"""
+        self._chk(self.lib.dtts_text2mel_fetch(self.h, what, C.byref(block), stream), f"dtts_text2mel_fetch({OUT_NAMES[what]})")
+
     def text2mel_posterior(self, tgt_mels, mel_ld, eps, eps_ld, mel_out, mel_cap, m_q, logs_q, z_p, kl, stream):
         """the teacher-forced FVAE posterior pass after an encode: dtts_text2mel_fetch(DTTS_OUT_POSTERIOR) with its host argument block
         (device pointers; eps / m_q / logs_q / z_p / kl may be None)"""
         a = PosteriorArgs(C.sizeof(PosteriorArgs), int(mel_ld), int(eps_ld), int(mel_cap), tgt_mels, eps, mel_out, m_q, logs_q, z_p, kl)
-        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_POSTERIOR, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_POSTERIOR)")
+        self._fetch_block(OUT_POSTERIOR, a, stream)
 
     def melspec(self, wav, wav_lens, B, wav_ld, hop, mel, mel_cap, mel_lens, stream, eps=1e-6, lin=None):
         """log-mel spectrograms of B waveforms in one launch (dtts_text2mel_fetch(DTTS_OUT_MELSPEC); needs PART_MELSPEC finalised, no encode):
         device pointers wav f32 [B, wav_ld], wav_lens i32 [B] or None, mel f32 [B, mel_cap, n_mels] out, mel_lens i32 [B] out or None,
         lin f32 like mel or None: the mel values before the floor and the logarithm"""
         a = MelspecArgs(C.sizeof(MelspecArgs), int(hop), int(B), int(wav_ld), int(mel_cap), float(eps), wav, wav_lens or None, mel, mel_lens or None, lin or None)
-        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_MELSPEC, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_MELSPEC)")
+        self._fetch_block(OUT_MELSPEC, a, stream)
 
     def stft_distance(self, x, y, lens, B, wav_ld, hops, sums, count, stream, mag=None, mag_cap=0):
         """the sums behind the multi-resolution STFT figures of B waveform pairs (dtts_text2mel_fetch(DTTS_OUT_STFT_DISTANCE); needs PART_STFT
@@ -442,7 +448,7 @@ class Context:
         if not 1 <= len(hops) <= 4:
             raise DttsError(f"stft_distance: {len(hops)} resolutions (supported: 1 .. 4)")
         a = StftArgs(C.sizeof(StftArgs), len(hops), (C.c_int32 * 4)(*hops), int(B), int(wav_ld), int(mag_cap), 0, x, y, lens or None, sums, count, mag or None)
-        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_STFT_DISTANCE, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_STFT_DISTANCE)")
+        self._fetch_block(OUT_STFT_DISTANCE, a, stream)
 
     def spectral(self, mode, B, wav_ld, hop, spec_cap, stream, wav=None, lens=None, frames=None, spec=None, out=None, out_lens=None, floor=0.0):
         """STFT (mode SPECTRAL_FORWARD), inverse STFT (SPECTRAL_INVERSE) or STFT -> max(|S| - floor, 0) -> inverse STFT (both bits: the
@@ -451,7 +457,7 @@ class Context:
         out_lens i32 [B] or None; with both bits spec and frames may be None (the context's workspace)."""
         a = SpectralArgs(C.sizeof(SpectralArgs), int(mode), int(hop), int(B), int(wav_ld), int(spec_cap), float(floor), wav or None, lens or None,
                          frames or None, spec or None, out or None, out_lens or None)
-        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_SPECTRAL, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_SPECTRAL)")
+        self._fetch_block(OUT_SPECTRAL, a, stream)
 
     def griffin_lim(self, B, spec_cap, hop, n_iter, wav_ld, out, stream, mag=None, mel=None, n_mels=0, init=None, frames=None, out_lens=None,
                     spec_out=None):
@@ -461,7 +467,7 @@ class Context:
         [B, wav_ld], out_lens i32 [B] or None, spec_out f32 like init or None: the spectrum `out` was inverted from."""
         a = GriffinLimArgs(C.sizeof(GriffinLimArgs), int(B), int(spec_cap), int(hop), int(n_iter), int(wav_ld), int(n_mels), 0, mag or None, mel or None,
                            init or None, frames or None, out or None, out_lens or None, spec_out or None)
-        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_GRIFFIN_LIM, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_GRIFFIN_LIM)")
+        self._fetch_block(OUT_GRIFFIN_LIM, a, stream)
 
     def losses(self, B, stream, pred=None, tgt=None, T=0, n_mel=0, mel_sums=None, mel_count=None, pred_ld=0, tgt_ld=0, bias=6.0, ssim_map=None,
                dur_pred=None, mel2word=None, word_len=None, T_w=0, T_mel=0, m2w_ld=0, dur_scale=0, dur_sums=None, dur_gt=None):
@@ -473,46 +479,41 @@ class Context:
         a = LossArgs(C.sizeof(LossArgs), int(B), int(T), int(n_mel), int(pred_ld), int(tgt_ld), float(bias), int(T_w), int(T_mel), int(m2w_ld),
                      int(dur_scale), 0, pred or None, tgt or None, mel_sums or None, mel_count or None, ssim_map or None, dur_pred or None,
                      mel2word or None, word_len or None, dur_sums or None, dur_gt or None)
-        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_LOSSES, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_LOSSES)")
+        self._fetch_block(OUT_LOSSES, a, stream)
 
     def dtw(self, B, stream, **kw):
         """dynamic time warping of B pairs (dtts_text2mel_fetch(DTTS_OUT_DTW); needs no weights and no encode).  Keywords: those of
         ``dtw_args`` — x [B, x_ld, F] and y [B, y_ld, F] of dtype 0 = f32 / 1 = f64, x_lens / y_lens i32 [B] or None, window (< 0: no
         band), slope, dist f64 [B] out, path i32 [B, 2, path_ld] + path_len i32 [B] out or None, acc f64 [B, x_ld, y_ld] out or None,
         moments f64 [B, 2, 4] out or None (F = 1)."""
-        a = dtw_args(B, **kw)
-        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_DTW, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_DTW)")
+        self._fetch_block(OUT_DTW, dtw_args(B, **kw), stream)
 
     def disc(self, B, stream, **kw):
         """HifiGAN's discriminators on B waveform pairs (dtts_text2mel_fetch(DTTS_OUT_DISC); needs PART_DISC finalised, no encode).  Keywords:
         those of ``disc_args`` — y, y_hat f32 [B, wav_ld], lens i32 [B] or None, which (DISC_MPD | DISC_MSD | DISC_FM), sums f64 [B, 8, 4],
         counts i64 [B, 8], status i32 [B] out, fm f64 [B, 8, 8] + fm_counts i64 [B, 8, 8] out (DISC_FM), d f32 [8, 2, B, d_ld] out or None."""
-        a = disc_args(B, **kw)
-        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_DISC, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_DISC)")
+        self._fetch_block(OUT_DISC, disc_args(B, **kw), stream)
 
     def meldisc(self, n_sig, stream, **kw):
         """the multi-window mel discriminator on clips of n_sig mels (dtts_text2mel_fetch(DTTS_OUT_MELDISC); needs PART_MELDISC finalised, no
         encode).  Keywords: those of ``meldisc_args`` — mel f32 [n_sig, T_ld, 80], lens i32 [n_sig] or None, n_win, clips_ld, starts i32
         [n_win, n_sig, clips_ld] or None (then hop), reduction, flags, sums f64 [n_sig, 3, 2], counts i64 [n_sig, 3], status i32 [n_sig] out,
         d f32 [n_win, n_sig, clips_ld, 16] out or None, h 9 x f32 [n_sig, clips_ld, t, f, H] out or None."""
-        a = meldisc_args(n_sig, **kw)
-        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_MELDISC, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_MELDISC)")
+        self._fetch_block(OUT_MELDISC, meldisc_args(n_sig, **kw), stream)
 
     def spkenc(self, B, stream, **kw):
         """utterance embeddings of B recordings or mel sequences (dtts_text2mel_fetch(DTTS_OUT_SPKENC); needs PART_SPKENC finalised, no
         encode).  Keywords: those of ``spkenc_args`` — wav f32 [B, wav_ld] (SPKENC_FROM_MELS: mels f32 [B, wav_ld, 40]), lens i32 [B] or
         None, frame_step, min_coverage, pad_mode, tile_m, embed f32 [B, 256] and n_partials i32 [B] out, partials f32 [B, P, 256], mel f32
         [B, F, 40], hseq 3 x f32 [B, P, T, 256] out or None (P = spkenc_max_partials, F = spkenc_frames_ld)."""
-        a = spkenc_args(B, **kw)
-        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_SPKENC, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_SPKENC)")
+        self._fetch_block(OUT_SPKENC, spkenc_args(B, **kw), stream)
 
     def pitch(self, B, stream, **kw):
         """F0 tracks of B waveforms (dtts_text2mel_fetch(DTTS_OUT_PITCH); needs no weights and no encode).  Keywords: those of
         ``pitch_args`` — wav f32 [B, wav_ld], lens i32 [B] or None, the analysis parameters, f0 f64 [B, frames_ld] and n_frames i32 [B] out,
         and the optional stage outputs acf f64 [B, frames_ld, n_lag], cand f64 [B, frames_ld, 15, 2], n_cand i32 [B, frames_ld], intensity
         f64 [B, frames_ld], selected i32 [B, frames_ld]."""
-        a = pitch_args(B, **kw)
-        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_PITCH, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_PITCH)")
+        self._fetch_block(OUT_PITCH, pitch_args(B, **kw), stream)
 
     def load_resample_filter(self, half_window, num_table):
         """the resampler's plan: half_window f64 [n_win] (the right half of the windowed sinc, n_win - 1 a multiple of num_table) and its
@@ -530,15 +531,13 @@ class Context:
         """band-limited resampling of B waveforms (dtts_text2mel_fetch(DTTS_OUT_RESAMPLE); needs PART_RESAMPLE finalised, no encode).
         Keywords: those of ``resample_args`` — wav f32 [B, wav_ld], lens i32 [B] or None, sr_in, sr_out, out f32 [B, out_ld] and out_lens
         i32 [B] out, out64 f64 [B, out_ld] or None: the accumulators before their one rounding."""
-        a = resample_args(B, **kw)
-        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_RESAMPLE, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_RESAMPLE)")
+        self._fetch_block(OUT_RESAMPLE, resample_args(B, **kw), stream)
 
     def loudness(self, B, stream, **kw):
         """BS.1770 integrated loudness of B waveforms and, with mode=1, their normalisation (dtts_text2mel_fetch(DTTS_OUT_LOUDNESS); needs no
         weights and no encode).  Keywords: those of ``loudness_args`` — wav f32 [B, wav_ld], lens i32 [B] or None, sample_rate, target_lufs,
         lufs f64 [B], gain f64 [B] and status i32 [B] out, out f32 [B, wav_ld] (mode 1), z f64 [B, blocks_ld] and n_blocks i32 [B] or None."""
-        a = loudness_args(B, **kw)
-        self._chk(self.lib.dtts_text2mel_fetch(self.h, OUT_LOUDNESS, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_OUT_LOUDNESS)")
+        self._fetch_block(OUT_LOUDNESS, loudness_args(B, **kw), stream)
 
     def fetch(self, what, dst, stream):
         self._chk(self.lib.dtts_text2mel_fetch(self.h, what, dst, stream), "dtts_text2mel_fetch")

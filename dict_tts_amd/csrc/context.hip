@@ -14,7 +14,70 @@ constexpr int TUNE_RELEASE_MASK = (1 << 8) | (1 << 9) | (1 << 12) | (1 << 13) | 
 
 static std::string g_create_err;
 
+// every workspace arena of a context, in the order dtts_debug_check names its zones: creation (the debug flag), destruction and the
+// red-zone mode walk this list and nothing else, so an arena that is in it cannot leak or escape the check
+static const struct { const char* name; Arena dtts_ctx::*a; } ARENAS[] = {
+    {"encode workspace", &dtts_ctx::a_enc},          {"decode workspace", &dtts_ctx::a_dec},
+    {"vocoder workspace", &dtts_ctx::a_voc},         {"fft workspace", &dtts_ctx::a_fft},
+    {"speaker workspace", &dtts_ctx::a_spk},         {"posterior workspace", &dtts_ctx::a_post},
+    {"stft workspace", &dtts_ctx::a_stft},           {"spectral workspace", &dtts_ctx::a_spec},
+    {"loss workspace", &dtts_ctx::a_loss},           {"dtw workspace", &dtts_ctx::a_dtw},
+    {"pitch workspace", &dtts_ctx::a_pitch},         {"loudness workspace", &dtts_ctx::a_loud},
+    {"discriminator workspace", &dtts_ctx::a_disc},  {"speaker encoder workspace", &dtts_ctx::a_spkenc},
+    {"mel discriminator workspace", &dtts_ctx::a_meldisc}};
+constexpr int ARENA_VOC = 2;   // dtts_debug_poke looks at this one first
+
 namespace dtts {
+
+template <class A, int (*F)(dtts_ctx*, const A*, hipStream_t)>
+static int as_block(dtts_ctx* h, const void* a, hipStream_t s) {
+    return F(h, (const A*)a, s);
+}
+#define PART(X) DTTS_PART_##X, "DTTS_PART_" #X
+#define NO_PART 0, nullptr, nullptr, nullptr, false, nullptr
+#define ITEM(X, A, F) DTTS_OUT_##X, as_block<A, F>
+#define NO_ITEM 0, nullptr, false
+
+// The parts come in build order; nothing else depends on where a row stands
+static const Unit UNITS[] = {
+    {PART(ACOUSTIC), "model.", build_acoustic, true, [](const dtts_ctx* h) { return h->acoustic_ready; }, NO_ITEM},
+    {PART(VOCODER), "vocoder.", build_vocoder, true, [](const dtts_ctx* h) { return h->vocoder_ready; }, NO_ITEM},
+    {PART(FFT), "fft.", build_fft, true, [](const dtts_ctx* h) { return h->fft_ready; }, NO_ITEM},
+    {PART(MELSPEC), "melspec.", build_melspec, false, [](const dtts_ctx* h) { return h->melspec_ready; },
+     ITEM(MELSPEC, dtts_melspec_args, melspec_forward), false},
+    {PART(STFT), "stft.", build_stft, false, [](const dtts_ctx* h) { return !h->stft_plans.empty(); },
+     ITEM(STFT_DISTANCE, dtts_stft_args, stft_forward), false},
+    {PART(ISTFT), "istft.", build_istft, false, [](const dtts_ctx* h) { return h->istft_ready; },
+     ITEM(SPECTRAL, dtts_spectral_args, spectral_forward), false},
+    {NO_PART, ITEM(GRIFFIN_LIM, dtts_griffinlim_args, griffin_lim), false},   // runs on the ISTFT part's plan
+    {NO_PART, ITEM(LOSSES, dtts_loss_args, losses_forward), false},
+    {NO_PART, ITEM(DTW, dtts_dtw_args, dtw_forward), true},
+    {NO_PART, ITEM(PITCH, dtts_pitch_args, pitch_forward), true},
+    {PART(RESAMPLE), "resample.", build_resample, false, [](const dtts_ctx* h) { return h->resample_ready; },
+     ITEM(RESAMPLE, dtts_resample_args, resample_forward), true},
+    {NO_PART, ITEM(LOUDNESS, dtts_loudness_args, loudness_forward), true},
+    {PART(DISC), "disc.", build_disc, true, [](const dtts_ctx* h) { return h->disc_ready; }, ITEM(DISC, dtts_disc_args, disc_forward), true},
+    {PART(SPKENC), "spkenc.", build_spkenc, true, [](const dtts_ctx* h) { return h->spkenc_ready; },
+     ITEM(SPKENC, dtts_spkenc_args, spkenc_forward), true},
+    {PART(MELDISC), "meldisc.", build_meldisc, true, [](const dtts_ctx* h) { return h->meldisc_ready; },
+     ITEM(MELDISC, dtts_meldisc_args, meldisc_forward), true},
+};
+#undef PART
+#undef NO_PART
+#undef ITEM
+#undef NO_ITEM
+
+const Unit* find_item(int what) {
+    for (const Unit& u : UNITS)
+        if (u.forward && u.out == what) return &u;
+    return nullptr;
+}
+
+int Block::finalized(int part) const {
+    for (const Unit& u : UNITS)
+        if (u.part == part) return u.ready(h) ? 0 : fail(h, DTTS_E_STATE, "%s before dtts_finalize_weights(%s)", me, u.part_name);
+    return fail(h, DTTS_E_INVAL, "%s: no part 0x%x", me, (unsigned)part);
+}
 
 int fail(dtts_ctx* h, int code, const char* fmt, ...) {
     char buf[512];
@@ -130,7 +193,7 @@ int dtts_create(const dtts_config* cfg, dtts_handle* out) {
     if (hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || h->n_cu <= 0) h->n_cu = 256;
     h->debug_rz = cfg->debug_redzone != 0;
     h->debug_misorder = cfg->debug_redzone == 2;
-    h->a_fft.debug = h->a_enc.debug = h->a_dec.debug = h->a_voc.debug = h->a_spk.debug = h->a_post.debug = h->a_stft.debug = h->a_spec.debug = h->a_loss.debug = h->a_dtw.debug = h->a_pitch.debug = h->a_loud.debug = h->a_disc.debug = h->a_spkenc.debug = h->a_meldisc.debug = h->debug_rz;
+    for (const auto& a : ARENAS) (h->*a.a).debug = h->debug_rz;
     *out = h;
     return DTTS_OK;
 }
@@ -145,21 +208,7 @@ void dtts_destroy(dtts_handle h) {
     (void)hipDeviceSynchronize();
     for (void* p : h->allocs) (void)hipFree(p);
     if (h->amax_bits) (void)hipFree(h->amax_bits);
-    h->a_fft.release();
-    h->a_enc.release();
-    h->a_dec.release();
-    h->a_voc.release();
-    h->a_spk.release();
-    h->a_post.release();
-    h->a_stft.release();
-    h->a_spec.release();
-    h->a_loss.release();
-    h->a_dtw.release();
-    h->a_pitch.release();
-    h->a_loud.release();
-    h->a_disc.release();
-    h->a_spkenc.release();
-    h->a_meldisc.release();
+    for (const auto& a : ARENAS) (h->*a.a).release();
     for (auto& t : h->timers)
         for (auto e : t.pool) (void)hipEventDestroy(e);
     delete h;
@@ -185,37 +234,19 @@ int dtts_load_weight(dtts_handle h, const char* name, const void* host_ptr, cons
 int dtts_finalize_weights(dtts_handle h, int parts) {
     if (!h) return DTTS_E_INVAL;
     h->err.clear();
-    int rc = DTTS_OK;
-    if ((parts & DTTS_PART_ACOUSTIC) && !h->acoustic_ready) rc = build_acoustic(h);
-    if (rc == DTTS_OK && (parts & DTTS_PART_VOCODER) && !h->vocoder_ready) rc = build_vocoder(h);
-    if (rc == DTTS_OK && (parts & DTTS_PART_FFT) && !h->fft_ready) rc = build_fft(h);
-    const bool ms = rc == DTTS_OK && (parts & DTTS_PART_MELSPEC);   // every call rebuilds this plan from the tensors loaded last
-    if (ms) rc = build_melspec(h);
-    const bool st = rc == DTTS_OK && (parts & DTTS_PART_STFT);      // and so does this one
-    if (st) rc = build_stft(h);
-    const bool is = rc == DTTS_OK && (parts & DTTS_PART_ISTFT);     // and this one
-    if (is) rc = build_istft(h);
-    const bool rs = rc == DTTS_OK && (parts & DTTS_PART_RESAMPLE);  // and this one
-    if (rs) rc = build_resample(h);
-    if (rc == DTTS_OK && (parts & DTTS_PART_DISC) && !h->disc_ready) rc = build_disc(h);
-    if (rc == DTTS_OK && (parts & DTTS_PART_SPKENC) && !h->spkenc_ready) rc = build_spkenc(h);
-    if (rc == DTTS_OK && (parts & DTTS_PART_MELDISC) && !h->meldisc_ready) rc = build_meldisc(h);
-    if (rc == DTTS_OK) {
-        // host copies are no longer needed for finished parts
-        for (auto it = h->w.begin(); it != h->w.end();) {
-            const bool a = it->first.rfind("model.", 0) == 0 && h->acoustic_ready;
-            const bool v = it->first.rfind("vocoder.", 0) == 0 && h->vocoder_ready;
-            const bool f = it->first.rfind("fft.", 0) == 0 && h->fft_ready;
-            const bool m = it->first.rfind("melspec.", 0) == 0 && ms;
-            const bool s = it->first.rfind("stft.", 0) == 0 && st;
-            const bool i = it->first.rfind("istft.", 0) == 0 && is;
-            const bool r = it->first.rfind("resample.", 0) == 0 && rs;
-            const bool d = it->first.rfind("disc.", 0) == 0 && h->disc_ready;
-            const bool e = it->first.rfind("spkenc.", 0) == 0 && h->spkenc_ready;
-            const bool g = it->first.rfind("meldisc.", 0) == 0 && h->meldisc_ready;
-            it = (a || v || f || m || s || i || r || d || e || g) ? h->w.erase(it) : std::next(it);
+    int rc = DTTS_OK, built = 0;   // built: the parts this call (re)built
+    for (const Unit& u : UNITS)
+        if (rc == DTTS_OK && (parts & u.part) && !(u.once && u.ready(h))) {
+            rc = u.build(h);
+            built |= u.part;
         }
-    }
+    if (rc == DTTS_OK)   // host copies are no longer needed for finished parts: those built once, and what this call rebuilt
+        for (auto it = h->w.begin(); it != h->w.end();) {
+            bool done = false;
+            for (const Unit& u : UNITS)
+                if (u.part && it->first.rfind(u.prefix, 0) == 0) done = u.once ? u.ready(h) : (built & u.part) != 0;
+            it = done ? h->w.erase(it) : std::next(it);
+        }
     return rc;
 }
 
@@ -279,8 +310,10 @@ int dtts_debug_poke(dtts_handle h, dtts_stream stream) {
     if (!h) return DTTS_E_INVAL;
     if (!h->debug_rz) return fail(h, DTTS_E_STATE, "dtts_debug_poke: the context was not created with dtts_config.debug_redzone = 1");
     char* target = nullptr;
-    for (Arena* a : {&h->a_voc, &h->a_enc, &h->a_dec, &h->a_fft, &h->a_spk, &h->a_post, &h->a_stft, &h->a_spec, &h->a_loss, &h->a_dtw, &h->a_pitch, &h->a_loud, &h->a_disc, &h->a_spkenc, &h->a_meldisc})
-        if (!target && a->base && !a->bufs.empty()) target = a->base + a->bufs[0].start + a->bufs[0].bytes;
+    for (int i = -1; i < (int)(sizeof ARENAS / sizeof ARENAS[0]); ++i) {   // the vocoder's first, then in the list's order
+        const Arena& a = h->*ARENAS[i < 0 ? ARENA_VOC : i].a;
+        if (!target && a.base && !a.bufs.empty()) target = a.base + a.bufs[0].start + a.bufs[0].bytes;
+    }
     if (!target && !h->rz_static.empty()) target = h->rz_static[0].p + h->rz_static[0].bytes;
     if (!target) return fail(h, DTTS_E_STATE, "dtts_debug_poke: nothing allocated yet");
     HIPCHK(hipMemsetAsync(target, 0, 1, (hipStream_t)stream));
@@ -300,16 +333,16 @@ int dtts_debug_check(dtts_handle h, int64_t* damaged_bytes, dtts_stream stream) 
         zones.push_back({(const unsigned char*)p0, (unsigned)n, (unsigned)names.size()});
         names.push_back(name);
     };
-    const std::pair<const char*, Arena*> arenas[] = {{"encode workspace", &h->a_enc}, {"decode workspace", &h->a_dec}, {"vocoder workspace", &h->a_voc}, {"fft workspace", &h->a_fft}, {"speaker workspace", &h->a_spk}, {"posterior workspace", &h->a_post}, {"stft workspace", &h->a_stft}, {"spectral workspace", &h->a_spec}, {"loss workspace", &h->a_loss}, {"dtw workspace", &h->a_dtw}, {"pitch workspace", &h->a_pitch}, {"loudness workspace", &h->a_loud}, {"discriminator workspace", &h->a_disc}, {"speaker encoder workspace", &h->a_spkenc}, {"mel discriminator workspace", &h->a_meldisc}};
-    for (const auto& a : arenas) {
-        const auto& bufs = a.second->bufs;
-        const char* base = a.second->base;
+    for (const auto& a : ARENAS) {
+        const Arena& arena = h->*a.a;
+        const auto& bufs = arena.bufs;
+        const char* base = arena.base;
         for (size_t i = 0; i < bufs.size(); ++i) {   // layout: [RZ][buffer 0][slack to 256 B][RZ][buffer 1]...[RZ .. up to the arena's end]
-            const std::string me = std::string(a.first) + " buffer #" + std::to_string(i) + " (" + std::to_string(bufs[i].bytes) + " B)";
+            const std::string me = std::string(a.name) + " buffer #" + std::to_string(i) + " (" + std::to_string(bufs[i].bytes) + " B)";
             const size_t end = bufs[i].start + bufs[i].bytes, padded_end = bufs[i].start + ((bufs[i].bytes + 255) & ~(size_t)255);
-            zone(base + bufs[i].start - RZ, RZ, i ? "AFTER " + std::string(a.first) + " buffer #" + std::to_string(i - 1) + " / BEFORE " + me : "BEFORE " + me);
+            zone(base + bufs[i].start - RZ, RZ, i ? "AFTER " + std::string(a.name) + " buffer #" + std::to_string(i - 1) + " / BEFORE " + me : "BEFORE " + me);
             zone(base + end, padded_end - end, "AFTER " + me + " (alignment slack)");
-            if (i + 1 == bufs.size()) zone(base + padded_end, std::min(RZ, a.second->cap - padded_end), "AFTER " + me);
+            if (i + 1 == bufs.size()) zone(base + padded_end, std::min(RZ, arena.cap - padded_end), "AFTER " + me);
         }
     }
     for (size_t i = 0; i < h->rz_static.size(); ++i) {

@@ -301,6 +301,32 @@ namespace dtts {
 // context.hip: records the message (h == null: for dtts_last_error(NULL)) and returns `code`
 int fail(dtts_ctx* h, int code, const char* fmt, ...);
 
+// ---- what the *_forward of every fetch unit opens with: the refusals of an argument block, each in its one wording (tests match the texts).
+// A method returns 0 where there is nothing to refuse, else the code it recorded: `if (int rc = blk.size(a->size, sizeof *a)) return rc;`
+struct Block {
+    dtts_ctx* h;
+    const char* me;   // "dtts_text2mel_fetch(DTTS_OUT_X)"
+    int size(int got, size_t want) const {
+        return got == (int)want ? 0 : fail(h, DTTS_E_INVAL, "%s: argument block of size = %d bytes, this library's is %d", me, got, (int)want);
+    }
+    template <size_t N>   // (an array of fixed length, so that the loop unrolls where n is a constant)
+    int aligned(int n, const std::pair<const char*, const void*> (&ptrs)[N]) const {   // n: a power of two; null counts as aligned
+        for (const auto& q : ptrs)
+            if ((uintptr_t)q.second & (uintptr_t)(n - 1)) return fail(h, DTTS_E_INVAL, "%s: %s = %p is not aligned to %d bytes", me, q.first, q.second, n);
+        return 0;
+    }
+    int handle() const { return h ? 0 : fail(nullptr, DTTS_E_INVAL, "%s: null handle", me); }
+    int finalized(int part) const;   // context.hip: the part's row of UNITS says whether it is ready
+    int workspace() const { return fail(h, DTTS_E_NOMEM, "%s: workspace", me); }
+};
+
+// the largest chunk of a batch of n whose workspace of bytes(chunk) stays within cap, found by halving (a chunk of 1 is taken as it is)
+template <class F>
+int chunk_within(int n, size_t cap, F bytes) {
+    while (n > 1 && bytes(n) > cap) n = (n + 1) / 2;
+    return n;
+}
+
 #define HIPCHK(expr)                                                                                       \
     do {                                                                                                   \
         hipError_t _e = (expr);                                                                            \
@@ -412,5 +438,21 @@ int build_spkenc(dtts_ctx* h);    // spkenc.hip
 int spkenc_forward(dtts_ctx* h, const dtts_spkenc_args* a, hipStream_t stream);       // spkenc.hip (the same)
 int build_meldisc(dtts_ctx* h);   // meldisc.hip
 int meldisc_forward(dtts_ctx* h, const dtts_meldisc_args* a, hipStream_t stream);     // meldisc.hip (the same)
+
+// ---- a row of the one table of parts and block items (UNITS, context.hip): dtts_finalize_weights walks its parts in row order,
+// dtts_text2mel_fetch finds the item's forward in it, Block::finalized the part's ready predicate.  A row may be a part without an item
+// (the acoustic model), an item without a part (the losses), or both
+struct Unit {
+    int part;                        // DTTS_PART_* bit, or 0: the item has no part of its own
+    const char* part_name;           // "DTTS_PART_X"
+    const char* prefix;              // the part owns the tensors named "<prefix>..." (the dot included)
+    int (*build)(dtts_ctx*);
+    bool once;                       // built once per context; false: rebuilt by every finalize that names it, from the tensors loaded last
+    bool (*ready)(const dtts_ctx*);
+    int out;                         // DTTS_OUT_* whose dst is this unit's argument block, or 0
+    int (*forward)(dtts_ctx*, const void*, hipStream_t);
+    bool null_handle;                // the forward checks its block before the handle, so it is reached with a null one too
+};
+const Unit* find_item(int what);   // the row whose argument block DTTS_OUT_<what> takes, or null
 
 } // namespace dtts

@@ -488,8 +488,8 @@ size_t plan_bytes(const DiscPlan& pl, int Bc) {
 // h may be null: the block is checked first, so that the refusals are reachable without a device
 int disc_forward(dtts_ctx* h, const dtts_disc_args* a, hipStream_t stream) {
     const char* me = "dtts_text2mel_fetch(DTTS_OUT_DISC)";
-    if (a->size != (int32_t)sizeof(dtts_disc_args))
-        return fail(h, DTTS_E_INVAL, "%s: argument block of size = %d bytes, this library's is %d", me, a->size, (int)sizeof(dtts_disc_args));
+    const Block blk{h, me};
+    if (int rc = blk.size(a->size, sizeof *a)) return rc;
     if (a->B < 1 || a->B > 65535) return fail(h, DTTS_E_INVAL, "%s: B = %d (supported: 1 .. 65535)", me, a->B);
     if (a->wav_ld < DTTS_DISC_MIN_LEN)
         return fail(h, DTTS_E_INVAL, "%s: wav_ld = %d samples is below DTTS_DISC_MIN_LEN = %d, the shortest waveform the reference's discriminators accept", me,
@@ -505,16 +505,11 @@ int disc_forward(dtts_ctx* h, const dtts_disc_args* a, hipStream_t stream) {
     if (fm && (!a->fm_dev || !a->fm_counts_dev)) return fail(h, DTTS_E_INVAL, "%s: DTTS_DISC_FM without fm_dev / fm_counts_dev", me);
     const int d_need = (a->wav_ld + 63) / 64 + 16;
     if (a->d_dev && a->d_ld < d_need) return fail(h, DTTS_E_INVAL, "%s: d_ld = %d entries for wav_ld = %d (needs %d)", me, a->d_ld, a->wav_ld, d_need);
-    const std::pair<const char*, const void*> p4[] = {{"y_dev", a->y_dev}, {"y_hat_dev", a->y_hat_dev}, {"lens_dev", a->lens_dev}, {"d_dev", a->d_dev},
-                                                      {"status_dev", a->status_dev}};
-    for (const auto& q : p4)
-        if ((uintptr_t)q.second & 3) return fail(h, DTTS_E_INVAL, "%s: %s = %p is not aligned to 4 bytes", me, q.first, q.second);
-    const std::pair<const char*, const void*> p8[] = {{"sums_dev", a->sums_dev}, {"counts_dev", a->counts_dev}, {"fm_dev", a->fm_dev},
-                                                      {"fm_counts_dev", a->fm_counts_dev}};
-    for (const auto& q : p8)
-        if ((uintptr_t)q.second & 7) return fail(h, DTTS_E_INVAL, "%s: %s = %p is not aligned to 8 bytes", me, q.first, q.second);
-    if (!h) return fail(nullptr, DTTS_E_INVAL, "%s: null handle", me);
-    if (!h->disc_ready) return fail(h, DTTS_E_STATE, "%s before dtts_finalize_weights(DTTS_PART_DISC)", me);
+    if (int rc = blk.aligned(4, {{"y_dev", a->y_dev}, {"y_hat_dev", a->y_hat_dev}, {"lens_dev", a->lens_dev}, {"d_dev", a->d_dev}, {"status_dev", a->status_dev}}))
+        return rc;
+    if (int rc = blk.aligned(8, {{"sums_dev", a->sums_dev}, {"counts_dev", a->counts_dev}, {"fm_dev", a->fm_dev}, {"fm_counts_dev", a->fm_counts_dev}})) return rc;
+    if (int rc = blk.handle()) return rc;
+    if (int rc = blk.finalized(DTTS_PART_DISC)) return rc;
 
     // measurement aid: the grouped layers as block-diagonal dense layers on conv1d_launch, packed here on first use (a host-side pack and
     // upload: this call synchronises)
@@ -537,8 +532,7 @@ int disc_forward(dtts_ctx* h, const dtts_disc_args* a, hipStream_t stream) {
 
     const int ld = a->wav_ld;
     const DiscPlan pl = disc_plan(ld, a->which);
-    int Bc = std::min(a->B, 65535 / (2 * DISC_MAX_P));
-    while (Bc > 1 && plan_bytes(pl, Bc) > (size_t)DTTS_DISC_WS_BYTES) Bc = (Bc + 1) / 2;
+    const int Bc = chunk_within(std::min(a->B, 65535 / (2 * DISC_MAX_P)), DTTS_DISC_WS_BYTES, [&](int n) { return plan_bytes(pl, n); });
     HIPCHK(h->a_disc.reserve(plan_bytes(pl, Bc), stream));
 
     for (int b0 = 0; b0 < a->B; b0 += Bc) {
@@ -553,7 +547,7 @@ int disc_forward(dtts_ctx* h, const dtts_disc_args* a, hipStream_t stream) {
         float* pool1 = (a->which & DTTS_DISC_MSD) ? ws.alloc<float>(pl.pool1 * B) : nullptr;
         float* pool2 = (a->which & DTTS_DISC_MSD) ? ws.alloc<float>(pl.pool2 * B) : nullptr;
         if (!vlen || !tab || !act[0] || !act[1] || !dws || (fm && !part) || ((a->which & DTTS_DISC_MSD) && (!pool1 || !pool2)))
-            return fail(h, DTTS_E_NOMEM, "%s: workspace", me);
+            return blk.workspace();
         const float* y = a->y_dev + (size_t)b0 * ld;
         const float* yh = a->y_hat_dev + (size_t)b0 * ld;
         hipLaunchKernelGGL(disc_vlen_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, a->lens_dev ? a->lens_dev + b0 : nullptr, B, ld, vlen,

@@ -349,8 +349,8 @@ hipError_t dtw_path_launch(const DtwParams& p, hipStream_t stream) {
 // h may be null: the block is checked first, so that the refusals are reachable without a device
 int dtw_forward(dtts_ctx* h, const dtts_dtw_args* a, hipStream_t stream) {
     const char* me = "dtts_text2mel_fetch(DTTS_OUT_DTW)";
-    if (a->size != (int32_t)sizeof(dtts_dtw_args))
-        return fail(h, DTTS_E_INVAL, "%s: argument block of size = %d bytes, this library's is %d", me, a->size, (int)sizeof(dtts_dtw_args));
+    const Block blk{h, me};
+    if (int rc = blk.size(a->size, sizeof *a)) return rc;
     if (a->B <= 0) return fail(h, DTTS_E_INVAL, "%s: B = %d", me, a->B);
     if (a->F < 1 || a->F > DTW_MAX_F) return fail(h, DTTS_E_INVAL, "%s: F = %d (supported: 1 .. %d)", me, a->F, DTW_MAX_F);
     if (a->dtype != 0 && a->dtype != 1) return fail(h, DTTS_E_INVAL, "%s: dtype = %d (0 = f32, 1 = f64)", me, a->dtype);
@@ -362,18 +362,11 @@ int dtw_forward(dtts_ctx* h, const dtts_dtw_args* a, hipStream_t stream) {
     if (a->path_dev && a->path_ld < a->x_ld + a->y_ld - 1)
         return fail(h, DTTS_E_INVAL, "%s: path_ld = %d entries for x_ld + y_ld - 1 = %d", me, a->path_ld, a->x_ld + a->y_ld - 1);
     if (a->moments_dev && a->F > 1) return fail(h, DTTS_E_INVAL, "%s: moments_dev with F = %d (the moments are those of 1-D tracks)", me, a->F);
-    const uintptr_t in_mask = a->dtype == 1 ? 7 : 3;
-    const std::pair<const char*, const void*> pin[] = {{"x_dev", a->x_dev}, {"y_dev", a->y_dev}};
-    for (const auto& q : pin)
-        if ((uintptr_t)q.second & in_mask) return fail(h, DTTS_E_INVAL, "%s: %s = %p is not aligned to %d bytes", me, q.first, q.second, (int)in_mask + 1);
-    const std::pair<const char*, const void*> p4[] = {{"x_lens_dev", a->x_lens_dev}, {"y_lens_dev", a->y_lens_dev}, {"path_dev", a->path_dev},
-                                                      {"path_len_dev", a->path_len_dev}};
-    for (const auto& q : p4)
-        if ((uintptr_t)q.second & 3) return fail(h, DTTS_E_INVAL, "%s: %s = %p is not aligned to 4 bytes", me, q.first, q.second);
-    const std::pair<const char*, const void*> p8[] = {{"dist_dev", a->dist_dev}, {"acc_dev", a->acc_dev}, {"moments_dev", a->moments_dev}};
-    for (const auto& q : p8)
-        if ((uintptr_t)q.second & 7) return fail(h, DTTS_E_INVAL, "%s: %s = %p is not aligned to 8 bytes", me, q.first, q.second);
-    if (!h) return fail(nullptr, DTTS_E_INVAL, "%s: null handle", me);
+    if (int rc = blk.aligned(a->dtype == 1 ? 8 : 4, {{"x_dev", a->x_dev}, {"y_dev", a->y_dev}})) return rc;
+    if (int rc = blk.aligned(4, {{"x_lens_dev", a->x_lens_dev}, {"y_lens_dev", a->y_lens_dev}, {"path_dev", a->path_dev}, {"path_len_dev", a->path_len_dev}}))
+        return rc;
+    if (int rc = blk.aligned(8, {{"dist_dev", a->dist_dev}, {"acc_dev", a->acc_dev}, {"moments_dev", a->moments_dev}})) return rc;
+    if (int rc = blk.handle()) return rc;
 
     DtwParams p{};
     p.x = a->x_dev;
@@ -398,11 +391,11 @@ int dtw_forward(dtts_ctx* h, const dtts_dtw_args* a, hipStream_t stream) {
         HIPCHK(h->a_dtw.reserve(((size_t)a->B * dir_words * sizeof(unsigned) + 256) + ((size_t)a->B * cost_words * sizeof(double) + 256), stream));
         if (dir_words) {
             p.dirs = h->a_dtw.alloc<unsigned>((size_t)a->B * dir_words);
-            if (!p.dirs) return fail(h, DTTS_E_NOMEM, "%s: workspace", me);
+            if (!p.dirs) return blk.workspace();
         }
         if (cost_words) {
             p.cost_w = h->a_dtw.alloc<double>((size_t)a->B * cost_words);
-            if (!p.cost_w) return fail(h, DTTS_E_NOMEM, "%s: workspace", me);
+            if (!p.cost_w) return blk.workspace();
             p.cost = p.cost_w;
         }
         p.dir_stride = dir_words;

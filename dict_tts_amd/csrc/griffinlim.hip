@@ -166,9 +166,9 @@ static hipError_t gl_project_launch(const SpecFwdParams& p, const GlProjParams& 
 // workspace grows
 int griffin_lim(dtts_ctx* h, const dtts_griffinlim_args* a, hipStream_t stream) {
     const char* me = "dtts_text2mel_fetch(DTTS_OUT_GRIFFIN_LIM)";
-    if (a->size != (int32_t)sizeof(dtts_griffinlim_args))
-        return fail(h, DTTS_E_INVAL, "%s: argument block of size = %d bytes, this library's is %d", me, a->size, (int)sizeof(dtts_griffinlim_args));
-    if (!h->istft_ready) return fail(h, DTTS_E_STATE, "%s before dtts_finalize_weights(DTTS_PART_ISTFT)", me);
+    const Block blk{h, me};
+    if (int rc = blk.size(a->size, sizeof *a)) return rc;
+    if (int rc = blk.finalized(DTTS_PART_ISTFT)) return rc;
     const int N = h->is.n_fft, bins = N / 2 + 1;
     if (a->B <= 0) return fail(h, DTTS_E_INVAL, "%s: B = %d", me, a->B);
     if (a->spec_cap <= 0) return fail(h, DTTS_E_INVAL, "%s: spec_cap = %d rows", me, a->spec_cap);
@@ -185,11 +185,10 @@ int griffin_lim(dtts_ctx* h, const dtts_griffinlim_args* a, hipStream_t stream) 
     if (L > INT_MAX || a->wav_ld < L) return fail(h, DTTS_E_INVAL, "%s: wav_ld = %d samples, spec_cap = %d rows at hop %d give %lld", me, a->wav_ld, a->spec_cap, a->hop, L);
     if (int e = check_wav_ld(h, me, (int)L, N)) return e;
     if (!a->out_dev && a->wav_ld > 0) return fail(h, DTTS_E_INVAL, "%s: null out_dev", me);
-    const std::pair<const char*, const void*> f4[] = {{"mag_dev", a->mag_dev}, {"mel_dev", a->mel_dev}, {"frames_dev", a->frames_dev}, {"out_dev", a->out_dev}, {"out_lens_dev", a->out_lens_dev}};
-    for (const auto& q : f4)
-        if ((uintptr_t)q.second & 3) return fail(h, DTTS_E_INVAL, "%s: %s = %p is not aligned to 4 bytes", me, q.first, q.second);
-    if ((uintptr_t)a->init_dev & 7) return fail(h, DTTS_E_INVAL, "%s: init_dev = %p is not aligned to 8 bytes", me, (const void*)a->init_dev);
-    if ((uintptr_t)a->spec_out_dev & 7) return fail(h, DTTS_E_INVAL, "%s: spec_out_dev = %p is not aligned to 8 bytes", me, (void*)a->spec_out_dev);
+    if (int rc = blk.aligned(4, {{"mag_dev", a->mag_dev}, {"mel_dev", a->mel_dev}, {"frames_dev", a->frames_dev}, {"out_dev", a->out_dev},
+                                 {"out_lens_dev", a->out_lens_dev}}))
+        return rc;
+    if (int rc = blk.aligned(8, {{"init_dev", a->init_dev}, {"spec_out_dev", a->spec_out_dev}})) return rc;
     if (int e = check_envelope(h, me, a->hop)) return e;
     const int cap = a->spec_cap, Li = (int)L;
     const long long n_tiles_inv = (long long)a->B * ((cap + ISTFT_TILE - 1) / ISTFT_TILE);
@@ -208,7 +207,7 @@ int griffin_lim(dtts_ctx* h, const dtts_griffinlim_args* a, hipStream_t stream) 
     float* fr = h->a_spec.alloc<float>(n_fr);
     float* y = n_y ? h->a_spec.alloc<float>(n_y) : nullptr;
     int* frames = h->a_spec.alloc<int>((size_t)a->B);
-    if (!A || !spec || !fr || (n_y && !y) || !frames) return fail(h, DTTS_E_NOMEM, "%s: workspace", me);
+    if (!A || !spec || !fr || (n_y && !y) || !frames) return blk.workspace();
 
     GlTargetParams t{};
     t.mag = a->mag_dev;

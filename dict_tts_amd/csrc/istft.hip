@@ -312,9 +312,9 @@ int check_envelope(dtts_ctx* h, const char* me, int hop) {
 // unless the workspace grows
 int spectral_forward(dtts_ctx* h, const dtts_spectral_args* a, hipStream_t stream) {
     const char* me = "dtts_text2mel_fetch(DTTS_OUT_SPECTRAL)";
-    if (a->size != (int32_t)sizeof(dtts_spectral_args))
-        return fail(h, DTTS_E_INVAL, "%s: argument block of size = %d bytes, this library's is %d", me, a->size, (int)sizeof(dtts_spectral_args));
-    if (!h->istft_ready) return fail(h, DTTS_E_STATE, "%s before dtts_finalize_weights(DTTS_PART_ISTFT)", me);
+    const Block blk{h, me};
+    if (int rc = blk.size(a->size, sizeof *a)) return rc;
+    if (int rc = blk.finalized(DTTS_PART_ISTFT)) return rc;
     const int N = h->is.n_fft;
     if (a->mode < 1 || a->mode > 3) return fail(h, DTTS_E_INVAL, "%s: mode = %d (DTTS_SPECTRAL_FORWARD = 1, DTTS_SPECTRAL_INVERSE = 2, or both = 3)", me, a->mode);
     const bool fwd = (a->mode & DTTS_SPECTRAL_FORWARD) != 0, inv = (a->mode & DTTS_SPECTRAL_INVERSE) != 0;
@@ -329,7 +329,7 @@ int spectral_forward(dtts_ctx* h, const dtts_spectral_args* a, hipStream_t strea
     if (inv && !a->out_dev && a->wav_ld > 0) return fail(h, DTTS_E_INVAL, "%s: null out_dev (DTTS_SPECTRAL_INVERSE writes it)", me);
     if (!(fwd && inv) && !a->spec_dev) return fail(h, DTTS_E_INVAL, "%s: null spec_dev (optional only with both mode bits)", me);
     if (!(fwd && inv) && !a->frames_dev) return fail(h, DTTS_E_INVAL, "%s: null frames_dev (optional only with both mode bits)", me);
-    if (a->spec_dev && ((uintptr_t)a->spec_dev & 7)) return fail(h, DTTS_E_INVAL, "%s: spec_dev = %p is not aligned to 8 bytes", me, (void*)a->spec_dev);
+    if (int rc = blk.aligned(8, {{"spec_dev", a->spec_dev}})) return rc;
     if (inv && a->out_dev && a->wav_dev) {   // the forward loads of one utterance would race with the gather stores of another
         const size_t n = (size_t)a->B * (size_t)a->wav_ld;
         if (a->out_dev < a->wav_dev + n && a->wav_dev < a->out_dev + n)
@@ -349,9 +349,9 @@ int spectral_forward(dtts_ctx* h, const dtts_spectral_args* a, hipStream_t strea
     float* spec = a->spec_dev;
     int* frames = a->frames_dev;
     float* fr = nullptr;
-    if (n_spec && !(spec = h->a_spec.alloc<float>(n_spec))) return fail(h, DTTS_E_NOMEM, "%s: workspace", me);
-    if (n_fr && !(fr = h->a_spec.alloc<float>(n_fr))) return fail(h, DTTS_E_NOMEM, "%s: workspace", me);
-    if (n_frames && !(frames = h->a_spec.alloc<int>(n_frames))) return fail(h, DTTS_E_NOMEM, "%s: workspace", me);
+    if (n_spec && !(spec = h->a_spec.alloc<float>(n_spec))) return blk.workspace();
+    if (n_fr && !(fr = h->a_spec.alloc<float>(n_fr))) return blk.workspace();
+    if (n_frames && !(frames = h->a_spec.alloc<int>(n_frames))) return blk.workspace();
 
     if (fwd) {
         if (h->is_skew_hop != a->hop) {

@@ -199,19 +199,17 @@ hipError_t loss_dur_launch(const LossDurParams& p, hipStream_t stream) {
 // workspace of the tile sums grows
 int losses_forward(dtts_ctx* h, const dtts_loss_args* a, hipStream_t stream) {
     const char* me = "dtts_text2mel_fetch(DTTS_OUT_LOSSES)";
-    if (a->size != (int32_t)sizeof(dtts_loss_args))
-        return fail(h, DTTS_E_INVAL, "%s: argument block of size = %d bytes, this library's is %d", me, a->size, (int)sizeof(dtts_loss_args));
+    const Block blk{h, me};
+    if (int rc = blk.size(a->size, sizeof *a)) return rc;
     const bool mel = a->mel_sums_dev != nullptr, dur = a->dur_sums_dev != nullptr;
     if (!mel && !dur) return fail(h, DTTS_E_INVAL, "%s: mel_sums_dev and dur_sums_dev are both NULL: no half requested", me);
     if (a->B <= 0) return fail(h, DTTS_E_INVAL, "%s: B = %d", me, a->B);
-    const std::pair<const char*, const void*> p4[] = {{"pred_dev", a->pred_dev}, {"tgt_dev", a->tgt_dev}, {"ssim_map_dev", a->ssim_map_dev},
-                                                      {"dur_pred_dev", a->dur_pred_dev}, {"word_len_dev", a->word_len_dev}, {"dur_gt_dev", a->dur_gt_dev}};
-    for (const auto& q : p4)
-        if ((uintptr_t)q.second & 3) return fail(h, DTTS_E_INVAL, "%s: %s = %p is not aligned to 4 bytes", me, q.first, q.second);
-    const std::pair<const char*, const void*> p8[] = {{"mel_sums_dev", a->mel_sums_dev}, {"mel_count_dev", a->mel_count_dev},
-                                                      {"mel2word_dev", a->mel2word_dev}, {"dur_sums_dev", a->dur_sums_dev}};
-    for (const auto& q : p8)
-        if ((uintptr_t)q.second & 7) return fail(h, DTTS_E_INVAL, "%s: %s = %p is not aligned to 8 bytes", me, q.first, q.second);
+    if (int rc = blk.aligned(4, {{"pred_dev", a->pred_dev}, {"tgt_dev", a->tgt_dev}, {"ssim_map_dev", a->ssim_map_dev}, {"dur_pred_dev", a->dur_pred_dev},
+                                 {"word_len_dev", a->word_len_dev}, {"dur_gt_dev", a->dur_gt_dev}}))
+        return rc;
+    if (int rc = blk.aligned(8, {{"mel_sums_dev", a->mel_sums_dev}, {"mel_count_dev", a->mel_count_dev}, {"mel2word_dev", a->mel2word_dev},
+                                 {"dur_sums_dev", a->dur_sums_dev}}))
+        return rc;
 
     LossMelParams mp{};
     if (mel) {
@@ -244,7 +242,7 @@ int losses_forward(dtts_ctx* h, const dtts_loss_args* a, hipStream_t stream) {
         HIPCHK(h->a_loss.reserve(n_part * 4 * sizeof(double) + 2 * 256, stream));
         mp.part = h->a_loss.alloc<double>(n_part * 3);
         mp.pcount = h->a_loss.alloc<long long>(n_part);
-        if (!mp.part || !mp.pcount) return fail(h, DTTS_E_NOMEM, "%s: workspace", me);
+        if (!mp.part || !mp.pcount) return blk.workspace();
         mp.pred = a->pred_dev;
         mp.tgt = a->tgt_dev;
         mp.win = h->loss_win;

@@ -304,8 +304,8 @@ hipError_t loud_launch(const LoudParams& p, hipStream_t stream) {
 // grows or a longer block table is uploaded.  h may be null: the block is checked first, so that the refusals are reachable without a device
 int loudness_forward(dtts_ctx* h, const dtts_loudness_args* a, hipStream_t stream) {
     const char* me = "dtts_text2mel_fetch(DTTS_OUT_LOUDNESS)";
-    if (a->size != (int32_t)sizeof(dtts_loudness_args))
-        return fail(h, DTTS_E_INVAL, "%s: argument block of size = %d bytes, this library's is %d", me, a->size, (int)sizeof(dtts_loudness_args));
+    const Block blk{h, me};
+    if (int rc = blk.size(a->size, sizeof *a)) return rc;
     if (a->B <= 0 || a->B > 65535) return fail(h, DTTS_E_INVAL, "%s: B = %d (supported: 1 .. 65535)", me, a->B);
     if (a->wav_ld < 1 || a->wav_ld > LOUD_MAX_WAV) return fail(h, DTTS_E_INVAL, "%s: wav_ld = %d samples (supported: 1 .. %d)", me, a->wav_ld, LOUD_MAX_WAV);
     if (a->sample_rate < 8000 || a->sample_rate > 48000) return fail(h, DTTS_E_INVAL, "%s: sample_rate = %d (supported: 8000 .. 48000)", me, a->sample_rate);
@@ -317,14 +317,11 @@ int loudness_forward(dtts_ctx* h, const dtts_loudness_args* a, hipStream_t strea
         return fail(h, DTTS_E_INVAL, "%s: blocks_ld = %d blocks (must be >= 1; wav_ld = %d samples give %d)", me, a->blocks_ld, a->wav_ld, nb_max);
     if (!a->wav_dev || !a->lufs_dev || !a->gain_dev || !a->status_dev) return fail(h, DTTS_E_INVAL, "%s: null wav_dev / lufs_dev / gain_dev / status_dev", me);
     if (a->mode == 1 && !a->out_dev) return fail(h, DTTS_E_INVAL, "%s: null out_dev with mode = 1", me);
-    const std::pair<const char*, const void*> p4[] = {{"wav_dev", a->wav_dev}, {"lens_dev", a->lens_dev}, {"status_dev", a->status_dev}, {"out_dev", a->out_dev},
-                                                      {"n_blocks_dev", a->n_blocks_dev}};
-    for (const auto& q : p4)
-        if ((uintptr_t)q.second & 3) return fail(h, DTTS_E_INVAL, "%s: %s = %p is not aligned to 4 bytes", me, q.first, q.second);
-    const std::pair<const char*, const void*> p8[] = {{"lufs_dev", a->lufs_dev}, {"gain_dev", a->gain_dev}, {"z_dev", a->z_dev}};
-    for (const auto& q : p8)
-        if ((uintptr_t)q.second & 7) return fail(h, DTTS_E_INVAL, "%s: %s = %p is not aligned to 8 bytes", me, q.first, q.second);
-    if (!h) return fail(nullptr, DTTS_E_INVAL, "%s: null handle", me);
+    if (int rc = blk.aligned(4, {{"wav_dev", a->wav_dev}, {"lens_dev", a->lens_dev}, {"status_dev", a->status_dev}, {"out_dev", a->out_dev},
+                                 {"n_blocks_dev", a->n_blocks_dev}}))
+        return rc;
+    if (int rc = blk.aligned(8, {{"lufs_dev", a->lufs_dev}, {"gain_dev", a->gain_dev}, {"z_dev", a->z_dev}})) return rc;
+    if (int rc = blk.handle()) return rc;
 
     if (h->loud_bounds_rate != a->sample_rate || h->loud_bounds_n < nb_max) {   // numpy's truncations, made here: (int)(0.4 (j 0.25) rate), (int)(0.4 (j 0.25 + 1) rate)
         const int n = nb_max + nb_max / 2 + 64;
@@ -366,7 +363,7 @@ int loudness_forward(dtts_ctx* h, const dtts_loudness_args* a, hipStream_t strea
     p.utt_max = h->a_loud.alloc<float>((size_t)a->B);
     p.z = a->z_dev ? a->z_dev : h->a_loud.alloc<double>(n_z);
     p.n_blocks = a->n_blocks_dev ? a->n_blocks_dev : h->a_loud.alloc<int>(n_nb);
-    if (!p.seg_end || !p.seg_start || !p.part || !p.seg_max || !p.utt_max || !p.z || !p.n_blocks) return fail(h, DTTS_E_NOMEM, "%s: workspace", me);
+    if (!p.seg_end || !p.seg_start || !p.part || !p.seg_max || !p.utt_max || !p.z || !p.n_blocks) return blk.workspace();
     LAUNCH(loud_launch(p, stream));
     return DTTS_OK;
 }

@@ -400,8 +400,8 @@ int build_meldisc(dtts_ctx* h) {
 // h may be null: the block is checked first, so that the refusals are reachable without a device
 int meldisc_forward(dtts_ctx* h, const dtts_meldisc_args* a, hipStream_t stream) {
     const char* me = "dtts_text2mel_fetch(DTTS_OUT_MELDISC)";
-    if (a->size != (int32_t)sizeof(dtts_meldisc_args))
-        return fail(h, DTTS_E_INVAL, "%s: argument block of size = %d bytes, this library's is %d", me, a->size, (int)sizeof(dtts_meldisc_args));
+    const Block blk{h, me};
+    if (int rc = blk.size(a->size, sizeof *a)) return rc;
     if (a->n_sig < 1 || a->n_sig > 65535) return fail(h, DTTS_E_INVAL, "%s: n_sig = %d (supported: 1 .. 65535)", me, a->n_sig);
     if (a->T_ld < 1 || a->T_ld > (1 << 20)) return fail(h, DTTS_E_INVAL, "%s: T_ld = %d frames (supported: 1 .. %d)", me, a->T_ld, 1 << 20);
     if (a->n_win < 1 || a->n_win > DTTS_MELDISC_MAX_WIN) return fail(h, DTTS_E_INVAL, "%s: n_win = %d (disc_win_num is 1 .. 3)", me, a->n_win);
@@ -416,17 +416,13 @@ int meldisc_forward(dtts_ctx* h, const dtts_meldisc_args* a, hipStream_t stream)
     if (a->reserved[0] != 0 || a->reserved[1] != 0) return fail(h, DTTS_E_INVAL, "%s: reserved = %d, %d (must be 0)", me, a->reserved[0], a->reserved[1]);
     if (!a->mel_dev || !a->sums_dev || !a->counts_dev || !a->status_dev)
         return fail(h, DTTS_E_INVAL, "%s: null mel_dev / sums_dev / counts_dev / status_dev", me);
-    const std::pair<const char*, const void*> p4[] = {{"mel_dev", a->mel_dev}, {"lens_dev", a->lens_dev}, {"starts_dev", a->starts_dev}, {"d_dev", a->d_dev},
-                                                      {"status_dev", a->status_dev}, {"h_dev[0]", a->h_dev[0]}, {"h_dev[1]", a->h_dev[1]}, {"h_dev[2]", a->h_dev[2]},
-                                                      {"h_dev[3]", a->h_dev[3]}, {"h_dev[4]", a->h_dev[4]}, {"h_dev[5]", a->h_dev[5]}, {"h_dev[6]", a->h_dev[6]},
-                                                      {"h_dev[7]", a->h_dev[7]}, {"h_dev[8]", a->h_dev[8]}};
-    for (const auto& q : p4)
-        if ((uintptr_t)q.second & 3) return fail(h, DTTS_E_INVAL, "%s: %s = %p is not aligned to 4 bytes", me, q.first, q.second);
-    const std::pair<const char*, const void*> p8[] = {{"sums_dev", a->sums_dev}, {"counts_dev", a->counts_dev}};
-    for (const auto& q : p8)
-        if ((uintptr_t)q.second & 7) return fail(h, DTTS_E_INVAL, "%s: %s = %p is not aligned to 8 bytes", me, q.first, q.second);
-    if (!h) return fail(nullptr, DTTS_E_INVAL, "%s: null handle", me);
-    if (!h->meldisc_ready) return fail(h, DTTS_E_STATE, "%s before dtts_finalize_weights(DTTS_PART_MELDISC)", me);
+    if (int rc = blk.aligned(4, {{"mel_dev", a->mel_dev}, {"lens_dev", a->lens_dev}, {"starts_dev", a->starts_dev}, {"d_dev", a->d_dev}, {"status_dev", a->status_dev},
+                                 {"h_dev[0]", a->h_dev[0]}, {"h_dev[1]", a->h_dev[1]}, {"h_dev[2]", a->h_dev[2]}, {"h_dev[3]", a->h_dev[3]}, {"h_dev[4]", a->h_dev[4]},
+                                 {"h_dev[5]", a->h_dev[5]}, {"h_dev[6]", a->h_dev[6]}, {"h_dev[7]", a->h_dev[7]}, {"h_dev[8]", a->h_dev[8]}}))
+        return rc;
+    if (int rc = blk.aligned(8, {{"sums_dev", a->sums_dev}, {"counts_dev", a->counts_dev}})) return rc;
+    if (int rc = blk.handle()) return rc;
+    if (int rc = blk.finalized(DTTS_PART_MELDISC)) return rc;
     if (a->n_win != h->meldisc_nwin) return fail(h, DTTS_E_INVAL, "%s: n_win = %d, the loaded discriminator has %d windows", me, a->n_win, h->meldisc_nwin);
     if ((a->reduction == DTTS_MELDISC_NONE) != h->meldisc_per_row)
         return fail(h, DTTS_E_INVAL, "%s: reduction = %d, the loaded adv_layer is %s", me, a->reduction,
@@ -439,8 +435,7 @@ int meldisc_forward(dtts_ctx* h, const dtts_meldisc_args* a, hipStream_t stream)
     const size_t a1 = (size_t)(wmax / 2) * 40 * H, a2 = (size_t)(wmax / 4) * 20 * H, a3 = (size_t)(wmax / 8) * 10 * H;
     const size_t per_clip = (a1 + a2 + a3 + 4 * (size_t)H + DTTS_MELDISC_D_LD) * sizeof(float);
     const size_t tab = (tot * DTTS_MELDISC_MAX_WIN + n_sig) * sizeof(int) + 2 * 256;
-    int Sc = n_sig;
-    while (Sc > 1 && per_clip * cl * Sc > (size_t)DTTS_MELDISC_WS_BYTES) Sc = (Sc + 1) / 2;
+    const int Sc = chunk_within(n_sig, DTTS_MELDISC_WS_BYTES, [&](int n) { return per_clip * cl * n; });
     HIPCHK(h->a_meldisc.reserve(per_clip * cl * Sc + tab + 16 * 256, stream));
     Arena& ws = h->a_meldisc;
     int* vlen = ws.alloc<int>((size_t)n_sig);
@@ -451,7 +446,7 @@ int meldisc_forward(dtts_ctx* h, const dtts_meldisc_args* a, hipStream_t stream)
     float* act3 = ws.alloc<float>(a3 * nc);
     float2* nrm[2] = {ws.alloc<float2>((size_t)H * nc), ws.alloc<float2>((size_t)H * nc)};
     float* dws = ws.alloc<float>((size_t)DTTS_MELDISC_D_LD * nc);
-    if (!vlen || !cst || !act1 || !act2 || !act3 || !nrm[0] || !nrm[1] || !dws) return fail(h, DTTS_E_NOMEM, "%s: workspace", me);
+    if (!vlen || !cst || !act1 || !act2 || !act3 || !nrm[0] || !nrm[1] || !dws) return blk.workspace();
 
     MelHops hops{};
     for (int w = 0; w < DTTS_MELDISC_MAX_WIN; ++w) hops.hop[w] = a->hop[w];

@@ -238,9 +238,9 @@ int build_melspec(dtts_ctx* h) {
 // ---- dtts_text2mel_fetch(DTTS_OUT_MELSPEC): one launch on the caller's stream, no host synchronisation
 int melspec_forward(dtts_ctx* h, const dtts_melspec_args* a, hipStream_t stream) {
     const char* me = "dtts_text2mel_fetch(DTTS_OUT_MELSPEC)";
-    if (a->size != (int32_t)sizeof(dtts_melspec_args))
-        return fail(h, DTTS_E_INVAL, "%s: argument block of size = %d bytes, this library's is %d", me, a->size, (int)sizeof(dtts_melspec_args));
-    if (!h->melspec_ready) return fail(h, DTTS_E_STATE, "%s before dtts_finalize_weights(DTTS_PART_MELSPEC)", me);
+    const Block blk{h, me};
+    if (int rc = blk.size(a->size, sizeof *a)) return rc;
+    if (int rc = blk.finalized(DTTS_PART_MELSPEC)) return rc;
     std::string why;
     if (!melspec_supported(h->ms.n_fft, a->hop, h->ms_win, h->ms_n_mels, &why)) return fail(h, DTTS_E_INVAL, "%s: unsupported %s", me, why.c_str());
     if (a->B <= 0) return fail(h, DTTS_E_INVAL, "%s: B = %d", me, a->B);

@@ -507,8 +507,8 @@ static std::vector<double> pitch_tables(const PitchGeometry& g) {
 // new window length uploads its tables.  h may be null: the block is checked first, so that the refusals are reachable without a device
 int pitch_forward(dtts_ctx* h, const dtts_pitch_args* a, hipStream_t stream) {
     const char* me = "dtts_text2mel_fetch(DTTS_OUT_PITCH)";
-    if (a->size != (int32_t)sizeof(dtts_pitch_args))
-        return fail(h, DTTS_E_INVAL, "%s: argument block of size = %d bytes, this library's is %d", me, a->size, (int)sizeof(dtts_pitch_args));
+    const Block blk{h, me};
+    if (int rc = blk.size(a->size, sizeof *a)) return rc;
     if (a->B <= 0 || a->B > 65535) return fail(h, DTTS_E_INVAL, "%s: B = %d (supported: 1 .. 65535)", me, a->B);
     if (a->wav_ld < 1 || a->wav_ld > PITCH_MAX_WAV) return fail(h, DTTS_E_INVAL, "%s: wav_ld = %d samples (supported: 1 .. %d)", me, a->wav_ld, PITCH_MAX_WAV);
     if (a->sample_rate < 8000 || a->sample_rate > 48000) return fail(h, DTTS_E_INVAL, "%s: sample_rate = %d (supported: 8000 .. 48000)", me, a->sample_rate);
@@ -532,14 +532,11 @@ int pitch_forward(dtts_ctx* h, const dtts_pitch_args* a, hipStream_t stream) {
     if (a->frames_ld < 1 || a->frames_ld > PITCH_MAX_FRAMES || a->frames_ld < nf_max)
         return fail(h, DTTS_E_INVAL, "%s: frames_ld = %d frames (supported: 1 .. %d; wav_ld = %d samples give %d)", me, a->frames_ld, PITCH_MAX_FRAMES, a->wav_ld, nf_max);
     if (!a->wav_dev || !a->f0_dev || !a->n_frames_dev) return fail(h, DTTS_E_INVAL, "%s: null wav_dev / f0_dev / n_frames_dev", me);
-    const std::pair<const char*, const void*> p4[] = {{"wav_dev", a->wav_dev}, {"lens_dev", a->lens_dev}, {"n_frames_dev", a->n_frames_dev},
-                                                      {"n_cand_dev", a->n_cand_dev}, {"selected_dev", a->selected_dev}};
-    for (const auto& q : p4)
-        if ((uintptr_t)q.second & 3) return fail(h, DTTS_E_INVAL, "%s: %s = %p is not aligned to 4 bytes", me, q.first, q.second);
-    const std::pair<const char*, const void*> p8[] = {{"f0_dev", a->f0_dev}, {"acf_dev", a->acf_dev}, {"cand_dev", a->cand_dev}, {"intensity_dev", a->intensity_dev}};
-    for (const auto& q : p8)
-        if ((uintptr_t)q.second & 7) return fail(h, DTTS_E_INVAL, "%s: %s = %p is not aligned to 8 bytes", me, q.first, q.second);
-    if (!h) return fail(nullptr, DTTS_E_INVAL, "%s: null handle", me);
+    if (int rc = blk.aligned(4, {{"wav_dev", a->wav_dev}, {"lens_dev", a->lens_dev}, {"n_frames_dev", a->n_frames_dev}, {"n_cand_dev", a->n_cand_dev},
+                                 {"selected_dev", a->selected_dev}}))
+        return rc;
+    if (int rc = blk.aligned(8, {{"f0_dev", a->f0_dev}, {"acf_dev", a->acf_dev}, {"cand_dev", a->cand_dev}, {"intensity_dev", a->intensity_dev}})) return rc;
+    if (int rc = blk.handle()) return rc;
 
     auto it = h->pitch_tabs.find(g.nsw);
     if (it == h->pitch_tabs.end()) {
@@ -579,7 +576,7 @@ int pitch_forward(dtts_ctx* h, const dtts_pitch_args* a, hipStream_t stream) {
     p.n_cand = a->n_cand_dev ? a->n_cand_dev : h->a_pitch.alloc<int>(n_nc);
     p.intensity = a->intensity_dev ? a->intensity_dev : h->a_pitch.alloc<double>(n_in);
     p.psi = h->a_pitch.alloc<unsigned char>(frames * PITCH_PSI);
-    if (!p.gpeak || !p.acf || !p.cand || !p.n_cand || !p.intensity || !p.psi) return fail(h, DTTS_E_NOMEM, "%s: workspace", me);
+    if (!p.gpeak || !p.acf || !p.cand || !p.n_cand || !p.intensity || !p.psi) return blk.workspace();
     LAUNCH(pitch_stats_launch(p, stream));
     LAUNCH(pitch_acf_launch(p, stream));
     LAUNCH(pitch_candidates_launch(p, stream));

@@ -135,8 +135,8 @@ int build_resample(dtts_ctx* h) {
 // checked first, so that the refusals are reachable without a device
 int resample_forward(dtts_ctx* h, const dtts_resample_args* a, hipStream_t stream) {
     const char* me = "dtts_text2mel_fetch(DTTS_OUT_RESAMPLE)";
-    if (a->size != (int32_t)sizeof(dtts_resample_args))
-        return fail(h, DTTS_E_INVAL, "%s: argument block of size = %d bytes, this library's is %d", me, a->size, (int)sizeof(dtts_resample_args));
+    const Block blk{h, me};
+    if (int rc = blk.size(a->size, sizeof *a)) return rc;
     if (a->B <= 0 || a->B > 65535) return fail(h, DTTS_E_INVAL, "%s: B = %d (supported: 1 .. 65535)", me, a->B);
     if (a->wav_ld < 1 || a->wav_ld > RESAMPLE_MAX_WAV) return fail(h, DTTS_E_INVAL, "%s: wav_ld = %d samples (supported: 1 .. %d)", me, a->wav_ld, RESAMPLE_MAX_WAV);
     if (a->out_ld < 1) return fail(h, DTTS_E_INVAL, "%s: out_ld = %d samples (must be >= 1)", me, a->out_ld);
@@ -144,11 +144,9 @@ int resample_forward(dtts_ctx* h, const dtts_resample_args* a, hipStream_t strea
     if (a->sr_out < 8000 || a->sr_out > 48000) return fail(h, DTTS_E_INVAL, "%s: sr_out = %d (supported: 8000 .. 48000)", me, a->sr_out);
     if (a->sr_in == a->sr_out) return fail(h, DTTS_E_INVAL, "%s: sr_out = sr_in = %d: nothing to resample", me, a->sr_in);
     if (!a->wav_dev || !a->out_dev || !a->out_lens_dev) return fail(h, DTTS_E_INVAL, "%s: null wav_dev / out_dev / out_lens_dev", me);
-    const std::pair<const char*, const void*> p4[] = {{"wav_dev", a->wav_dev}, {"lens_dev", a->lens_dev}, {"out_dev", a->out_dev}, {"out_lens_dev", a->out_lens_dev}};
-    for (const auto& q : p4)
-        if ((uintptr_t)q.second & 3) return fail(h, DTTS_E_INVAL, "%s: %s = %p is not aligned to 4 bytes", me, q.first, q.second);
-    if ((uintptr_t)a->out64_dev & 7) return fail(h, DTTS_E_INVAL, "%s: out64_dev = %p is not aligned to 8 bytes", me, (const void*)a->out64_dev);
-    if (!h) return fail(nullptr, DTTS_E_INVAL, "%s: null handle", me);
+    if (int rc = blk.aligned(4, {{"wav_dev", a->wav_dev}, {"lens_dev", a->lens_dev}, {"out_dev", a->out_dev}, {"out_lens_dev", a->out_lens_dev}})) return rc;
+    if (int rc = blk.aligned(8, {{"out64_dev", a->out64_dev}})) return rc;
+    if (int rc = blk.handle()) return rc;
     if (!h->resample_ready) return fail(h, DTTS_E_NOENT, "%s: no filter: load resample.filter and resample.num_table, then dtts_finalize_weights(DTTS_PART_RESAMPLE)", me);
 
     ResampleParams p{};

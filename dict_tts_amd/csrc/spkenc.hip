@@ -381,8 +381,8 @@ size_t spk_bytes(const SpkShape& s, int Bc, bool from_wav) {
 // h may be null: the block is checked first, so that the refusals are reachable without a device
 int spkenc_forward(dtts_ctx* h, const dtts_spkenc_args* a, hipStream_t stream) {
     const char* me = "dtts_text2mel_fetch(DTTS_OUT_SPKENC)";
-    if (a->size != (int32_t)sizeof(dtts_spkenc_args))
-        return fail(h, DTTS_E_INVAL, "%s: argument block of size = %d bytes, this library's is %d", me, a->size, (int)sizeof(dtts_spkenc_args));
+    const Block blk{h, me};
+    if (int rc = blk.size(a->size, sizeof *a)) return rc;
     if (a->mode != DTTS_SPKENC_FROM_WAV && a->mode != DTTS_SPKENC_FROM_MELS)
         return fail(h, DTTS_E_INVAL, "%s: mode = %d (DTTS_SPKENC_FROM_WAV = 0 or DTTS_SPKENC_FROM_MELS = 1)", me, a->mode);
     const bool from_wav = a->mode == DTTS_SPKENC_FROM_WAV;
@@ -399,21 +399,20 @@ int spkenc_forward(dtts_ctx* h, const dtts_spkenc_args* a, hipStream_t stream) {
     if (a->reserved != 0) return fail(h, DTTS_E_INVAL, "%s: reserved = %d (must be 0)", me, a->reserved);
     if (!a->wav_dev || !a->embed_dev || !a->n_partials_dev) return fail(h, DTTS_E_INVAL, "%s: null wav_dev / embed_dev / n_partials_dev", me);
     if (!from_wav && (a->lens_dev || a->mel_dev)) return fail(h, DTTS_E_INVAL, "%s: lens_dev / mel_dev with DTTS_SPKENC_FROM_MELS (wav_dev holds the mels)", me);
-    const std::pair<const char*, const void*> p4[] = {{"wav_dev", a->wav_dev},   {"lens_dev", a->lens_dev},       {"embed_dev", a->embed_dev},
-                                                      {"n_partials_dev", a->n_partials_dev}, {"partials_dev", a->partials_dev}, {"mel_dev", a->mel_dev},
-                                                      {"hseq_dev[0]", a->hseq_dev[0]},       {"hseq_dev[1]", a->hseq_dev[1]},   {"hseq_dev[2]", a->hseq_dev[2]}};
-    for (const auto& q : p4)
-        if ((uintptr_t)q.second & 3) return fail(h, DTTS_E_INVAL, "%s: %s = %p is not aligned to 4 bytes", me, q.first, q.second);
+    if (int rc = blk.aligned(4, {{"wav_dev", a->wav_dev}, {"lens_dev", a->lens_dev}, {"embed_dev", a->embed_dev}, {"n_partials_dev", a->n_partials_dev},
+                                 {"partials_dev", a->partials_dev}, {"mel_dev", a->mel_dev}, {"hseq_dev[0]", a->hseq_dev[0]}, {"hseq_dev[1]", a->hseq_dev[1]},
+                                 {"hseq_dev[2]", a->hseq_dev[2]}}))
+        return rc;
     if (!from_wav && ((uintptr_t)a->wav_dev & 15)) return fail(h, DTTS_E_INVAL, "%s: wav_dev = %p (the mels) is not aligned to 16 bytes", me, (const void*)a->wav_dev);
-    if (!h) return fail(nullptr, DTTS_E_INVAL, "%s: null handle", me);
-    if (!h->spkenc_ready) return fail(h, DTTS_E_STATE, "%s before dtts_finalize_weights(DTTS_PART_SPKENC)", me);
+    if (int rc = blk.handle()) return rc;
+    if (int rc = blk.finalized(DTTS_PART_SPKENC)) return rc;
 
     SpkShape s;
     s.T = from_wav ? SPK_PART : a->wav_ld;
     s.P_max = from_wav ? spkenc_max_partials(a->wav_ld, a->frame_step) : 1;
     s.F_ld = from_wav ? spkenc_frames_ld(a->wav_ld, a->frame_step) : s.T;
-    int Bc = std::min(a->B, 65535 / s.P_max);   // (at most 1 361 partials per utterance at 2^24 samples; conv1d takes 65535 sequences)
-    while (Bc > 1 && spk_bytes(s, Bc, from_wav) > (size_t)DTTS_SPKENC_WS_BYTES) Bc = (Bc + 1) / 2;
+    // (at most 1 361 partials per utterance at 2^24 samples; conv1d takes 65535 sequences)
+    const int Bc = chunk_within(std::min(a->B, 65535 / s.P_max), DTTS_SPKENC_WS_BYTES, [&](int n) { return spk_bytes(s, n, from_wav); });
     HIPCHK(h->a_spkenc.reserve(spk_bytes(s, Bc, from_wav), stream));
 
     for (int b0 = 0; b0 < a->B; b0 += Bc) {
@@ -427,7 +426,7 @@ int spkenc_forward(dtts_ctx* h, const dtts_spkenc_args* a, hipStream_t stream) {
         float* xproj = ws.alloc<float>(std::max((size_t)B * s.F_ld, (size_t)N * s.T) * SPK_G);
         float* hs[2] = {ws.alloc<float>((size_t)N * s.T * SPK_H), ws.alloc<float>((size_t)N * s.T * SPK_H)};
         float* part = ws.alloc<float>((size_t)N * SPK_H);
-        if (!tabs || (from_wav && !mel) || !xproj || !hs[0] || !hs[1] || !part) return fail(h, DTTS_E_NOMEM, "%s: workspace", me);
+        if (!tabs || (from_wav && !mel) || !xproj || !hs[0] || !hs[1] || !part) return blk.workspace();
 
         SpkPlanParams pp{};
         pp.lens = a->lens_dev ? a->lens_dev + b0 : nullptr;

@@ -206,9 +206,9 @@ int build_stft(dtts_ctx* h) {
 // ---- dtts_text2mel_fetch(DTTS_OUT_STFT_DISTANCE): one launch per resolution + the reduction, on the caller's stream, no host synchronisation
 int stft_forward(dtts_ctx* h, const dtts_stft_args* a, hipStream_t stream) {
     const char* me = "dtts_text2mel_fetch(DTTS_OUT_STFT_DISTANCE)";
-    if (a->size != (int32_t)sizeof(dtts_stft_args))
-        return fail(h, DTTS_E_INVAL, "%s: argument block of size = %d bytes, this library's is %d", me, a->size, (int)sizeof(dtts_stft_args));
-    if (h->stft_plans.empty()) return fail(h, DTTS_E_STATE, "%s before dtts_finalize_weights(DTTS_PART_STFT)", me);
+    const Block blk{h, me};
+    if (int rc = blk.size(a->size, sizeof *a)) return rc;
+    if (int rc = blk.finalized(DTTS_PART_STFT)) return rc;
     if (a->n_res < 1 || a->n_res > (int)h->stft_plans.size())
         return fail(h, DTTS_E_INVAL, "%s: n_res = %d (this context has %d plans)", me, a->n_res, (int)h->stft_plans.size());
     if (a->B <= 0) return fail(h, DTTS_E_INVAL, "%s: B = %d", me, a->B);
@@ -259,7 +259,7 @@ int stft_forward(dtts_ctx* h, const dtts_stft_args* a, hipStream_t stream) {
     HIPCHK(h->a_stft.reserve(ws, stream));
     for (int i = 0; i < a->n_res; ++i) {
         sp[i].part = h->a_stft.alloc<double>((size_t)a->B * sp[i].g.ntile * 3);
-        if (!sp[i].part) return fail(h, DTTS_E_NOMEM, "%s: workspace", me);
+        if (!sp[i].part) return blk.workspace();
         rp.part[i] = sp[i].part;
     }
     for (int i = 0; i < a->n_res; ++i) LAUNCH(stft_launch(sp[i], stream));

@@ -766,19 +766,9 @@ int dtts_text2mel_forward_ids(dtts_handle h, const int64_t* word_tokens, const i
 }
 
 int dtts_text2mel_fetch(dtts_handle h, int what, void* dst, dtts_stream stream) {
-    if (what == DTTS_OUT_DTW && dst) return dtw_forward(h, (const dtts_dtw_args*)dst, (hipStream_t)stream);   // checks its block before the handle
-    if (what == DTTS_OUT_PITCH && dst) return pitch_forward(h, (const dtts_pitch_args*)dst, (hipStream_t)stream);   // the same
-    if (what == DTTS_OUT_RESAMPLE && dst) return resample_forward(h, (const dtts_resample_args*)dst, (hipStream_t)stream);   // the same
-    if (what == DTTS_OUT_LOUDNESS && dst) return loudness_forward(h, (const dtts_loudness_args*)dst, (hipStream_t)stream);   // the same
-    if (what == DTTS_OUT_DISC && dst) return disc_forward(h, (const dtts_disc_args*)dst, (hipStream_t)stream);   // the same
-    if (what == DTTS_OUT_SPKENC && dst) return spkenc_forward(h, (const dtts_spkenc_args*)dst, (hipStream_t)stream);   // the same
-    if (what == DTTS_OUT_MELDISC && dst) return meldisc_forward(h, (const dtts_meldisc_args*)dst, (hipStream_t)stream);   // the same
+    // the block items (none needs an encode); a unit that checks its block before the handle is reached with a null one too
+    if (const Unit* u = find_item(what); u && dst && (h || u->null_handle)) return u->forward(h, dst, (hipStream_t)stream);
     if (!h || !dst) return DTTS_E_INVAL;
-    if (what == DTTS_OUT_MELSPEC) return melspec_forward(h, (const dtts_melspec_args*)dst, (hipStream_t)stream);   // needs no encode
-    if (what == DTTS_OUT_STFT_DISTANCE) return stft_forward(h, (const dtts_stft_args*)dst, (hipStream_t)stream);   // nor does this
-    if (what == DTTS_OUT_SPECTRAL) return spectral_forward(h, (const dtts_spectral_args*)dst, (hipStream_t)stream);      // nor this
-    if (what == DTTS_OUT_GRIFFIN_LIM) return griffin_lim(h, (const dtts_griffinlim_args*)dst, (hipStream_t)stream);      // nor this
-    if (what == DTTS_OUT_LOSSES) return losses_forward(h, (const dtts_loss_args*)dst, (hipStream_t)stream);                // nor this
     if (!h->encoded) return fail(h, DTTS_E_STATE, "dtts_text2mel_fetch before encode");
     if (what == DTTS_OUT_POSTERIOR) {   // the posterior pass; dst is the host argument block
         const dtts_posterior_args* a = (const dtts_posterior_args*)dst;

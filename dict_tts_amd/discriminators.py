@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import abi
+from .unit import DeviceUnit
 
 MPD_CONVS, MSD_CONVS = 5, 7
 
@@ -115,17 +116,17 @@ def figures(sums, counts, fm=None, fm_counts=None):
     return out
 
 
-class Discriminators:
+class Discriminators(DeviceUnit):
     """``Discriminators(weights)``: plain folded weights (``fold_state_dict``'s names) -> ``scores(y, y_hat, lens)``.
 
     ctx: an existing ``abi.Context`` (e.g. the vocoder's), or None for one of its own; it is created on the first call, so that argument
     errors surface without a GPU."""
 
+    PREFIX, PART = "disc", abi.PART_DISC
+
     def __init__(self, weights, ctx=None):
         self.weights = {k: np.ascontiguousarray(np.asarray(v, np.float32)) for k, v in weights.items()}
         self.ctx = ctx
-        self.device = None
-        self._loaded = False
 
     @classmethod
     def from_checkpoint(cls, path_or_state, hparams=None, ctx=None):
@@ -134,19 +135,6 @@ class Discriminators:
         refuse use_cond_disc / use_spec_disc by name (a ``cond_net`` or ``specd`` key in the checkpoint is refused too)."""
         check_hparams(hparams)
         return cls(fold_state_dict(model_disc_of(path_or_state)), ctx=ctx)
-
-    def _context(self):
-        if self.device is None:
-            if not torch.cuda.is_available():
-                raise abi.DttsError("dict_tts_amd.discriminators.Discriminators needs a ROCm GPU: the HIP path has no CPU fallback")
-            self.device = torch.device("cuda", torch.cuda.current_device())
-            if self.ctx is None:
-                self.ctx = abi.Context()
-        if not self._loaded:
-            self.ctx.load_state_dict("disc", self.weights)
-            self.ctx.finalize(abi.PART_DISC)
-            self._loaded = True
-        return self.ctx
 
     def scores(self, y, y_hat, lens=None, feature_matching=False, which=("mpd", "msd"), return_d=False):
         """y (recordings), y_hat (generated) [B, T] float32, lens [B] valid samples of both or None (= T) -> dict of float64 device tensors:

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import abi
+from .unit import DeviceUnit
 
 GT_SUFFIX = "_gt.npy"
 
@@ -39,7 +40,7 @@ def _lens(name, lens, B, ld):
     return lens
 
 
-class DTW:
+class DTW(DeviceUnit):
     """``DTW(ctx)(x, y, ...)``: a batch of pairs -> distance, path, accumulated cost, moments, as tensors on the device.
 
     ctx: an existing ``abi.Context`` (e.g. the model's), or None for one of its own; it is created on the first call, so that argument
@@ -47,16 +48,6 @@ class DTW:
 
     def __init__(self, ctx=None):
         self.ctx = ctx
-        self.device = None
-
-    def _context(self):
-        if self.device is None:
-            if not torch.cuda.is_available():
-                raise abi.DttsError("dict_tts_amd.dtw.DTW needs a ROCm GPU: the HIP path has no CPU fallback")
-            self.device = torch.device("cuda", torch.cuda.current_device())
-            if self.ctx is None:
-                self.ctx = abi.Context()
-        return self.ctx
 
     def __call__(self, x, y, x_lens=None, y_lens=None, window=None, slope=1.0, path=True, acc=False, moments=False):
         """x [B, N] or [B, N, F], y [B, M] or [B, M, F] (float32, or float64 when either is), x_lens / y_lens [B] or None (= N / M),

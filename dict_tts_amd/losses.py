@@ -20,6 +20,7 @@ import torch
 
 from . import abi
 from . import hparams as hparams_mod
+from .unit import DeviceUnit
 
 SSIM_WINDOW, SSIM_SIGMA, SSIM_BIAS = 11, 1.5, 6.0
 KL_FLOOR = 0.002   # tasks/tts/dict_tts.py:74
@@ -61,7 +62,7 @@ def _ratio(num, den):
     return num / den   # 0 / 0 = NaN, as the reference's masked means give it
 
 
-class ValidationLosses:
+class ValidationLosses(DeviceUnit):
     """mel(), dur(), run_model(), validation_step(): the reference's eval-mode loss figures, as float64 cuda tensors.
 
     hparams: the reference's keys mel_loss, lambda_kl, lambda_sent_dur, dur_scale, dur_level (None: the global hparams when set, else
@@ -86,17 +87,7 @@ class ValidationLosses:
         if self.lambda_sent_dur > 0 and self.dur_scale != "linear":
             raise ValueError("lambda_sent_dur > 0 needs dur_scale = 'linear' (the reference asserts it, tasks/tts/ps_flow.py:111)")
         self.ctx = ctx
-        self.device = None
         self.mel_disc = mel_disc
-
-    def _context(self):
-        if self.device is None:
-            if not torch.cuda.is_available():
-                raise abi.DttsError("dict_tts_amd.losses.ValidationLosses needs a ROCm GPU: the HIP path has no CPU fallback")
-            self.device = torch.device("cuda", torch.cuda.current_device())
-            if self.ctx is None:
-                self.ctx = abi.Context()
-        return self.ctx
 
     # -- the two halves ------------------------------------------------------------------------------------
     def mel(self, mel_out, target, bias=SSIM_BIAS, ssim_map=False):

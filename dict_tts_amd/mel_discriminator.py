@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import abi
+from .unit import DeviceUnit
 from .discriminators import fold_spectral_norm
 
 WINS = abi.MELDISC_WINS
@@ -177,11 +178,13 @@ def figures(sums, counts, n_win):
     return out
 
 
-class MelDiscriminator:
+class MelDiscriminator(DeviceUnit):
     """``MelDiscriminator(weights, reduction)``: plain folded weights (``fold_state_dict``'s names) -> ``forward`` / ``scores``.
 
     ctx: an existing ``abi.Context`` (e.g. the model's), or None for one of its own; it is created on the first call, so that argument
     errors surface without a GPU."""
+
+    PREFIX, PART = "meldisc", abi.PART_MELDISC
 
     def __init__(self, weights, reduction=None, hparams=None, ctx=None):
         hp = dict(hparams or {})
@@ -190,8 +193,6 @@ class MelDiscriminator:
         self.win_num, self.hidden, self.norm, self.reduction = check_hparams(hp, weights)
         self.weights = {k: np.ascontiguousarray(np.asarray(v, np.float32)) for k, v in weights.items()}
         self.ctx = ctx
-        self.device = None
-        self._loaded = False
 
     @classmethod
     def from_checkpoint(cls, path_or_state, hparams=None, ctx=None):
@@ -204,19 +205,6 @@ class MelDiscriminator:
                 from .vocoder import load_config_chain
                 hparams = {k: v for k, v in load_config_chain(cfg).items() if k in HP_DEFAULTS}
         return cls(fold_state_dict(mel_disc_of(path_or_state)), hparams=hparams, ctx=ctx)
-
-    def _context(self):
-        if self.device is None:
-            if not torch.cuda.is_available():
-                raise abi.DttsError("dict_tts_amd.mel_discriminator.MelDiscriminator needs a ROCm GPU: the HIP path has no CPU fallback")
-            self.device = torch.device("cuda", torch.cuda.current_device())
-            if self.ctx is None:
-                self.ctx = abi.Context()
-        if not self._loaded:
-            self.ctx.load_state_dict("meldisc", self.weights)
-            self.ctx.finalize(abi.PART_MELDISC)
-            self._loaded = True
-        return self.ctx
 
     def _check_mel(self, x, what):
         x = torch.as_tensor(x)

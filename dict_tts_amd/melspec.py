@@ -9,6 +9,7 @@ import torch
 
 from . import abi
 from .hparams import BIAOBEI_DEFAULTS
+from .unit import DeviceUnit
 
 EPS = 1e-6   # process_utterance(eps=1e-6)
 
@@ -72,25 +73,27 @@ def read_wav(path, sample_rate):
     return wav.mean(axis=1).astype(np.float32) if wav.ndim == 2 else wav   # librosa.load(mono=True)
 
 
-class MelSpectrogram:
+class MelSpectrogram(DeviceUnit):
     """wav [B, L] -> (log10-mel [B, T, n_mels], frames [B]) with T = 1 + L // hop, one launch per batch, nothing leaves the device.
 
     hparams keys (the reference's, egs/egs_bases/tts/base.yaml:48-54): fft_size, hop_size, win_size, audio_num_mel_bins, fmin, fmax,
     audio_sample_rate.  ctx: an existing ``abi.Context`` to load the plan into (e.g. the vocoder's), or None for one of its own."""
+
+    PREFIX, PART = "melspec", abi.PART_MELSPEC
 
     def __init__(self, hparams=None, ctx=None):
         hp = {**BIAOBEI_DEFAULTS, **(hparams or {})}
         self.n_fft, self.hop, self.win = int(hp["fft_size"]), int(hp["hop_size"]), int(hp["win_size"] or hp["fft_size"])
         self.n_mels, self.sample_rate = int(hp["audio_num_mel_bins"]), int(hp["audio_sample_rate"])
         self.fmin, self.fmax = hp["fmin"], hp["fmax"]
-        if not torch.cuda.is_available():
-            raise abi.DttsError("dict_tts_amd.melspec.MelSpectrogram needs a ROCm GPU: the HIP path has no CPU fallback")
-        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.ctx = ctx
+        self._device()   # (refuses before anything is computed; this unit loads its plan at construction)
         self.mel_basis = mel_filterbank(self.sample_rate, self.n_fft, self.n_mels, self.fmin, self.fmax).astype(np.float32)   # (librosa's dtype)
         self.window = hann_window(self.win).astype(np.float32)
-        self.ctx = ctx if ctx is not None else abi.Context()
-        self.ctx.load_state_dict("melspec", {"mel_basis": self.mel_basis, "window": self.window})
-        self.ctx.finalize(abi.PART_MELSPEC)
+        self._context()
+
+    def _state(self):
+        return {"mel_basis": self.mel_basis, "window": self.window}
 
     def frames(self, n_samples):
         return 1 + int(n_samples) // self.hop

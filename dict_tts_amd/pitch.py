@@ -14,6 +14,7 @@ import torch
 
 from . import abi
 from . import dtw as _dtw
+from .unit import DeviceUnit
 
 PRAAT_DEFAULTS = dict(silence_threshold=0.03, octave_cost=0.01, octave_jump_cost=0.35, voiced_unvoiced_cost=0.14)
 REFERENCE_LPAD = {256: 4, 128: 8}   # get_pitch: pad_size * 2, pad_size = 2 (hop 256) / 4 (hop 128); any other hop trips its assert
@@ -54,7 +55,7 @@ def n_frames_of(L, first, hop):
     return (int(L) - first) // hop + 1 if L >= first else 0
 
 
-class PitchAC:
+class PitchAC(DeviceUnit):
     """``PitchAC(...)(wavs, lens)``: a batch of waveforms -> F0 tracks, as tensors on the device.
 
     ctx: an existing ``abi.Context`` (e.g. the vocoder's), or None for one of its own; it is created on the first call, so that argument
@@ -63,7 +64,6 @@ class PitchAC:
     def __init__(self, ctx=None, sample_rate=22050, hop_size=256, f0_min=80.0, f0_max=750.0, voicing_threshold=0.6, silence_threshold=0.03,
                  octave_cost=0.01, octave_jump_cost=0.35, voiced_unvoiced_cost=0.14):
         self.ctx = ctx
-        self.device = None
         self.sample_rate, self.hop = int(sample_rate), int(hop_size)
         if self.sample_rate != sample_rate or not 8000 <= self.sample_rate <= 48000:
             raise ValueError(f"sample_rate = {sample_rate!r} (supported: an integer in 8000 .. 48000)")
@@ -97,15 +97,6 @@ class PitchAC:
         if ext != "parselmouth":
             raise ValueError(f"pitch_extractor = {ext!r} (the reference knows parselmouth, harvest and dio)")
         return cls(ctx, sample_rate=hp["audio_sample_rate"], hop_size=hp["hop_size"], **kw)
-
-    def _context(self):
-        if self.device is None:
-            if not torch.cuda.is_available():
-                raise abi.DttsError("dict_tts_amd.pitch.PitchAC needs a ROCm GPU: the HIP path has no CPU fallback")
-            self.device = torch.device("cuda", torch.cuda.current_device())
-            if self.ctx is None:
-                self.ctx = abi.Context()
-        return self.ctx
 
     def frames(self, L):
         return n_frames_of(L, self.geo["first"], self.hop)

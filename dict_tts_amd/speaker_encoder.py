@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import abi, melspec
+from .unit import DeviceUnit
 
 SAMPLING_RATE = 16000
 MEL_WINDOW_LENGTH, MEL_WINDOW_STEP, MEL_N_CHANNELS = 25, 10, 40
@@ -114,21 +115,21 @@ def similarity(a, b):
     return (a * b).sum(-1) / (a.norm(dim=-1) * b.norm(dim=-1))
 
 
-class VoiceEncoder:
+class VoiceEncoder(DeviceUnit):
     """``VoiceEncoder.from_checkpoint("pretrained.pt").embed_utterance(wav)``: Resemblyzer's interface on the device.
 
     ctx: an existing ``abi.Context`` or None for one of its own; it is created, and the weights loaded, on the first device call, so that
     argument errors surface without a GPU.  pad_mode: how the mel's centred frames see beyond the waveform's ends — 'constant' (zeros;
     librosa 0.9.2, the version the reference pins) or 'reflect' (librosa <= 0.8)."""
 
+    PREFIX, PART = "spkenc", abi.PART_SPKENC
+
     def __init__(self, ctx=None, pad_mode="constant"):
         if pad_mode not in PAD_MODES:
             raise ValueError(f"pad_mode = {pad_mode!r} (known: 'constant', 'reflect')")
         self.ctx = ctx
         self.pad_mode = pad_mode
-        self.device = None
         self.weights = None
-        self._loaded = False
 
     # ---- weights
     def load_state_dict(self, state):
@@ -142,23 +143,13 @@ class VoiceEncoder:
         """Resemblyzer's ``pretrained.pt`` (path or loaded: ``{"model_state": state_dict, ...}``) or the state dict itself"""
         return cls(ctx=ctx, pad_mode=pad_mode).load_state_dict(path_or_state)
 
-    def _context(self):
+    def _state(self):
         if self.weights is None:
             raise abi.DttsError("VoiceEncoder: no weights (load_state_dict / from_checkpoint first)")
-        if self.device is None:
-            if not torch.cuda.is_available():
-                raise abi.DttsError("dict_tts_amd.speaker_encoder.VoiceEncoder needs a ROCm GPU: the HIP path has no CPU fallback")
-            self.device = torch.device("cuda", torch.cuda.current_device())
-            if self.ctx is None:
-                self.ctx = abi.Context()
-        if not self._loaded:
-            w = dict(self.weights)
-            w["mel_basis"] = melspec.mel_filterbank(SAMPLING_RATE, N_FFT, MEL_N_CHANNELS, 0, SAMPLING_RATE // 2).astype(np.float32)
-            w["window"] = melspec.hann_window(N_FFT).astype(np.float32)
-            self.ctx.load_state_dict("spkenc", w)
-            self.ctx.finalize(abi.PART_SPKENC)
-            self._loaded = True
-        return self.ctx
+        w = dict(self.weights)
+        w["mel_basis"] = melspec.mel_filterbank(SAMPLING_RATE, N_FFT, MEL_N_CHANNELS, 0, SAMPLING_RATE // 2).astype(np.float32)
+        w["window"] = melspec.hann_window(N_FFT).astype(np.float32)
+        return w
 
     # ---- host arithmetic
     @staticmethod

@@ -17,6 +17,7 @@ import torch
 
 from . import abi
 from .hparams import BIAOBEI_DEFAULTS
+from .unit import DeviceUnit
 
 ENVELOPE_MIN = 1e-11   # torch.istft's criterion on the window envelope (librosa divides where it exceeds the smallest float instead)
 
@@ -59,7 +60,7 @@ def inverse_mel_basis(hp, n_fft):
     return np.ascontiguousarray(np.linalg.pinv(basis.astype(np.float64)).astype(np.float32))
 
 
-class Spectral:
+class Spectral(DeviceUnit):
     """``stft`` / ``istft`` / ``denoise`` / ``griffin_lim`` of batches of waveforms with one plan (fft_size, hop_size, win_size).
 
     hp: the reference's hparams keys fft_size, hop_size, win_size (egs/egs_bases/tts/base.yaml:48-54; Biaobei's by default), fft_size 512 /
@@ -94,10 +95,7 @@ class Spectral:
             self.inv_mel_basis = inverse_mel_basis(self._mel_hp, self.n_fft)
         if self.ctx is not None and getattr(self.ctx, "_istft_plan_of", None) is self and (self._plan_has_inv or not mel):
             return
-        if not torch.cuda.is_available():
-            raise abi.DttsError("dict_tts_amd.spectral.Spectral needs a ROCm GPU: the HIP path has no CPU fallback")
-        if self.ctx is None:
-            self.ctx = abi.Context()
+        self._device()   # (no PART: which plan the context holds is decided here, call by call)
         self.ctx._istft_plan_of = None   # (a refused finalise leaves no plan behind)
         state = {"window": self.window}
         if self.inv_mel_basis is not None:

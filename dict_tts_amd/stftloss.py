@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import abi
+from .unit import DeviceUnit
 
 FFT_SIZES, HOP_SIZES, WIN_LENGTHS = (1024, 2048, 512), (120, 240, 50), (600, 1200, 240)   # MultiResolutionSTFTLoss.__init__ defaults
 
@@ -53,13 +54,15 @@ def scores(sums, count):
             "sc_batch": sc_pool.mean(), "mag_batch": mag_pool.mean(), "sums": sums, "count": count}
 
 
-class MultiResolutionSTFT:
+class MultiResolutionSTFT(DeviceUnit):
     """(x [B, L], y [B, L]) -> the reference's multi-resolution ``sc`` / ``mag`` per utterance and pooled, one launch per resolution plus
     one reduction launch, no host synchronisation.
 
     fft_sizes / hop_sizes / win_lengths: up to four resolutions, the reference's three by default; fft sizes 512 / 1024 / 2048, any hop in
     1 .. fft_size, any win_length <= fft_size.  ctx: an existing ``abi.Context`` to load the plans into (e.g. the vocoder's), or None for
     one of its own; it is created on the first call, so that argument errors surface without a GPU."""
+
+    PREFIX, PART = "stft", abi.PART_STFT
 
     def __init__(self, fft_sizes=FFT_SIZES, hop_sizes=HOP_SIZES, win_lengths=WIN_LENGTHS, ctx=None):
         self.fft_sizes, self.hop_sizes, self.win_lengths = [int(v) for v in fft_sizes], [int(v) for v in hop_sizes], [int(v) for v in win_lengths]
@@ -74,23 +77,16 @@ class MultiResolutionSTFT:
                 raise ValueError(f"hop = {h} (supported: 1 .. fft_size = {n})")
         self.windows = [centred_window(n, w) for n, w in zip(self.fft_sizes, self.win_lengths)]
         self.ctx = ctx
-        self._ready = False
 
     @property
     def n_res(self):
         return len(self.fft_sizes)
 
+    def _state(self):
+        return {f"{i}.window": w for i, w in enumerate(self.windows)}
+
     def _plan(self):
-        if self._ready:
-            return
-        if not torch.cuda.is_available():
-            raise abi.DttsError("dict_tts_amd.stftloss.MultiResolutionSTFT needs a ROCm GPU: the HIP path has no CPU fallback")
-        self.device = torch.device("cuda", torch.cuda.current_device())
-        if self.ctx is None:
-            self.ctx = abi.Context()
-        self.ctx.load_state_dict("stft", {f"{i}.window": w for i, w in enumerate(self.windows)})
-        self.ctx.finalize(abi.PART_STFT)
-        self._ready = True
+        self._context()
 
     def mag_layout(self, B, mag_cap):
         """(offset, shape) of every resolution's block [2 (x, y), B, mag_cap, fft_size // 2 + 1] inside the flat ``mag`` buffer"""

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import abi
+from .unit import DeviceUnit
 
 KAISER_BEST = dict(num_zeros=64, precision=9, beta=14.769656459379492, rolloff=0.9475937167399596)
 KAISER_FAST = dict(num_zeros=16, precision=9, beta=8.555504641634386, rolloff=0.85)
@@ -113,22 +114,7 @@ def _batch(wavs, lens):
     return wavs, lens, B, L
 
 
-class _Unit:
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self.device = None
-
-    def _context(self):
-        if self.device is None:
-            if not torch.cuda.is_available():
-                raise abi.DttsError(f"dict_tts_amd.wavprep.{type(self).__name__} needs a ROCm GPU: the HIP path has no CPU fallback")
-            self.device = torch.device("cuda", torch.cuda.current_device())
-            if self.ctx is None:
-                self.ctx = abi.Context()
-        return self.ctx
-
-
-class Resampler(_Unit):
+class Resampler(DeviceUnit):
     """``Resampler(sr_in, sr_out)(wavs, lens)`` -> (out f32 [B, ceil(L ratio)], out_lens i32 [B]) on the device.
 
     filter: "kaiser_best" (librosa's default), "kaiser_fast", or a pair (half_window f64 [n_win], num_table).  ctx: an existing
@@ -138,7 +124,7 @@ class Resampler(_Unit):
     but should not alternate call by call."""
 
     def __init__(self, sr_in, sr_out, filter="kaiser_best", ctx=None):
-        super().__init__(ctx)
+        self.ctx = ctx
         self.sr_in, self.sr_out = _rate("sr_in", sr_in), _rate("sr_out", sr_out)
         if self.sr_in == self.sr_out:
             raise ValueError(f"sr_in = sr_out = {self.sr_in}: nothing to resample")
@@ -187,11 +173,11 @@ class Resampler(_Unit):
         return (out, out_lens, out64) if acc64 else (out, out_lens)
 
 
-class Loudness(_Unit):
+class Loudness(DeviceUnit):
     """BS.1770 integrated loudness of a batch of mono waveforms at `sample_rate`, and their normalisation.  ctx as for ``Resampler``."""
 
     def __init__(self, sample_rate, ctx=None):
-        super().__init__(ctx)
+        self.ctx = ctx
         self.sample_rate = _rate("sample_rate", sample_rate)
 
     def blocks(self, L):
