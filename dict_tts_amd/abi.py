@@ -67,6 +67,9 @@ MELDISC_WITHIN_LEN = 1   # DTTS_MELDISC_WITHIN_LEN (flags): a slot is a clip onl
 MELDISC_BAD_LEN = 1      # DTTS_MELDISC_BAD_LEN (status bit)
 MELDISC_MELS, MELDISC_MAX_WIN, MELDISC_D_LD, MELDISC_MAX_HIDDEN = 80, 3, 16, 256
 MELDISC_WINS = (32, 64, 128)
+PART_GLOSS = 1024     # the gloss encoder (RoFormer): "gloss.<HF key without 'roformer.'>" + "gloss.config"; built once per context
+GLOSS_ENCODE = 64     # DTTS_GLOSS_ENCODE: what dtts_text2mel_fetch takes for a GlossArgs block (not an OUT_ item: it is no output of the text-to-mel path)
+GLOSS_MAX_L = 64      # DTTS_GLOSS_MAX_L: tokens per gloss, [CLS] and [SEP] included
 SPECTRAL_FORWARD, SPECTRAL_INVERSE = 1, 2  # dtts_spectral_args.mode bits; both = the reference's denoise
 SPK_EMBED, SPK_ID = 1, 2   # dtts_text2mel_speakers kinds: fp32 [B,256] (use_spk_embed) / int64 [B] (use_spk_id)
 TIMER_VOC_CONV, TIMER_S2PA = 1, 2
@@ -250,6 +253,17 @@ def meldisc_args(n_sig, mel, T_ld, n_win, clips_ld, sums, counts, status, reduct
     return MeldiscArgs(C.sizeof(MeldiscArgs), int(n_sig), int(T_ld), int(n_win), int(reduction), int(flags), int(clips_ld),
                        (C.c_int32 * 3)(*[int(v) for v in hop]), (C.c_int32 * 2)(0, 0), mel or None, lens or None, starts or None, d or None, sums or None,
                        counts or None, status or None, (C.c_void_p * 9)(*[v or None for v in h]))
+
+
+class GlossArgs(C.Structure):
+    """dtts_gloss_args (include/dicttts_hip.h): the argument block of dtts_text2mel_fetch(DTTS_GLOSS_ENCODE)"""
+    _fields_ = [("size", C.c_int32), ("n_gloss", C.c_int32), ("sum_L", C.c_int32), ("L_max", C.c_int32), ("ids_dev", C.c_void_p),
+                ("tok_off_dev", C.c_void_p), ("out_dev", C.c_void_p), ("status_dev", C.c_void_p)]
+
+
+def gloss_args(n_gloss, ids, tok_off, sum_L, L_max, out, status):
+    """a filled GlossArgs block (device pointers as integers, 0 / None = NULL)"""
+    return GlossArgs(C.sizeof(GlossArgs), int(n_gloss), int(sum_L), int(L_max), ids or None, tok_off or None, out or None, status or None)
 
 
 class DttsConfig(C.Structure):
@@ -567,6 +581,13 @@ class Context:
     def fft_blocks_forward(self, x, lens, pos_table, n_pos, B, T, y, stream):
         self._chk(self.lib.dtts_fft_blocks_forward(self.h, x, lens or None, pos_table or None, int(n_pos), B, T, y, stream),
                   "dtts_fft_blocks_forward")
+
+    def gloss_encode(self, n_gloss, stream, **kw):
+        """gloss embeddings of n_gloss glosses packed as one ragged sequence (dtts_text2mel_fetch(DTTS_GLOSS_ENCODE); needs PART_GLOSS finalised).  Keywords: those
+        of ``gloss_args`` — ids i64 [sum_L], tok_off i32 [n_gloss + 1], sum_L, L_max (the longest gloss), out f32 [sum_L, hidden] and status
+        i64 [2] out.  Synchronises the stream once (the offsets are checked on the host)."""
+        a = gloss_args(n_gloss, **kw)
+        self._chk(self.lib.dtts_text2mel_fetch(self.h, GLOSS_ENCODE, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_GLOSS_ENCODE)")
 
     def timer_enable(self, which):
         self._chk(self.lib.dtts_timer_enable(self.h, which), "dtts_timer_enable")

@@ -37,6 +37,7 @@
 #include "disc.h"
 #include "spkenc.h"
 #include "meldisc.h"
+#include "gloss.h"
 
 // dtts_config.tune_flags: the bits the library honours are listed at TUNE_RELEASE_MASK (context.hip)
 #define DTTS_TUNE(h, bit) (((h)->tune & (bit)) != 0)
@@ -294,6 +295,15 @@ struct dtts_ctx {
     const float2* meldisc_ident = nullptr;                 // (0, 1) [H]
     const float* meldisc_zero = nullptr;                   // 0 [H]
     dtts::Arena a_meldisc;
+    // ---- the gloss encoder (dtts_text2mel_fetch(DTTS_GLOSS_ENCODE); gloss.hip): the packs of dtts_finalize_weights(DTTS_PART_GLOSS) and the one workspace of a
+    // call (the hidden rows, the attention block's output, the running sum, and q | k | v + ctx sharing their rows with the feed-forward's)
+    bool gloss_ready = false;
+    std::vector<dtts::GlossLayer> gloss_layers;
+    float *gloss_word = nullptr, *gloss_tt0 = nullptr, *gloss_eg = nullptr, *gloss_eb = nullptr;   // word_embeddings, token_type row 0, embeddings.LayerNorm
+    const float2* gloss_rot = nullptr;                     // (sin, cos) [64][32]
+    int gloss_vocab = 0, gloss_C = 0, gloss_F = 0;
+    float gloss_eps = 0.f;
+    dtts::Arena a_gloss;
 };
 
 namespace dtts {
@@ -438,6 +448,8 @@ int build_spkenc(dtts_ctx* h);    // spkenc.hip
 int spkenc_forward(dtts_ctx* h, const dtts_spkenc_args* a, hipStream_t stream);       // spkenc.hip (the same)
 int build_meldisc(dtts_ctx* h);   // meldisc.hip
 int meldisc_forward(dtts_ctx* h, const dtts_meldisc_args* a, hipStream_t stream);     // meldisc.hip (the same)
+int build_gloss(dtts_ctx* h);     // gloss.hip
+int gloss_forward(dtts_ctx* h, const dtts_gloss_args* a, hipStream_t stream);         // gloss.hip (the same)
 
 // ---- a row of the one table of parts and block items (UNITS, context.hip): dtts_finalize_weights walks its parts in row order,
 // dtts_text2mel_fetch finds the item's forward in it, Block::finalized the part's ready predicate.  A row may be a part without an item

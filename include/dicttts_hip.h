@@ -215,6 +215,19 @@ DTTS_API int dtts_load_weight(dtts_handle h, const char* name, const void* host_
  * not a multiple of 32 in 32 .. DTTS_MELDISC_MAX_HIDDEN, a window count outside 1 .. 3 ("meldisc.3.*" present), a layer of another shape,
  * and an adv_layer whose width does not match its window (or differs in kind between windows).  Built once per context. */
 #define DTTS_PART_MELDISC 512
+/* The gloss encoder (DTTS_GLOSS_ENCODE below; the first layers of the RoFormer whose hidden states the reference's binariser averages into
+ * the dictionary's `dict_embed`): "gloss.<key>" with <key> the Hugging Face state-dict key without its "roformer." prefix —
+ *   "gloss.embeddings.word_embeddings.weight" [vocab][hidden], "gloss.embeddings.token_type_embeddings.weight" [>= 1][hidden] (row 0 is
+ *   used), "gloss.embeddings.LayerNorm.weight" / ".bias" [hidden];
+ *   per layer l = 0 .. n - 1, "gloss.encoder.layer.<l>." + "attention.self.query" / "key" / "value" / "attention.output.dense" ".weight"
+ *   [hidden][hidden] and ".bias" [hidden], "attention.output.LayerNorm" / "output.LayerNorm" ".weight" / ".bias" [hidden],
+ *   "intermediate.dense.weight" [ffn][hidden] + ".bias" [ffn], "output.dense.weight" [hidden][ffn] + ".bias" [hidden];
+ *   "gloss.config" [4]: num_attention_heads, layer_norm_eps, rotary_value (0 / 1), hidden_act (0 = "gelu", the erf form; 1 = any other).
+ * The number of layers is what was loaded (1 .. 64); the mean runs over n + 2 terms.  "encoder.embed_positions.weight" is not read: the
+ * rotary table is made here, in fp64, rounded once.  DTTS_E_INVAL naming the value: a hidden size that is no multiple of 64, heads of
+ * another width than 64, a word-embedding width (embedding_size) other than the hidden size, rotary_value = 1, hidden_act != 0, a tensor
+ * of another shape, and a tensor that a loaded layer lacks; DTTS_E_NOENT: no config / embeddings at all.  Built once per context. */
+#define DTTS_PART_GLOSS 1024
 /* Fold, repack into MFMA fragment order and upload.  Fails with DTTS_E_NOENT naming the first missing tensor. */
 DTTS_API int dtts_finalize_weights(dtts_handle h, int parts);
 
@@ -1009,6 +1022,39 @@ DTTS_API int dtts_hifigan_hop(dtts_handle h); /* product of upsample_rates (256)
  */
 DTTS_API int dtts_fft_blocks_forward(dtts_handle h, const float* x_dev, const int32_t* lens_dev, const float* pos_table_dev, int n_pos,
                             int B, int T, float* y_dev, dtts_stream stream);
+
+/*
+ * Gloss embeddings — dtts_text2mel_fetch(h, DTTS_GLOSS_ENCODE, (dtts_gloss_args*), stream), args->size = sizeof(*args): not a copy, needs NO
+ * encode, and not one of the DTTS_OUT_* outputs of the text-to-mel path (it makes an INPUT of that path: the dictionary's embeddings); it
+ * goes through the same dispatcher as the block items so that the library keeps its entry points.  Replaces get_encodings of the
+ * reference's binariser (data_gen/tts/binarizer_zh.py) for n_gloss glosses at once, with the encoder of dtts_finalize_weights(DTTS_PART_GLOSS).  The glosses are packed back to back as ONE ragged sequence: gloss g owns rows
+ * tok_off[g] .. tok_off[g + 1] - 1 of ids_dev ([CLS] .. [SEP] included) and of out_dev; L_g = its length, 1 .. DTTS_GLOSS_MAX_L.  Per gloss,
+ * alone (no padded rows exist, a row's arithmetic never depends on another gloss):
+ *   E = word_embeddings[ids]; h_0 = LN(E + token_type_embeddings[0]); h_(l+1) = layer l of h_l, a post-LN BERT layer whose q and k are
+ *   rotated per head of 64 channels by the position's angle p / 10000^(2 j / 64) (pairs (2 j, 2 j + 1); v is not rotated), scores / 8,
+ *   softmax over the gloss's own L_g keys, erf-GELU feed-forward; out = (E + h_0 + .. + h_n) / (n + 2), summed in that order in fp32.
+ * Dense layers: exact fp32 products in a fixed order (a row's bits depend on the layer alone); LayerNorm with the biased variance.  No
+ * atomics: a gloss's rows are bit-identical alone and at any place in any batch.  An id outside [0, vocab) gives a zero E row and
+ * status_dev i64 [2] = {first offending row + 1, that id} (0, 0: every id valid; written by every call).
+ * tok_off_dev is copied to the host and checked before the first launch (one stream synchronisation per call).  Workspace:
+ * sum_L * (3 hidden + max(4 hidden, ffn)) floats.
+ * DTTS_E_INVAL (naming the value): a wrong size, n_gloss < 1, L_max outside 1 .. DTTS_GLOSS_MAX_L, a sum_L that n_gloss glosses of 1 .. L_max
+ * tokens cannot have or that exceeds what one call takes, a NULL or misaligned pointer — all checked before the handle — then
+ * tok_off[0] != 0, a gloss of fewer than 1 or more than DTTS_GLOSS_MAX_L tokens, tok_off[n_gloss] != sum_L, an L_max that is not the
+ * longest gloss's length.  DTTS_E_STATE before dtts_finalize_weights(DTTS_PART_GLOSS).
+ */
+#define DTTS_GLOSS_ENCODE 64
+#define DTTS_GLOSS_MAX_L 64
+typedef struct dtts_gloss_args {
+    int32_t size;                 /* sizeof(dtts_gloss_args) */
+    int32_t n_gloss;
+    int32_t sum_L;                /* rows of ids_dev / out_dev */
+    int32_t L_max;                /* the longest gloss's length */
+    const int64_t* ids_dev;       /* [sum_L] */
+    const int32_t* tok_off_dev;   /* [n_gloss + 1] */
+    float* out_dev;               /* [sum_L][hidden] */
+    int64_t* status_dev;          /* [2] */
+} dtts_gloss_args;
 
 /*
  * Output side — replaces the sample conversion of save_wav (utils/audio.py:11-16; called from after_infer,
