@@ -333,6 +333,11 @@ int build_gloss(dtts_ctx* h) {
         if (Fl < 1 || Fl > 65536 || (l > 0 && Fl != F))
             return fail(h, DTTS_E_INVAL, "%s: %sintermediate.dense.weight is %s; the encoder's is [intermediate_size <= 65536, %d], one size for all layers", GL_ME,
                         p.c_str(), gl_shape(wi_it->second.shape).c_str(), C);
+        // output.dense stages its input rows, whose pitch is intermediate_size floats, in 16-byte pieces (conv1d.hip: `ci < C_in` guards the
+        // piece's FIRST channel): a size that is no multiple of 4 would misalign every other row's loads and read past the last row
+        if (Fl % 4)
+            return fail(h, DTTS_E_INVAL, "%s: intermediate_size = %lld (supported: a multiple of 4 up to 65536; the feed-forward rows are read in 16-byte pieces)",
+                        GL_ME, (long long)Fl);
         F = (int)Fl;
         const HostTensor* wi = gl_tensor(h, p + "intermediate.dense.weight", {F, C}, DTTS_E_INVAL, &rc);
         if (!wi) return rc;

@@ -29,6 +29,10 @@ def check_config(config, n_hidden=8):
     E = int(config.get("embedding_size", H))
     if E != H:
         raise ValueError(f"embedding_size = {E} differs from hidden_size = {H} (the reference's feature buffer assumes they are equal)")
+    F = int(config["intermediate_size"])
+    if not 4 <= F <= 65536 or F % 4:
+        raise ValueError(f"intermediate_size = {F}: the gloss encoder supports a multiple of 4 up to 65536 (the feed-forward rows are read in "
+                         f"16-byte pieces)")
     if config.get("rotary_value", False):
         raise ValueError("rotary_value = true is not supported (the reference's checkpoint rotates q and k only)")
     if config.get("hidden_act", "gelu") != "gelu":

@@ -224,7 +224,9 @@ DTTS_API int dtts_load_weight(dtts_handle h, const char* name, const void* host_
  *   "intermediate.dense.weight" [ffn][hidden] + ".bias" [ffn], "output.dense.weight" [hidden][ffn] + ".bias" [hidden];
  *   "gloss.config" [4]: num_attention_heads, layer_norm_eps, rotary_value (0 / 1), hidden_act (0 = "gelu", the erf form; 1 = any other).
  * The number of layers is what was loaded (1 .. 64); the mean runs over n + 2 terms.  "encoder.embed_positions.weight" is not read: the
- * rotary table is made here, in fp64, rounded once.  DTTS_E_INVAL naming the value: a hidden size that is no multiple of 64, heads of
+ * rotary table is made here, in fp64, rounded once.  Supported: hidden a multiple of 64 up to 8192, ffn (intermediate_size) a multiple of 4
+ * up to 65536 (the feed-forward rows are read in 16-byte pieces), one ffn for all layers.  DTTS_E_INVAL naming the value: a hidden size that
+ * is no multiple of 64, an intermediate_size that is no multiple of 4, heads of
  * another width than 64, a word-embedding width (embedding_size) other than the hidden size, rotary_value = 1, hidden_act != 0, a tensor
  * of another shape, and a tensor that a loaded layer lacks; DTTS_E_NOENT: no config / embeddings at all.  Built once per context. */
 #define DTTS_PART_GLOSS 1024

@@ -15,11 +15,31 @@ def config(hidden, heads, ffn, layers, vocab=VOCAB):
 
 # name -> (config, n_hidden): the accuracy shapes (the mean runs over layers + 2 terms, n_hidden = layers + 1 hidden states)
 CFGS = {"h128x7": (config(128, 2, 256, 7), 8), "h768x1": (config(768, 12, 3072, 1), 2), "h384x2": (config(384, 6, 1536, 2), 3)}
-GOLDEN_CFG = config(128, 2, 256, 8)      # eight layers in the checkpoint, seven used: what the reference does with its twelve
+# name -> (config, n_hidden): each named after the dispatch branch it forces (conv1d.hip: launch_engine<ENG_F32>, gloss.hip: the head
+# groups of gloss_attn_kernel, the shared workspace row W = max(4 hidden, ffn))
+EDGE_CFGS = {
+    # a head group of ONE head (nh = 1); ffn > 4 hidden: the workspace row is the feed-forward's, not q | k | v | ctx
+    "h64_nh1_wideffn": (config(64, 1, 320, 2), 3),
+    # nh = 3; ffn = 200: C_out_pad = 224 of intermediate.dense and C_in_pad = 256 of output.dense are padded, ffn % 32 != 0
+    "h192_nh3_pad": (config(192, 3, 200, 2), 3),
+    # the first width whose 32-row tile of three bf16 planes (32 x (2 x 832 + 16) x 3 = 161,280 B) exceeds the short kernel's 150 KB:
+    # q | k | v, the output projection and the GELU layer on conv1d_cl_kernel<ENG_F32>; head groups 4 + 4 + 4 + 1; output.dense
+    # (C_in = 256) on the short kernel
+    "h832_generic": (config(832, 13, 256, 1), 2),
+    # the generic kernel on all four contractions
+    "h1024_generic": (config(1024, 16, 4096, 1), 2),
+}
+ALL_CFGS = {**CFGS, **EDGE_CFGS}
+GOLDEN_CFG = config(128, 2, 256, 8)     # eight layers in the checkpoint, seven used: what the reference does with its twelve
 GOLDEN_LENGTHS = (1, 2, 3, 5, 31, 64)
 
 # every path of the attention kernel and the GEMM row seams in one call: sum = 229, no multiple of 32 or 128
 MIXED_LENGTHS = (1, 2, 3, 31, 32, 33, 63, 64)
+
+# row totals that END on a tile: 32 (the short kernel's and the generic kernel's small tile), 64 / 65 (the generic kernel's switch from
+# 32 t x 128 co to 128 t x 64 co), 128 and 256 (its large tile); then calls whose longest gloss, which sizes the attention kernel's LDS
+# tiles, has 2 and 33 tokens
+SEAM_LENGTHS = ((32,), (64,), (64, 1), (64, 64), (63, 64, 64, 64, 1), (2, 1, 2), (33, 1, 32))
 
 
 def id_sets(lengths, seed=SEED, vocab=VOCAB):
