@@ -2,10 +2,10 @@
 (test infrastructure), the non-default shapes the text-to-mel tests run, and the per-row comparison they use.
 
 ``forward`` composes the oracle's pieces (oracle/dict_tts_ref.py: dict_encoder, add_dur, expand, prior_flow_reverse, wn; fvae_infer's
-body) with every shape taken from the hparams (synth.acoustic_shape), as tests/speaker_ref.py does for speakers; the posterior pass is
-tests/posterior_ref.forward_posterior(hp=...).  The dtype of the folded state dict decides the arithmetic: ``state(..., torch.float64)``
-gives the float64 reference the GPU is compared with.  At the ps_flow.yaml shape in fp32 it IS oracle.dict_tts_ref.forward_infer, bit for
-bit (tests/test_acoustic_ref_cpu.py).
+body) with every shape taken from the hparams (synth.acoustic_shape); ``form`` / ``spk`` add the speaker conditioning of
+tests/speaker_ref.py at any shape and dtype; the posterior pass is tests/posterior_ref.forward_posterior(hp=..., form=..., spk=...).
+The dtype of the folded state dict decides the arithmetic: ``state(..., torch.float64)`` gives the float64 reference the GPU is compared
+with.  At the ps_flow.yaml shape in fp32 it IS oracle.dict_tts_ref.forward_infer, bit for bit (tests/test_acoustic_ref_cpu.py).
 
 ``rowcmp`` reports, for outputs with rows on axis 1 (frames or words): the max abs error and where it is, the largest RMS over a
 window of WIN consecutive rows of one utterance and where it starts, and the global RMS.  ``check`` prints one ``T2MMEAS {json}`` line
@@ -17,6 +17,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+import speaker_ref
 from dict_tts_amd import synth
 from oracle import dict_tts_ref as ref
 from oracle import hifigan_ref as href
@@ -60,9 +61,12 @@ def inputs(batch, dtype=torch.float32):
     return t["word_tokens"], (f(t["keys"]), f(t["values"]), f(t["key_map"]), t["pinyin"], t["pinyin_map"]), t["pron_modified"]
 
 
-def forward(sd, hp, word_tokens, dict_msg, pron_modified, mel2word=None, z_p=None, hook=None):
+def forward(sd, hp, word_tokens, dict_msg, pron_modified, mel2word=None, z_p=None, hook=None, form=None, spk=None, spk_hook=None):
     """PortaSpeech_dict.forward(infer=True) (modules/dict_tts/model.py:36-62,84-121) at the shape of hparams hp.  sd: state(...);
     z_p: [B, latent, T_mel/4] or a callable (B, T4) -> tensor; hook: oracle.dict_tts_ref.wn's (plants a kernel defect).
+    form / spk: speaker conditioning exactly as tests/speaker_ref.forward_infer_spk restates it ("embed": spk [B, 256] in sd's dtype,
+    "id": int64 [B]; None = none, bit for bit the unconditioned forward); spk_hook(weo, rows, nonpadding) -> (weo, dur_input), if given,
+    replaces the two speaker lines (plants a defect of the speaker epilogue: tests/speaker_shapes.py).
     -> word_encoder_out, dict_attn, pron_attn, context, dur, mel2word, x_mask, z (the reverse flow's output), mel_out"""
     sh = synth.acoustic_shape(hp)
     dt = sd["fvae.decoder.out_proj.weight"].dtype
@@ -70,9 +74,18 @@ def forward(sd, hp, word_tokens, dict_msg, pron_modified, mel2word=None, z_p=Non
         ret = {}
         weo, dict_attn, pron_attn, context = ref.dict_encoder(sd, word_tokens, dict_msg, pron_modified, sh["hidden_size"], sh["num_heads"],
                                                               sh["enc_ffn_kernel_size"])
-        ret.update(dict_attn=dict_attn, pron_attn=pron_attn, word_encoder_out=weo, context=context)
         nonpadding = (1 - word_tokens.eq(0).to(dt))[:, :, None]
-        dur, mel2word = ref.add_dur(sd, weo * nonpadding, mel2word, sh["dur_predictor_layers"], sh["dur_predictor_kernel"])
+        dur_input = None
+        if form is not None:
+            rows = speaker_ref.project(sd, form, spk)
+            if spk_hook is not None:
+                weo, dur_input = spk_hook(weo, rows, nonpadding)
+            else:
+                weo = weo + rows[:, None, :]                                    # model.py:94, every row
+        ret.update(dict_attn=dict_attn, pron_attn=pron_attn, word_encoder_out=weo, context=context)
+        if dur_input is None:
+            dur_input = weo * nonpadding                                        # model.py:96
+        dur, mel2word = ref.add_dur(sd, dur_input, mel2word, sh["dur_predictor_layers"], sh["dur_predictor_kernel"])
         ret["dur"] = dur
         x, tgt_nonpadding, mel2word = ref.expand(weo, mel2word)
         ret["mel2word"] = mel2word
@@ -197,10 +210,11 @@ KL_REL = 1.4e-5                                                           # |kl 
 _SD = {}
 
 
-def sd_np(hp):
-    key = tuple(sorted(hp.items()))
+def sd_np(hp, form=None, num_spk=4):
+    """the seeded state dict of shape hp; form "embed" / "id" adds the spk_embed_proj of a checkpoint with num_spk speakers"""
+    key = tuple(sorted(hp.items())) + (() if form is None else (form, num_spk))
     if key not in _SD:
-        _SD[key] = synth.dict_tts_state_dict(SEED, acoustic=hp)
+        _SD[key] = synth.dict_tts_state_dict(SEED, acoustic=hp, speaker=form, num_spk=num_spk)
     return _SD[key]
 
 

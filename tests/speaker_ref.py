@@ -54,10 +54,11 @@ def g11_state_dict(form):
 
 
 def project(sd, form, spk):
-    """spk_embed_proj(spk) -> [B, hidden] (modules/portaspeech/model.py:159-163)"""
+    """spk_embed_proj(spk) -> [B, hidden] (modules/portaspeech/model.py:159-163), in the state dict's dtype (fp32, or float64 for the
+    restatements the GPU is compared with)"""
     if form == "id":
         return F.embedding(spk.long(), sd["spk_embed_proj.weight"])
-    return F.linear(spk.float(), sd["spk_embed_proj.weight"], sd["spk_embed_proj.bias"])
+    return F.linear(spk.to(sd["spk_embed_proj.weight"].dtype), sd["spk_embed_proj.weight"], sd["spk_embed_proj.bias"])
 
 
 def forward_infer_spk(sd, form, spk, word_tokens, dict_msg, pron_modified, mel2word=None, z_p=None):
