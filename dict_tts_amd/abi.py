@@ -70,6 +70,15 @@ MELDISC_WINS = (32, 64, 128)
 PART_GLOSS = 1024     # the gloss encoder (RoFormer): "gloss.<HF key without 'roformer.'>" + "gloss.config"; built once per context
 GLOSS_ENCODE = 64     # DTTS_GLOSS_ENCODE: what dtts_text2mel_fetch takes for a GlossArgs block (not an OUT_ item: it is no output of the text-to-mel path)
 GLOSS_MAX_L = 64      # DTTS_GLOSS_MAX_L: tokens per gloss, [CLS] and [SEP] included
+PART_PORTASPEECH = 2048   # the PortaSpeech baseline: "ps.<state-dict key>" + "ps.config" + "ps.word_encoder.pos_table"; built once; excludes PART_ACOUSTIC
+PS_ENCODE = 65            # DTTS_PS_ENCODE: what dtts_text2mel_fetch takes for a PsArgs block (the baseline's encode; not an OUT_ item)
+PS_PH_ENCODER_OUT, PS_ATTN, PS_DECODER_INP = 66, 67, 68   # DTTS_PS_*: the copy items after a PS_ENCODE
+PS_BAD_TOKEN, PS_ZERO_TOKEN, PS_BAD_PH2WORD, PS_EMPTY_WORD, PS_BAD_MEL2WORD = 1, 2, 3, 4, 5   # dtts_ps_args status codes
+PS_STATUS_NAMES = {PS_BAD_TOKEN: "DTTS_PS_BAD_TOKEN: a token outside [0, n_phone)",
+                   PS_ZERO_TOKEN: "DTTS_PS_ZERO_TOKEN: a zero token inside the live prefix",
+                   PS_BAD_PH2WORD: "DTTS_PS_BAD_PH2WORD: ph2word must start at 0 or 1, grow by 0 or 1 per live phoneme up to T_w, and be 0 past the live prefix",
+                   PS_EMPTY_WORD: "DTTS_PS_EMPTY_WORD: a live frame whose word has no phonemes",
+                   PS_BAD_MEL2WORD: "DTTS_PS_BAD_MEL2WORD: mel2word must lie in [0, T_w], be non-decreasing over its non-zero prefix and 0 behind it"}
 SPECTRAL_FORWARD, SPECTRAL_INVERSE = 1, 2  # dtts_spectral_args.mode bits; both = the reference's denoise
 SPK_EMBED, SPK_ID = 1, 2   # dtts_text2mel_speakers kinds: fp32 [B,256] (use_spk_embed) / int64 [B] (use_spk_id)
 TIMER_VOC_CONV, TIMER_S2PA = 1, 2
@@ -266,6 +275,19 @@ def gloss_args(n_gloss, ids, tok_off, sum_L, L_max, out, status):
     return GlossArgs(C.sizeof(GlossArgs), int(n_gloss), int(sum_L), int(L_max), ids or None, tok_off or None, out or None, status or None)
 
 
+class PsArgs(C.Structure):
+    """dtts_ps_args (include/dicttts_hip.h): the argument block of dtts_text2mel_fetch(DTTS_PS_ENCODE)"""
+    _fields_ = [("size", C.c_int32), ("B", C.c_int32), ("T_ph", C.c_int32), ("T_w", C.c_int32), ("T_m2w", C.c_int32), ("want_attn", C.c_int32),
+                ("txt_tokens_dev", C.c_void_p), ("ph2word_dev", C.c_void_p), ("mel2word_dev", C.c_void_p), ("status_dev", C.c_void_p),
+                ("T_mel_host", C.POINTER(C.c_int32))]
+
+
+def ps_args(B, T_ph, T_w, txt_tokens, ph2word, status, T_mel, mel2word=None, T_m2w=0, want_attn=True):
+    """a filled PsArgs block (device pointers as integers, 0 / None = NULL; T_mel: a ctypes.c_int32 the call writes)"""
+    return PsArgs(C.sizeof(PsArgs), int(B), int(T_ph), int(T_w), int(T_m2w), int(bool(want_attn)), txt_tokens or None, ph2word or None,
+                  mel2word or None, status or None, C.pointer(T_mel) if T_mel is not None else None)
+
+
 class DttsConfig(C.Structure):
     """struct dtts_config (include/dicttts_hip.h); field <- reference hparams key.
     resblock_dilation_sizes: one row per kernel size; three dilations >= 1 = ResBlock1, a row whose third entry is 0 = a two-dilation
@@ -285,6 +307,14 @@ class DttsConfig(C.Structure):
 
 class DttsError(RuntimeError):
     pass
+
+
+def ps_status_error(status):
+    """None for a clean status word of a PS_ENCODE ([4] integers), else the message naming utterance, code, value and position"""
+    st = [int(v) for v in status]
+    if st[0] == 0:
+        return None
+    return f"utterance {st[0] - 1}, position {st[3]}, value {st[2]}: {PS_STATUS_NAMES.get(st[1], f'code {st[1]}')}"
 
 
 _lib = None
@@ -588,6 +618,16 @@ class Context:
         i64 [2] out.  Synchronises the stream once (the offsets are checked on the host)."""
         a = gloss_args(n_gloss, **kw)
         self._chk(self.lib.dtts_text2mel_fetch(self.h, GLOSS_ENCODE, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_GLOSS_ENCODE)")
+
+    def ps_encode(self, B, T_ph, T_w, txt_tokens, ph2word, status, stream, mel2word=None, want_attn=True):
+        """the PortaSpeech baseline's encode (dtts_text2mel_fetch(DTTS_PS_ENCODE); needs PART_PORTASPEECH finalised): device pointers txt_tokens /
+        ph2word i64 [B, T_ph], status i64 [4] out, mel2word = (ptr, T_m2w) or None; returns T_mel.  Synchronises the stream once without
+        mel2word; the caller reads ``status`` afterwards (``ps_status_error``)."""
+        t_mel = C.c_int32(0)
+        m2w, t_m2w = mel2word if mel2word else (None, 0)
+        a = ps_args(B, T_ph, T_w, txt_tokens, ph2word, status, t_mel, m2w, t_m2w, want_attn)
+        self._chk(self.lib.dtts_text2mel_fetch(self.h, PS_ENCODE, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_PS_ENCODE)")
+        return t_mel.value
 
     def timer_enable(self, which):
         self._chk(self.lib.dtts_timer_enable(self.h, which), "dtts_timer_enable")

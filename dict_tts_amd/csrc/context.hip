@@ -24,7 +24,8 @@ static const struct { const char* name; Arena dtts_ctx::*a; } ARENAS[] = {
     {"loss workspace", &dtts_ctx::a_loss},           {"dtw workspace", &dtts_ctx::a_dtw},
     {"pitch workspace", &dtts_ctx::a_pitch},         {"loudness workspace", &dtts_ctx::a_loud},
     {"discriminator workspace", &dtts_ctx::a_disc},  {"speaker encoder workspace", &dtts_ctx::a_spkenc},
-    {"mel discriminator workspace", &dtts_ctx::a_meldisc}, {"gloss workspace", &dtts_ctx::a_gloss}};
+    {"mel discriminator workspace", &dtts_ctx::a_meldisc}, {"gloss workspace", &dtts_ctx::a_gloss},
+    {"portaspeech workspace", &dtts_ctx::a_ps},      {"portaspeech frame workspace", &dtts_ctx::a_psf}};
 constexpr int ARENA_VOC = 2;   // dtts_debug_poke looks at this one first
 
 namespace dtts {
@@ -63,6 +64,8 @@ static const Unit UNITS[] = {
      ITEM(MELDISC, dtts_meldisc_args, meldisc_forward), true},
     {PART(GLOSS), "gloss.", build_gloss, true, [](const dtts_ctx* h) { return h->gloss_ready; },
      DTTS_GLOSS_ENCODE, as_block<dtts_gloss_args, gloss_forward>, true},   // (an item outside the DTTS_OUT_* numbering: it is no output of an encode)
+    {PART(PORTASPEECH), "ps.", build_ps, true, [](const dtts_ctx* h) { return h->ps_ready; },
+     DTTS_PS_ENCODE, as_block<dtts_ps_args, ps_forward>, true},             // (the same: it is the baseline's encode itself)
 };
 #undef PART
 #undef NO_PART

@@ -38,6 +38,7 @@
 #include "spkenc.h"
 #include "meldisc.h"
 #include "gloss.h"
+#include "portaspeech.h"
 
 // dtts_config.tune_flags: the bits the library honours are listed at TUNE_RELEASE_MASK (context.hip)
 #define DTTS_TUNE(h, bit) (((h)->tune & (bit)) != 0)
@@ -119,6 +120,23 @@ struct Encoder {
     std::vector<EncLayer> l;
     float *lg = nullptr, *lb = nullptr;
 };
+// an FFT block stack (FFTBlocks / FastspeechDecoder): the context's "fft." part and the PortaSpeech baseline's word encoder
+struct FftStack {
+    std::vector<EncLayer> l;
+    float *g = nullptr, *b = nullptr, *alpha = nullptr;   // the last LayerNorm (or null), pos_embed_alpha (or null = 1)
+    int K = 9;                                            // FFN kernel size
+    bool pos = true, last_norm = true;
+};
+// the buffers a stack runs in, rows = B * T: x, hb, att [rows][C], qkv [rows][3C], ff [rows][4C], lens [B], pos [rows]
+struct FftBufs {
+    float *x, *hb, *qkv, *att, *ff;
+    int *lens, *pos;
+};
+// a layer of the baseline's relative-position phoneme encoder (post-LN): emb_rel_k / emb_rel_v [2 w + 1][d_k]
+struct PsLayer {
+    PackedConv qkv, o, ffn1, ffn2;
+    float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr, *ek = nullptr, *ev = nullptr;
+};
 struct WNet {
     PackedConv cond;
     std::vector<PackedConv> in, rs;
@@ -152,8 +170,7 @@ struct dtts_ctx {
     std::vector<StaticBuf> rz_static;                         // debug: weight packs / tables (user pointer, payload bytes) between red zones
     bool acoustic_ready = false, vocoder_ready = false, fft_ready = false;
     // ---- FFT block stack
-    std::vector<dtts::EncLayer> fft;
-    float *fft_g = nullptr, *fft_b = nullptr, *fft_alpha = nullptr;
+    dtts::FftStack fft;
     dtts::Arena a_fft;
     // ---- acoustic model
     float *word_emb = nullptr, *pinyin_emb = nullptr;
@@ -304,6 +321,24 @@ struct dtts_ctx {
     int gloss_vocab = 0, gloss_C = 0, gloss_F = 0;
     float gloss_eps = 0.f;
     dtts::Arena a_gloss;
+    // ---- the PortaSpeech baseline (dtts_text2mel_fetch(DTTS_PS_ENCODE); portaspeech.hip): the packs of dtts_finalize_weights(DTTS_PART_PORTASPEECH)
+    // beside the duration predictor and the FVAE it shares with the Dict-TTS part (dur_*, g_pre, flows, dec_*), and the workspace of an
+    // encode, which keeps the dense condition of the decode (decoder_inp) and the three items a fetch may copy
+    bool ps_ready = false;
+    int ps_window = 4;
+    float* ps_emb = nullptr;                          // ph_encoder.emb [n_phone][hidden]
+    dtts::PackedConv ps_pre[3], ps_pre_proj;          // the prenet's convolutions and its 1x1 projection
+    float *ps_pre_g[3] = {nullptr, nullptr, nullptr}, *ps_pre_b[3] = {nullptr, nullptr, nullptr};
+    std::vector<dtts::PsLayer> ps_layers;
+    dtts::FftStack ps_word;                           // word_encoder
+    float* ps_pos_table = nullptr;                    // its sinusoid table [ps_n_pos][hidden]
+    int ps_n_pos = 0;
+    float* ps_freq = nullptr;                         // sin_pos frequencies [hidden / 2]
+    dtts::PackedConv ps_enc_pos, ps_dec_qr, ps_q, ps_kv, ps_out;   // enc_pos_proj; dec_query_proj | dec_res_proj; attn's Wq; Wk | Wv; out_proj
+    dtts::Arena a_ps, a_psf;                          // the phoneme / word side, and the frames' (sized once T_mel is known)
+    bool ps_encoded = false;                          // the last successful encode was the baseline's: decode reads ps_g
+    float *ps_g = nullptr, *ps_ph_out = nullptr, *ps_attn = nullptr;
+    int ps_T_ph = 0;
 };
 
 namespace dtts {
@@ -449,6 +484,20 @@ int spkenc_forward(dtts_ctx* h, const dtts_spkenc_args* a, hipStream_t stream); 
 int build_meldisc(dtts_ctx* h);   // meldisc.hip
 int meldisc_forward(dtts_ctx* h, const dtts_meldisc_args* a, hipStream_t stream);     // meldisc.hip (the same)
 int build_gloss(dtts_ctx* h);     // gloss.hip
+int build_ps(dtts_ctx* h);        // portaspeech.hip
+int ps_forward(dtts_ctx* h, const dtts_ps_args* a, hipStream_t stream);               // portaspeech.hip (the same)
+// text2mel_build.hip: the halves of the acoustic part that the PortaSpeech baseline shares, from the tensors "<m>dur_predictor.*" / "<m>fvae.*"
+bool build_dur_predictor(dtts_ctx* h, Need& need, const std::string& m);
+bool build_fvae(dtts_ctx* h, Need& need, const std::string& m, int* rc);   // *rc != 0: refused with a message of its own
+// text2mel.hip: the duration predictor's launches (in [B][T][cin] -> dur [B][T], d0 / d1 [B*T][dur_chans] scratch) and the frame layout
+// every encode ends with (T_raw -> T_mel, the decode workspace, mel2word filled from `starts` or copied from mel2word, the encoded state)
+int run_dur_predictor(dtts_ctx* h, const float* in, int cin, const int* ilens, float* d0, float* d1, float* dur, int B, int T, hipStream_t s);
+int lay_out_frames(dtts_ctx* h, const int64_t* mel2word, int T_m2w, int T_raw, const int* starts, const int* ilens, int T_w, hipStream_t s,
+                   int32_t* T_mel_host);
+// fft_blocks.hip: a stack's weights from "<p>layers.<i>.op.*" (+ "<p>layer_norm.*", "<p>pos_embed_alpha"), and its launches
+int build_fft_stack(dtts_ctx* h, Need& need, FftStack& S, const std::string& p, int layers, int C, int heads, bool* ok);
+int run_fft_stack(dtts_ctx* h, const FftStack& S, const float* x_in, const int* lens_in, const float* pos_table, int n_pos, int B, int T, int C,
+                  int heads, float* y, const FftBufs& w, hipStream_t s);
 int gloss_forward(dtts_ctx* h, const dtts_gloss_args* a, hipStream_t stream);         // gloss.hip (the same)
 
 // ---- a row of the one table of parts and block items (UNITS, context.hip): dtts_finalize_weights walks its parts in row order,

@@ -197,25 +197,34 @@ int run_prior_flow(dtts_ctx* h, const std::vector<Flow>& flows, const float* fs_
 // output (or the zero row): the convolution is applied to the B*T_w word rows (33x fewer than the B*T frames) and its
 // output gathered by mel2word; frames with mel2word == 0 get conv(0) = bias.  Bit-identical: every output row of this
 // kernel depends only on its own input row, summed in the same order whatever the tile shape.
+// dense_g != null (the PortaSpeech baseline): g is a dense per-frame tensor [B][T][C], no gather of word rows: the conditioning is the same
+// convolution applied to the B*T frames (run_wn's dense-g branch) and every layer reads its own row of it.
 int run_decoder_tail(dtts_ctx* h, Arena& A, const char* ws_name, float* cond_w, float* dx, float* dacts, float* dout, const float* mask,
-                     float* mel_out, int mel_cap, hipStream_t s) {
+                     float* mel_out, int mel_cap, hipStream_t s, const float* dense_g = nullptr) {
     const dtts_config& c = h->cfg;
     const int B = h->B, T = h->T_mel, C = c.hidden_size, Hd = c.fvae_enc_dec_hidden, CW = 2 * Hd * c.fvae_dec_n_layers;
-    // row 0: conv(0) = the bias, rows 1..: the B*T_w word rows
-    if (hipMemcpyAsync(cond_w, h->dec_wn.cond.bias, (size_t)CW * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return fail(h, DTTS_E_HIP, "decoder conditioning bias row");
-    ConvParams p = base_params(h->weo, C, B, h->T_w, h->T_w, cond_w + CW, CW);
-    LAUNCH(conv1d_launch(h->dec_wn.cond, p, s));
     int rc;
-    if (!h->dec_wn.in.empty() && h->dec_wn.in[0].engine == ENG_BF16X3) {
-        // split-operand layers: every layer's epilogue gathers its conditioning row by mel2word from the word-level tensor (L2-resident,
-        // B*T_w rows) — the [B*T, 2*Hd*layers] expansion (221 MB written and read back at B=60) never exists
-        rc = run_wn(h, h->dec_wn, dx, nullptr, C, cond_w, dacts, dout, B, T, s, h->m2w, h->T_w, mask);
-    } else {
+    ConvParams p;
+    if (dense_g) {
         float* dcond = A.alloc<float>((size_t)B * T * CW);
         if (!dcond) return fail(h, DTTS_E_NOMEM, "%s", ws_name);
-        LAUNCH(expand_launch(cond_w + CW, h->m2w, dcond, nullptr, B, h->T_w, T, CW, s, h->dec_wn.cond.bias));
-        rc = run_wn(h, h->dec_wn, dx, nullptr, C, dcond, dacts, dout, B, T, s, nullptr, 0, mask);
+        rc = run_wn(h, h->dec_wn, dx, dense_g, C, dcond, dacts, dout, B, T, s, nullptr, 0, mask);
+    } else {
+        // row 0: conv(0) = the bias, rows 1..: the B*T_w word rows
+        if (hipMemcpyAsync(cond_w, h->dec_wn.cond.bias, (size_t)CW * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return fail(h, DTTS_E_HIP, "decoder conditioning bias row");
+        p = base_params(h->weo, C, B, h->T_w, h->T_w, cond_w + CW, CW);
+        LAUNCH(conv1d_launch(h->dec_wn.cond, p, s));
+        if (!h->dec_wn.in.empty() && h->dec_wn.in[0].engine == ENG_BF16X3) {
+            // split-operand layers: every layer's epilogue gathers its conditioning row by mel2word from the word-level tensor (L2-resident,
+            // B*T_w rows) — the [B*T, 2*Hd*layers] expansion (221 MB written and read back at B=60) never exists
+            rc = run_wn(h, h->dec_wn, dx, nullptr, C, cond_w, dacts, dout, B, T, s, h->m2w, h->T_w, mask);
+        } else {
+            float* dcond = A.alloc<float>((size_t)B * T * CW);
+            if (!dcond) return fail(h, DTTS_E_NOMEM, "%s", ws_name);
+            LAUNCH(expand_launch(cond_w + CW, h->m2w, dcond, nullptr, B, h->T_w, T, CW, s, h->dec_wn.cond.bias));
+            rc = run_wn(h, h->dec_wn, dx, nullptr, C, dcond, dacts, dout, B, T, s, nullptr, 0, mask);
+        }
     }
     if (rc) return rc;
     p = base_params(dout, Hd, B, T, T, mel_out, c.audio_num_mel_bins);
@@ -228,6 +237,50 @@ int run_decoder_tail(dtts_ctx* h, Arena& A, const char* ws_name, float* cond_w, 
 }
 
 } // namespace
+
+namespace dtts {
+
+// DurationPredictor.forward (modules/portaspeech/model.py:58-66) on in [B][T][cin]; ilens: the rows that are no padding
+int run_dur_predictor(dtts_ctx* h, const float* in, int cin, const int* ilens, float* d0, float* d1, float* dur, int B, int T, hipStream_t s) {
+    const dtts_config& c = h->cfg;
+    for (int i = 0; i < c.dur_predictor_layers; ++i) {
+        ConvParams p = base_params(in, cin, B, T, T, d0, c.dur_chans);
+        p.post_act = 1;
+        LAUNCH(conv1d_launch(h->dur_conv[i], p, s));
+        LAUNCH(layernorm_launch(d0, d1, h->dur_g[i], h->dur_b[i], 1e-5f, ilens, 0, 1, B, T, c.dur_chans, s));
+        in = d1;  // next conv reads d1 and writes d0 again
+        cin = c.dur_chans;
+    }
+    LAUNCH(dur_head_launch(in, h->dur_w, h->dur_bias, ilens, dur, B, T, c.dur_chans, s));
+    return DTTS_OK;
+}
+
+// What every encode ends with: T_raw -> T_mel, the decode workspace with mel2word and x_mask first, mel2word from the durations' `starts`
+// (mel2word == null) or copied, the encoded state
+int lay_out_frames(dtts_ctx* h, const int64_t* mel2word, int T_m2w, int T_raw, const int* starts, const int* ilens, int T_w, hipStream_t s,
+                   int32_t* T_mel_host) {
+    const dtts_config& c = h->cfg;
+    const int B = h->B, C = c.hidden_size;
+    const int fm = c.frames_multiple;
+    const int T_mel = (T_raw % fm) ? T_raw + fm - T_raw % fm : T_raw;
+    const int T4 = T_mel / 4;
+    const size_t mrows = (size_t)B * T_mel, qrows = (size_t)B * T4;
+    const int Hd = c.fvae_enc_dec_hidden, Hf = c.prior_glow_hidden;
+    HIPCHK(h->a_dec.reserve(mrows * (size_t)(C + 1 + 2 + 2 * Hd * c.fvae_dec_n_layers + 3 * Hd + 8) * sizeof(float) +
+                            qrows * (size_t)(C + 2 * c.latent_size + 2 * Hf * c.prior_glow_n_layers * (1 + c.prior_glow_n_blocks) + 3 * Hf + 16) * sizeof(float) +
+                            (size_t)B * T_w * 2 * Hd * c.fvae_dec_n_layers * sizeof(float) + (64 << 10), s));
+    h->m2w = h->a_dec.alloc<int64_t>(mrows);
+    h->x_mask = h->a_dec.alloc<float>(mrows);
+    if (!h->m2w || !h->x_mask) return fail(h, DTTS_E_NOMEM, "decoder workspace");
+    if (!mel2word) LAUNCH(mel2word_fill_launch(starts, h->mel_lens, ilens, h->m2w, B, T_w, T_raw, T_mel, s));
+    else LAUNCH(mel2word_copy_launch(mel2word, h->m2w, h->mel_lens, B, T_m2w, T_mel, s));
+    h->T_mel = T_mel;
+    *T_mel_host = T_mel;
+    h->encoded = true;
+    return DTTS_OK;
+}
+
+} // namespace dtts
 
 extern "C" {
 
@@ -255,6 +308,7 @@ static int encode_impl(dtts_handle h, const int64_t* word_tokens, const float* k
     const int C = c.hidden_size, D = c.gloss_dim, F = 4 * C;
     const size_t rows = (size_t)B * T_w;
     h->encoded = false;
+    h->ps_encoded = false;
     HIPCHK(h->a_enc.reserve(rows * (size_t)(12 * C + 3 * C + F + 2 * D + 3 * c.dur_chans + P + 8) * sizeof(float) +
                             (size_t)B * L_k * T_w * sizeof(float) + (size_t)B * (T_w + 8) * 4 * sizeof(int) + (64 << 10), s));
     Arena& A = h->a_enc;
@@ -362,19 +416,8 @@ static int encode_impl(dtts_handle h, const int64_t* word_tokens, const float* k
     t_dict.stop();
     // A5: duration predictor
     LAUNCH(rowcount_nonzero_launch(h->weo, ilens, B, T_w, C, s));
-    {
-        const float* in = h->weo;
-        int cin = C;
-        for (int i = 0; i < c.dur_predictor_layers; ++i) {
-            ConvParams p = base_params(in, cin, B, T_w, T_w, d0, c.dur_chans);
-            p.post_act = 1;
-            LAUNCH(conv1d_launch(h->dur_conv[i], p, s));
-            LAUNCH(layernorm_launch(d0, d1, h->dur_g[i], h->dur_b[i], 1e-5f, ilens, 0, 1, B, T_w, c.dur_chans, s));
-            in = d1;  // next conv reads d1 and writes d0 again
-            cin = c.dur_chans;
-        }
-        LAUNCH(dur_head_launch(in, h->dur_w, h->dur_bias, ilens, h->dur, B, T_w, c.dur_chans, s));
-    }
+    rc = run_dur_predictor(h, h->weo, C, ilens, d0, d1, h->dur, B, T_w, s);
+    if (rc) return rc;
     // A6/A7: durations -> mel2word
     int T_raw = 0;
     if (!mel2word) {
@@ -400,22 +443,8 @@ static int encode_impl(dtts_handle h, const int64_t* word_tokens, const float* k
         if (T_m2w <= 0) return fail(h, DTTS_E_INVAL, "mel2word given with T_m2w=%d", T_m2w);
         T_raw = T_m2w;
     }
-    const int fm = c.frames_multiple;
-    const int T_mel = (T_raw % fm) ? T_raw + fm - T_raw % fm : T_raw;
-    const int T4 = T_mel / 4;
-    const size_t mrows = (size_t)B * T_mel, qrows = (size_t)B * T4;
-    const int Hd = c.fvae_enc_dec_hidden, Hf = c.prior_glow_hidden;
-    HIPCHK(h->a_dec.reserve(mrows * (size_t)(C + 1 + 2 + 2 * Hd * c.fvae_dec_n_layers + 3 * Hd + 8) * sizeof(float) +
-                            qrows * (size_t)(C + 2 * c.latent_size + 2 * Hf * c.prior_glow_n_layers * (1 + c.prior_glow_n_blocks) + 3 * Hf + 16) * sizeof(float) +
-                            (size_t)B * T_w * 2 * Hd * c.fvae_dec_n_layers * sizeof(float) + (64 << 10), s));
-    h->m2w = h->a_dec.alloc<int64_t>(mrows);
-    h->x_mask = h->a_dec.alloc<float>(mrows);
-    if (!h->m2w || !h->x_mask) return fail(h, DTTS_E_NOMEM, "decoder workspace");
-    if (!mel2word) LAUNCH(mel2word_fill_launch(starts, h->mel_lens, ilens, h->m2w, B, T_w, T_raw, T_mel, s));
-    else LAUNCH(mel2word_copy_launch(mel2word, h->m2w, h->mel_lens, B, T_m2w, T_mel, s));
-    h->T_mel = T_mel;
-    *T_mel_host = T_mel;
-    h->encoded = true;
+    rc = lay_out_frames(h, mel2word, T_m2w, T_raw, starts, ilens, T_w, s, T_mel_host);
+    if (rc) return rc;
     h->enc_spk = spk != nullptr;
     h->enc_spk_gen = h->spk_gen;
     return DTTS_OK;
@@ -591,7 +620,7 @@ static int decode_impl(dtts_handle h, const float* z_p, int z_ld, float* mel_out
     A.rewind();
     (void)A.alloc<int64_t>(mrows);
     (void)A.alloc<float>(mrows);
-    float* g = A.alloc<float>(mrows * C);
+    float* g = h->ps_encoded ? h->ps_g : A.alloc<float>(mrows * C);   // (the baseline's encode left its dense condition and x_mask behind)
     float* gs = A.alloc<float>(qrows * C);
     float* z = A.alloc<float>(qrows * Z);
     float* fcond = A.alloc<float>(qrows * 2 * Hf * c.prior_glow_n_layers);
@@ -604,7 +633,7 @@ static int decode_impl(dtts_handle h, const float* z_p, int z_ld, float* mel_out
     if (!g || !gs || !z || !fcond || !fh || !facts || !fout || !dx || !dacts || !dout)
         return fail(h, DTTS_E_NOMEM, "decoder workspace");
     // A7: gather-expand (x * tgt_nonpadding is implied: padded frames gather the zero row)
-    LAUNCH(expand_launch(h->weo, h->m2w, g, h->x_mask, B, h->T_w, T, C, s));
+    if (!h->ps_encoded) LAUNCH(expand_launch(h->weo, h->m2w, g, h->x_mask, B, h->T_w, T, C, s));
     // A8: g_sqz = Conv1d(k=8, s=4, p=2)(g)
     int rc = run_g_sqz(h, g, gs, B, T, s);
     if (rc) return rc;
@@ -627,9 +656,9 @@ static int decode_impl(dtts_handle h, const float* z_p, int z_ld, float* mel_out
     // A10: decoder
     ConvParams p = base_params(zf, Z, B, T4, T4, dx, 4 * Hd);  // ConvTranspose1d(k=4,s=4): [B,T4,16] -> [B,T4,4*Hd] == [B,T,Hd]
     LAUNCH(conv1d_launch(h->dec_pre, p, s));
-    float* cond_w = A.alloc<float>(((size_t)B * h->T_w + 1) * 2 * Hd * c.fvae_dec_n_layers);
-    if (!cond_w) return fail(h, DTTS_E_NOMEM, "decoder workspace");
-    return run_decoder_tail(h, A, "decoder workspace", cond_w, dx, dacts, dout, nullptr, mel_out, mel_cap, s);
+    float* cond_w = h->ps_encoded ? nullptr : A.alloc<float>(((size_t)B * h->T_w + 1) * 2 * Hd * c.fvae_dec_n_layers);   // (word rows: unused with a dense g)
+    if (!cond_w && !h->ps_encoded) return fail(h, DTTS_E_NOMEM, "decoder workspace");
+    return run_decoder_tail(h, A, "decoder workspace", cond_w, dx, dacts, dout, nullptr, mel_out, mel_cap, s, h->ps_encoded ? g : nullptr);
 }
 
 int dtts_text2mel_decode(dtts_handle h, const float* z_p, float* mel_out, dtts_stream stream) {
@@ -770,6 +799,11 @@ int dtts_text2mel_fetch(dtts_handle h, int what, void* dst, dtts_stream stream) 
     if (const Unit* u = find_item(what); u && dst && (h || u->null_handle)) return u->forward(h, dst, (hipStream_t)stream);
     if (!h || !dst) return DTTS_E_INVAL;
     if (!h->encoded) return fail(h, DTTS_E_STATE, "dtts_text2mel_fetch before encode");
+    if (h->ps_encoded && (what == DTTS_OUT_PRON_ATTN || what == DTTS_OUT_DICT_ATTN || what == DTTS_OUT_CONTEXT || what == DTTS_OUT_POSTERIOR))
+        return fail(h, DTTS_E_STATE, "dtts_text2mel_fetch: item %d belongs to the Dict-TTS model; the last encode was the PortaSpeech baseline's "
+                    "(DTTS_PS_ENCODE), which has no dictionary attention and whose posterior pass is not implemented", what);
+    if (!h->ps_encoded && (what == DTTS_PS_PH_ENCODER_OUT || what == DTTS_PS_ATTN || what == DTTS_PS_DECODER_INP))
+        return fail(h, DTTS_E_STATE, "dtts_text2mel_fetch: item %d needs an encode of the PortaSpeech baseline (DTTS_PS_ENCODE)", what);
     if (what == DTTS_OUT_POSTERIOR) {   // the posterior pass; dst is the host argument block
         const dtts_posterior_args* a = (const dtts_posterior_args*)dst;
         if (a->size != (int32_t)sizeof(dtts_posterior_args))
@@ -805,6 +839,13 @@ int dtts_text2mel_fetch(dtts_handle h, int what, void* dst, dtts_stream stream) 
         case DTTS_OUT_X_MASK: src = h->x_mask; bytes = mrows * 4; break;
         case DTTS_OUT_CONTEXT: src = h->context; bytes = rows * h->cfg.hidden_size * 4; break;
         case DTTS_OUT_MEL_LENS: src = h->mel_lens; bytes = (size_t)h->B * 4; break;
+        case DTTS_PS_PH_ENCODER_OUT: src = h->ps_ph_out; bytes = (size_t)h->B * h->ps_T_ph * h->cfg.hidden_size * 4; break;
+        case DTTS_PS_DECODER_INP: src = h->ps_g; bytes = mrows * h->cfg.hidden_size * 4; break;
+        case DTTS_PS_ATTN:
+            if (!h->ps_attn) return fail(h, DTTS_E_STATE, "dtts_text2mel_fetch(DTTS_PS_ATTN): the encode ran with want_attn = 0");
+            src = h->ps_attn;
+            bytes = mrows * h->ps_T_ph * 4;
+            break;
         default: return fail(h, DTTS_E_INVAL, "dtts_text2mel_fetch: unknown item %d", what);
     }
     HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));

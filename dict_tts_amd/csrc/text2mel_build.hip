@@ -229,32 +229,10 @@ int build_posterior(dtts_ctx* h) {
 
 namespace dtts {
 
-int build_acoustic(dtts_ctx* h) {
-    Need need{h, ""};
+// The duration predictor (modules/portaspeech/model.py:38-66) from "<m>dur_predictor.*": shared by the Dict-TTS part and the baseline
+bool build_dur_predictor(dtts_ctx* h, Need& need, const std::string& m) {
     const dtts_config& c = h->cfg;
-    const std::string m = "model.";
-    const std::string enc = m + "dict_encoder.S2PA_module";
     bool ok = true;
-    h->word_emb = upload_named(h, need, enc + ".word_emb.weight");
-    const std::string att = enc + ".s2pa_attention";
-    h->pinyin_emb = upload_named(h, need, att + ".pinyin_embedding.weight");
-    ok = ok && h->word_emb && h->pinyin_emb;
-    ok = ok && build_encoder(h, need, h->sem, enc + ".semantic_encoder");
-    ok = ok && build_encoder(h, need, h->lin, enc + ".linguistic_encoder");
-    // S2PA projections (no bias).  k_transform is applied TRANSPOSED to the query (see ops.h)
-    const HostTensor *wq = need.get(att + ".q_transform.weight"), *wk = need.get(att + ".k_transform.weight"),
-                     *wv = need.get(att + ".v_transform.weight"), *wo = need.get(att + ".output_transform.weight");
-    if (ok && wq && wk && wv && wo) {
-        const int H = c.hidden_size, D = c.gloss_dim;
-        const float *pq = wq->f.data(), *pk = wk->f.data(), *pv = wv->f.data(), *po = wo->f.data();
-        ok = ok && pack_conv(h, h->s2_q, ENG_F32, H, H, 1, [=](int co, int ci, int) { return pq[(size_t)co * H + ci]; }, {}, 1, 1, 0);
-        ok = ok && pack_conv(h, h->s2_kT, ENG_F32, D, H, 1, [=](int co, int ci, int) { return pk[(size_t)ci * D + co]; }, {}, 1, 1, 0);
-        ok = ok && pack_conv(h, h->s2_k, ENG_F32, H, D, 1, [=](int co, int ci, int) { return pk[(size_t)co * D + ci]; }, {}, 1, 1, 0);
-        ok = ok && pack_conv(h, h->s2_v, ENG_F32, H, D, 1, [=](int co, int ci, int) { return pv[(size_t)co * D + ci]; }, {}, 1, 1, 0);
-        ok = ok && pack_conv(h, h->s2_o, ENG_F32, H, H, 1, [=](int co, int ci, int) { return po[(size_t)co * H + ci]; }, {}, 1, 1, 0);
-    } else
-        ok = false;
-    // duration predictor
     h->dur_conv.resize(c.dur_predictor_layers);
     h->dur_g.resize(c.dur_predictor_layers);
     h->dur_b.resize(c.dur_predictor_layers);
@@ -268,7 +246,14 @@ int build_acoustic(dtts_ctx* h) {
     h->dur_w = upload_named(h, need, m + "dur_predictor.linear.0.weight");
     h->dur_bias = upload_named(h, need, m + "dur_predictor.linear.0.bias");
     ok = ok && h->dur_w && h->dur_bias;
-    // FVAE
+    return ok;
+}
+
+// The FVAE's inference half (g_pre_net, the prior flow in reverse, the decoder) from "<m>fvae.*": shared in the same way
+bool build_fvae(dtts_ctx* h, Need& need, const std::string& m, int* rc) {
+    const dtts_config& c = h->cfg;
+    bool ok = true;
+    *rc = DTTS_OK;
     ok = ok && pack_plain(h, need, h->g_pre, c.decoder_fp32 ? ENG_F32 : ENG_BF16X3, m + "fvae.g_pre_net.0", 1, 4, 2);
     // g_pre_net = Conv1d(k = 8, stride 4, pad 2) as a STRIDE-1, 3-tap convolution over 4-frame groups: [B][T][C] is also [B][T/4][4C]
     // (T is a multiple of frames_multiple = 4), out[q] = sum_j W_j x[4q + j - 2] reads group q - 1 (frames 2, 3), q (all four) and q + 1
@@ -323,7 +308,7 @@ int build_acoustic(dtts_ctx* h) {
         if (ok && fuse_flows) fuse_flows = flowstack_block(h, need, p, rev, -1.f, fs_host, fs_cond_w, fs_cond_b);
     }
     if (ok && parity != 0)
-        return fail(h, DTTS_E_INVAL, "prior_glow_n_blocks %d: an odd number of flow blocks is not supported", c.prior_glow_n_blocks);
+        return (*rc = fail(h, DTTS_E_INVAL, "prior_glow_n_blocks %d: an odd number of flow blocks is not supported", c.prior_glow_n_blocks)), false;
     h->fs_w = nullptr;
     if (ok && fuse_flows && !h->flows.empty()) {
         h->fs_w = upload(h, fs_host);
@@ -339,6 +324,43 @@ int build_acoustic(dtts_ctx* h) {
     const int dec_eng = (c.fvae_enc_dec_hidden % 64 == 0 && !c.decoder_fp32) ? ENG_BF16X3 : ENG_F32;
     ok = ok && build_wn(h, need, h->dec_wn, m + "fvae.decoder.wn", c.fvae_enc_dec_hidden, c.fvae_kernel_size, c.fvae_dec_n_layers, dec_eng);
     ok = ok && pack_plain(h, need, h->dec_out, ENG_F32, m + "fvae.decoder.out_proj", 1, 1, 0);
+    return ok;
+}
+
+int build_acoustic(dtts_ctx* h) {
+    if (h->ps_ready)   // the two acoustic models share the duration predictor's and the FVAE's packs: a context holds one of them
+        return fail(h, DTTS_E_STATE, "dtts_finalize_weights(DTTS_PART_ACOUSTIC): this context holds the PortaSpeech baseline (DTTS_PART_PORTASPEECH); "
+                    "a context holds one acoustic model");
+    Need need{h, ""};
+    const dtts_config& c = h->cfg;
+    const std::string m = "model.";
+    const std::string enc = m + "dict_encoder.S2PA_module";
+    bool ok = true;
+    h->word_emb = upload_named(h, need, enc + ".word_emb.weight");
+    const std::string att = enc + ".s2pa_attention";
+    h->pinyin_emb = upload_named(h, need, att + ".pinyin_embedding.weight");
+    ok = ok && h->word_emb && h->pinyin_emb;
+    ok = ok && build_encoder(h, need, h->sem, enc + ".semantic_encoder");
+    ok = ok && build_encoder(h, need, h->lin, enc + ".linguistic_encoder");
+    // S2PA projections (no bias).  k_transform is applied TRANSPOSED to the query (see ops.h)
+    const HostTensor *wq = need.get(att + ".q_transform.weight"), *wk = need.get(att + ".k_transform.weight"),
+                     *wv = need.get(att + ".v_transform.weight"), *wo = need.get(att + ".output_transform.weight");
+    if (ok && wq && wk && wv && wo) {
+        const int H = c.hidden_size, D = c.gloss_dim;
+        const float *pq = wq->f.data(), *pk = wk->f.data(), *pv = wv->f.data(), *po = wo->f.data();
+        ok = ok && pack_conv(h, h->s2_q, ENG_F32, H, H, 1, [=](int co, int ci, int) { return pq[(size_t)co * H + ci]; }, {}, 1, 1, 0);
+        ok = ok && pack_conv(h, h->s2_kT, ENG_F32, D, H, 1, [=](int co, int ci, int) { return pk[(size_t)ci * D + co]; }, {}, 1, 1, 0);
+        ok = ok && pack_conv(h, h->s2_k, ENG_F32, H, D, 1, [=](int co, int ci, int) { return pk[(size_t)co * D + ci]; }, {}, 1, 1, 0);
+        ok = ok && pack_conv(h, h->s2_v, ENG_F32, H, D, 1, [=](int co, int ci, int) { return pv[(size_t)co * D + ci]; }, {}, 1, 1, 0);
+        ok = ok && pack_conv(h, h->s2_o, ENG_F32, H, H, 1, [=](int co, int ci, int) { return po[(size_t)co * H + ci]; }, {}, 1, 1, 0);
+    } else
+        ok = false;
+    ok = ok && build_dur_predictor(h, need, m);
+    if (ok) {
+        int rc = DTTS_OK;
+        ok = build_fvae(h, need, m, &rc);
+        if (rc) return rc;
+    }
     if (ok) {
         const int rc = build_speaker(h);
         if (rc) return rc;

@@ -131,11 +131,33 @@ def speaker_kind(hp):
     return "id" if hp.get("use_spk_id") else "embed"   # use_spk_id wins (modules/portaspeech/model.py:160-163, tasks/tts/dict_tts.py:182)
 
 
-def fill_abi_config(cfg, hp=None, voc=None, n_phone=None, vocoder_precision=None):
-    """copy reference hparams into a DttsConfig (abi.DttsConfig); unsupported settings fail loudly"""
+# what the PortaSpeech baseline (modules/portaspeech/model.py::PortaSpeech) reads beyond BIAOBEI_DEFAULTS, with the values of
+# egs/egs_bases/tts/ps.yaml; window_size is TextEncoder's default (model.py:79), not an hparam of the reference
+PORTASPEECH_DEFAULTS = {"enc_layers": 4, "word_enc_layers": 4, "ps_window_size": 4}
+
+
+def is_baseline(hp):
+    """True when the hparams' task is the PortaSpeech baseline (``task_cls: tasks.tts.ps_adv.PortaSpeechAdvTask`` / ``tasks.tts.ps.*``),
+    False for the Dict-TTS task or when no task is named"""
+    task = str((hp or {}).get("task_cls", ""))
+    return task.startswith(("tasks.tts.ps_adv.", "tasks.tts.ps.", "tasks.tts.ps_flow."))
+
+
+def fill_abi_config(cfg, hp=None, voc=None, n_phone=None, vocoder_precision=None, baseline=False):
+    """copy reference hparams into a DttsConfig (abi.DttsConfig); unsupported settings fail loudly.  baseline: the config of the
+    PortaSpeech baseline (dict_tts_amd.model.PortaSpeech), which also reads enc_layers and refuses what that class does not run"""
     hp = {**BIAOBEI_DEFAULTS, **(hp or {})}
     if hp.get("use_post_glow"):
         raise NotImplementedError("use_post_glow=True is outside the Dict-TTS path (egs/egs_bases/tts/dict_tts.yaml:4)")
+    if baseline:
+        hp = {**PORTASPEECH_DEFAULTS, **hp}
+        if hp.get("use_spk_embed") or hp.get("use_spk_id"):
+            which = "use_spk_id" if hp.get("use_spk_id") else "use_spk_embed"
+            raise NotImplementedError(f"{which}=True: speakers are not implemented for the PortaSpeech baseline (they are added to ph_encoder_out "
+                                      f"including its padded rows, which changes what the duration predictor sees as padding)")
+        if hp.get("dur_level", "word") != "word":
+            raise NotImplementedError(f"dur_level={hp.get('dur_level')!r}: the PortaSpeech baseline is implemented for dur_level: word only")
+        cfg.enc_layers = int(hp["enc_layers"])
     speaker_kind(hp)   # use_spk_embed / use_spk_id need num_spk > 1; nothing of it goes into the config struct (the weights carry the form)
     if not hp.get("use_prior_glow", True) or hp.get("dur_scale", "log") != "log":
         raise NotImplementedError("only use_prior_glow=True / dur_scale=log are implemented")

@@ -38,7 +38,8 @@ def wav_to_int16(wav, norm=False):
 
 def infer_batch(model, vocoder, batch, z_p=None, denoise_c=0.0):
     """batch: dict of tensors as DictTTSDataset.collater produces (word_tokens, keys, values, key_map, pinyin,
-    pinyin_map, pron_modified).  Returns (outputs dict, list of float32 waveforms, one per utterance).
+    pinyin_map, pron_modified), or a batch of the PortaSpeech baseline (txt_tokens, ph2word, word_lengths) for
+    dict_tts_amd.model.PortaSpeech.  Returns (outputs dict, list of float32 waveforms, one per utterance).
     denoise_c > 0: the vocoder's spectral-subtraction filter at that strength (``run_inference``)."""
     out = _model_forward(model, batch, z_p)
     lens = out["mel_lens"]
@@ -51,8 +52,17 @@ def infer_batch(model, vocoder, batch, z_p=None, denoise_c=0.0):
     return out, [wav_h[i, : lens_h[i] * hop] for i in range(len(lens_h))]
 
 
+def is_baseline_batch(batch):
+    """a batch of the PortaSpeech baseline (tasks/tts/ps_adv.py: txt_tokens, ph2word, word_lengths; no dictionary tensors)"""
+    return "word_tokens" not in batch and "ph2word" in batch
+
+
 def _model_forward(model, batch, z_p):
     kw = {}
+    if is_baseline_batch(batch):   # PortaSpeech.forward(txt_tokens, ph2word, word_len, infer=True): tasks/tts/ps.py run_model
+        word_len = batch["word_lengths"] if "word_lengths" in batch else torch.as_tensor(batch["ph2word"]).max(1)[0]
+        return model(batch["txt_tokens"], batch["ph2word"], torch.as_tensor(word_len).max(), mel2word=batch.get("mel2word_forced"), infer=True,
+                     z_p=z_p)
     if "spk_embed" in batch or "spk_ids" in batch:   # multi-speaker batches: tasks/tts/dict_tts.py:182
         hp = getattr(model, "hparams", None) or hparams_mod.hparams
         kw["spk_embed"] = batch.get("spk_ids") if hp.get("use_spk_id") else batch.get("spk_embed")
@@ -133,11 +143,14 @@ def run_inference(model, vocoder, batches, gen_dir, pinyin_encoder, sample_rate=
     if pipeline is None:
         pipeline = hasattr(model, "ctx") and hasattr(vocoder, "ctx")
     for batch, out, wavs in _iter_results(model, vocoder, batches, pipeline, out_wav_norm, denoise_c):
-        pron_attn = out["pron_attn"].cpu()
+        baseline = is_baseline_batch(batch)   # the baseline predicts no pronunciations: its pinyin_tokens column stays empty
+        pron_attn = None if baseline else out["pron_attn"].cpu()
         for i, wav in enumerate(wavs):
             item_name, text = batch["item_name"][i], batch["text"][i]
-            n_words = int((batch["word_tokens"][i] > 0).sum())
-            ids = decode_pinyin_ids(pron_attn[i, :n_words], torch.as_tensor(batch["pinyin"][i][:n_words]))
+            ids = []
+            if not baseline:
+                n_words = int((batch["word_tokens"][i] > 0).sum())
+                ids = decode_pinyin_ids(pron_attn[i, :n_words], torch.as_tensor(batch["pinyin"][i][:n_words]))
             base_fn = base_filename(results_id, item_name, text)
             if save_wavs:
                 pcm = wav if wav.dtype == np.int16 else wav_to_int16(wav, out_wav_norm)   # int16: converted on the device

@@ -244,6 +244,111 @@ class PortaSpeech_dict(torch.nn.Module):
         return ret
 
 
+# state-dict groups of a baseline checkpoint that the PortaSpeech class accepts and does not upload
+PS_UNUSED_PREFIXES = ("post_flow.", "g_proj.", "sin_pos.", "spk_embed_proj.")
+PS_USED_PREFIXES = ("ph_encoder.", "word_encoder.", "enc_pos_proj.", "dec_query_proj.", "dec_res_proj.", "attn.", "dur_predictor.", "fvae.")
+
+
+class PortaSpeech(torch.nn.Module):
+    """Drop-in for the reference's phoneme-input baseline ``modules.portaspeech.model.PortaSpeech`` at inference (model.py:133-367;
+    ``task_cls: tasks.tts.ps_adv.PortaSpeechAdvTask``, ``dur_level: word``, ``use_post_glow: false``): the same ``forward`` signature and
+    return keys, ``load_state_dict`` with the reference's key names, every tensor op executed by libdicttts_hip.so
+    (dtts_text2mel_fetch(DTTS_PS_ENCODE) + dtts_text2mel_decode).  Extra keyword ``z_p`` ([B, latent, T_mel/4]): the prior sample, drawn as
+    the reference draws it when omitted.  Refused by name: ``infer=False`` (the baseline's posterior pass is not implemented),
+    ``dur_level: ph``, ``use_post_glow``, ``use_spk_embed`` / ``use_spk_id``.  ``ret['attn']`` rows of frames with mel2word = 0 are zeros
+    (the reference leaves meaningless softmax rows there; they never reach decoder_inp)."""
+
+    def __init__(self, dictionary=None, out_dims=None, hparams=None, ctx=None):
+        super().__init__()
+        if not torch.cuda.is_available():
+            raise abi.DttsError("dict_tts_amd.model.PortaSpeech needs a ROCm GPU: the HIP path has no CPU fallback")
+        if hparams is None:
+            if not hparams_mod.hparams:
+                raise RuntimeError("PortaSpeech(hparams=None) needs the global hparams: call dict_tts_amd.hparams.set_hparams(...) "
+                                   "or alias the reference's (INTEGRATION.md), or pass hparams={} for the ps_adv.yaml defaults")
+            hparams = hparams_mod.hparams
+        hp = {**hparams_mod.PORTASPEECH_DEFAULTS, **dict(hparams)}
+        self.hparams = hp
+        if out_dims is not None and int(out_dims) != int(hp.get("audio_num_mel_bins", 80)):
+            raise NotImplementedError(f"out_dims={out_dims} differs from audio_num_mel_bins={hp.get('audio_num_mel_bins', 80)}")
+        n_phone = len(dictionary) if dictionary is not None else hp.get("ps_n_phone")
+        if n_phone is None:
+            raise ValueError("PortaSpeech needs the phoneme dictionary (its length gives the rows of ph_encoder.emb)")
+        if ctx is None:
+            ctx = abi.Context(fill_abi_config(abi.default_config(), hp, None, n_phone=n_phone, baseline=True))
+        self.ctx = ctx
+        self.cfg = ctx.cfg
+        self._state = {}
+        self._ready = False
+        self.device = torch.device("cuda", torch.cuda.current_device())
+
+    def load_state_dict(self, state_dict, strict=True):
+        unexpected = [k for k in state_dict if not k.startswith(PS_USED_PREFIXES + PS_UNUSED_PREFIXES)]
+        if strict and unexpected:
+            raise RuntimeError(f"Unexpected key(s) in state_dict: {unexpected[:5]}")
+        used = {k: v for k, v in state_dict.items() if k.startswith(PS_USED_PREFIXES) and not k.endswith("embed_positions._float_tensor")}
+        from .fft import DEFAULT_MAX_TARGET_POSITIONS, sinusoid_table
+        H = self.cfg.hidden_size
+        used["config"] = np.array([self.hparams["ps_window_size"], self.hparams["word_enc_layers"]], np.float32)
+        used["word_encoder.pos_table"] = sinusoid_table(DEFAULT_MAX_TARGET_POSITIONS, H, 0)   # SinusoidalPositionalEmbedding.weights
+        self._state = dict(state_dict)
+        self.ctx.load_state_dict("ps", used)
+        try:
+            self.ctx.finalize(abi.PART_PORTASPEECH)   # names the first missing tensor (strict)
+        except abi.DttsError as e:
+            raise RuntimeError(f"Error(s) in loading state_dict for PortaSpeech: {e}") from e
+        self._ready = True
+        return torch.nn.modules.module._IncompatibleKeys([], [])
+
+    def state_dict(self, *args, **kwargs):
+        return dict(self._state)
+
+    def forward(self, txt_tokens, ph2word, word_len, mel2word=None, mel2ph=None, spk_embed=None, infer=False, tgt_mels=None,
+                forward_post_glow=True, two_stage=True, z_p=None):
+        if not infer:
+            raise NotImplementedError("PortaSpeech.forward(infer=False): the posterior pass of the baseline is not implemented on the MI355X "
+                                      "path; only inference (infer=True) is")
+        if not self._ready:
+            raise RuntimeError("load_state_dict() must be called first")
+        dev = self.device
+        i64 = lambda t: None if t is None else torch.as_tensor(t).to(device=dev, dtype=torch.int64).contiguous()
+        txt_tokens, ph2word, mel2word = i64(txt_tokens), i64(ph2word), i64(mel2word)
+        B, T_ph = txt_tokens.shape
+        if tuple(ph2word.shape) != (B, T_ph):
+            raise ValueError(f"ph2word must be [B, T_ph] = {(B, T_ph)}, got {tuple(ph2word.shape)}")
+        T_w = int(torch.as_tensor(word_len).max())     # the reference: torch.arange(word_len) / word_len.max() + 1 (model.py:240,316)
+        stream = torch.cuda.current_stream().cuda_stream
+        status = torch.zeros(4, dtype=torch.int64, device=dev)
+        T_mel = self.ctx.ps_encode(B, T_ph, T_w, txt_tokens.data_ptr(), ph2word.data_ptr(), status.data_ptr(), stream,
+                                   mel2word=(mel2word.data_ptr(), mel2word.shape[1]) if mel2word is not None else None, want_attn=True)
+        bad = abi.ps_status_error(status.cpu().tolist())   # (the frames' checks, and all of them with a teacher-forced mel2word)
+        if bad:
+            raise abi.DttsError(f"dtts_text2mel_fetch(DTTS_PS_ENCODE): {bad}")
+        H, Z, n_mel = self.cfg.hidden_size, self.cfg.latent_size, self.cfg.audio_num_mel_bins
+        if z_p is None:
+            z_p = torch.distributions.Normal(0, 1).sample([B, Z, T_mel // 4])   # fvae.py: prior_dist.sample
+        z_p = z_p.to(device=dev, dtype=torch.float32).contiguous()
+        assert tuple(z_p.shape) == (B, Z, T_mel // 4), (tuple(z_p.shape), (B, Z, T_mel // 4))
+        mel = torch.empty(B, T_mel, n_mel, dtype=torch.float32, device=dev)
+        self.ctx.text2mel_decode(z_p.data_ptr(), mel.data_ptr(), stream)
+        out = lambda shape, dt=torch.float32: torch.empty(*shape, dtype=dt, device=dev)
+        ret = {"ph_encoder_out": out((B, T_ph, H)), "dur": out((B, T_w)), "attn": out((B, T_mel, T_ph)), "word_encoder_out": out((B, T_w, H)),
+               "x_mask": out((B, T_mel, 1)), "decoder_inp": out((B, T_mel, H)), "mel2word": out((B, T_mel), torch.int64),
+               "mel_lens": out((B,), torch.int32)}
+        for key, what in (("ph_encoder_out", abi.PS_PH_ENCODER_OUT), ("dur", abi.OUT_DUR), ("attn", abi.PS_ATTN),
+                          ("word_encoder_out", abi.OUT_WORD_ENCODER_OUT), ("x_mask", abi.OUT_X_MASK), ("decoder_inp", abi.PS_DECODER_INP),
+                          ("mel2word", abi.OUT_MEL2WORD), ("mel_lens", abi.OUT_MEL_LENS)):
+            self.ctx.fetch(what, ret[key].data_ptr(), stream)
+        ret["mel_out"] = ret["mel_out_fvae"] = mel
+        ret["z_p_in"] = z_p
+        return ret
+
+
+def model_cls(hp):
+    """the acoustic model class of the hparams' task: PortaSpeech for ``task_cls: tasks.tts.ps_adv.*`` (the baseline), else PortaSpeech_dict"""
+    return PortaSpeech if hparams_mod.is_baseline(hp) else PortaSpeech_dict
+
+
 def decode_pinyin_ids(pron_attn, pinyin):
     """after_infer's pinyin decode for ONE utterance (tasks/tts/dict_tts.py:294-304): pron_attn [T_w,P],
     pinyin [T_w,P] -> list of pinyin-token ids, two per inner word"""

@@ -552,3 +552,106 @@ def make_id_batch(sentences, table, pron_every=7):
     entry[:, 0] = -1
     entry[:, -1] = -1
     return {"word_tokens": word_tokens, "entry_ids": entry, "pron_modified": pron_modified, "L_k": L_k, "P": P}
+
+
+# ----------------------------------------------------------------------------------------------------------
+# the PortaSpeech baseline (modules/portaspeech/model.py::PortaSpeech, dur_level: word)
+# ----------------------------------------------------------------------------------------------------------
+PS_N_PHONE = 64      # rows of the phoneme embedding (len(dictionary)); row 0 is padding
+PS_WINDOW = 4        # TextEncoder's window_size (model.py:79)
+
+
+def portaspeech_state_dict(seed=1234, n_phone=PS_N_PHONE, acoustic=None, word_enc_layers=4, enc_layers=4, window=PS_WINDOW):
+    """numpy state dict with the key names / shapes of the baseline's ``state_dict['model']``.  acoustic: ACOUSTIC_SHAPE keys, as for
+    dict_tts_state_dict.  The prenet's ``proj`` is NON-zero (the reference initialises it to zero, which would hide the prenet), and the
+    duration head is scaled so that a word of 1 .. 3 phonemes gets roughly 0 .. 30 frames (the per-phoneme durations are summed per word
+    BEFORE exp(.) - 1)."""
+    sh = acoustic_shape(acoustic)
+    sd = {}
+    h, heads = sh["hidden_size"], sh["num_heads"]
+    Hd, Z, Hf = sh["fvae_enc_dec_hidden"], sh["latent_size"], sh["prior_glow_hidden"]
+    p = "ph_encoder"
+    sd[p + ".emb.weight"] = randn(seed, "ps.emb", (n_phone, h), h ** -0.5)
+    sd[p + ".emb.weight"][0] = 0
+    for i in range(3):
+        _conv(sd, seed, f"{p}.pre.conv_layers.{i}", h, h, 5, gain=1.2)
+        _ln(sd, seed, f"{p}.pre.norm_layers.{i}", h)
+    _conv(sd, seed, f"{p}.pre.proj", h, h, 1, gain=0.5)
+    dk = h // heads
+    for i in range(enc_layers):
+        for n in "qkvo":
+            _conv(sd, seed, f"{p}.encoder.attn_layers.{i}.conv_{n}", h, h, 1, gain=1.0 if n in "qk" else 0.7)
+        sd[f"{p}.encoder.attn_layers.{i}.emb_rel_k"] = randn(seed, f"ps.rel_k.{i}", (1, 2 * window + 1, dk), 2.0 * dk ** -0.5)
+        sd[f"{p}.encoder.attn_layers.{i}.emb_rel_v"] = randn(seed, f"ps.rel_v.{i}", (1, 2 * window + 1, dk), 2.0 * dk ** -0.5)
+        _ln(sd, seed, f"{p}.encoder.norm_layers_1.{i}", h)
+        _conv(sd, seed, f"{p}.encoder.ffn_layers.{i}.conv_1", 4 * h, h, sh["enc_ffn_kernel_size"], gain=1.2)
+        _conv(sd, seed, f"{p}.encoder.ffn_layers.{i}.conv_2", h, 4 * h, 1, gain=0.7)
+        _ln(sd, seed, f"{p}.encoder.norm_layers_2.{i}", h)
+    for k, v in fft_blocks_state_dict(seed + 1, hidden=h, layers=word_enc_layers, kernel_size=1).items():
+        sd["word_encoder." + k] = v
+    for n in ("enc_pos_proj", "dec_query_proj", "dec_res_proj"):
+        _linear(sd, seed, "ps." + n, h, 2 * h, gain=1.4, bias=0.02)
+        sd[n + ".weight"], sd[n + ".bias"] = sd.pop(f"ps.{n}.weight"), sd.pop(f"ps.{n}.bias")
+    sd["attn.in_proj_weight"] = randn(seed, "ps.attn.in_proj_weight", (3 * h, h), 2.0 * h ** -0.5)
+    sd["attn.out_proj.weight"] = randn(seed, "ps.attn.out_proj", (h, h), h ** -0.5)
+    for i in range(sh["dur_predictor_layers"]):
+        _conv(sd, seed, f"dur_predictor.conv.{i}.1", 128, h if i == 0 else 128, sh["dur_predictor_kernel"], gain=1.3)
+        _ln(sd, seed, f"dur_predictor.conv.{i}.3", 128, "weight", "bias")
+    sd["dur_predictor.linear.0.weight"] = randn(seed, "ps.dur.lin.w", (1, 128), 0.5 / np.sqrt(128))
+    sd["dur_predictor.linear.0.bias"] = np.array([0.35], np.float32)   # softplus ~ 0.9 per phoneme: exp(0.9 n) - 1 frames for n phonemes
+    _conv(sd, seed, "fvae.g_pre_net.0", h, h, 8, gain=1.0)
+    _conv(sd, seed, "fvae.encoder.pre_net.0", Hd, N_MEL, 8)
+    _wn(sd, seed, "fvae.encoder.wn", Hd, sh["fvae_kernel_size"], sh["fvae_enc_n_layers"], h)
+    _conv(sd, seed, "fvae.encoder.out_proj", 2 * Z, Hd, 1)
+    for f in range(0, 2 * sh["prior_glow_n_blocks"], 2):
+        q = f"fvae.prior_flow.flows.{f}"
+        _conv(sd, seed, q + ".pre", Hf, Z // 2, 1, gain=1.0)
+        _wn(sd, seed, q + ".enc", Hf, sh["glow_kernel_size"], 4, h)
+        _conv(sd, seed, q + ".post", Z // 2, Hf, 1, gain=0.5)
+    _conv(sd, seed, "fvae.decoder.pre_net.0", Hd, Z, 4, gain=1.0, transposed=True)
+    _wn(sd, seed, "fvae.decoder.wn", Hd, sh["fvae_kernel_size"], sh["fvae_dec_n_layers"], h)
+    _conv(sd, seed, "fvae.decoder.out_proj", N_MEL, Hd, 1, gain=1.5)
+    sd["fvae.decoder.out_proj.bias"] = (sd["fvae.decoder.out_proj.bias"] - 2.5).astype(np.float32)
+    return sd
+
+
+def portaspeech_batch(words, seed=1234, n_phone=PS_N_PHONE, T_ph=None, T_w=None):
+    """words: per utterance the list of phonemes per word (each >= 1), e.g. [[2, 1, 3], [1]] -> the collated inputs of the baseline:
+    txt_tokens [B, T_ph] i64 in [1, n_phone) (0 = padding), ph2word [B, T_ph] i64 (1-based, 0 = padding), word_len [B] i64.
+    T_ph / T_w: pad the phoneme axis / report a wider word axis (the same utterance inside a wider batch)."""
+    B = len(words)
+    n_ph = [int(sum(w)) for w in words]
+    T_ph = max(n_ph) if T_ph is None else int(T_ph)
+    assert T_ph >= max(n_ph) and all(min(w) >= 1 for w in words)
+    txt = np.zeros((B, T_ph), np.int64)
+    ph2word = np.zeros((B, T_ph), np.int64)
+    for b, w in enumerate(words):
+        txt[b, :n_ph[b]] = _rng(seed, f"ps.tokens.{b}.{n_ph[b]}").integers(1, n_phone, size=n_ph[b])
+        ph2word[b, :n_ph[b]] = np.repeat(np.arange(1, len(w) + 1), w)
+    word_len = np.array([len(w) for w in words], np.int64)
+    assert T_w is None or T_w >= word_len.max()
+    return {"txt_tokens": txt, "ph2word": ph2word, "word_len": word_len, "T_w": int(word_len.max() if T_w is None else T_w)}
+
+
+def portaspeech_words(first=0, count=60, seed=1234, max_ph=3):
+    """phonemes per word for ``count`` Biaobei sentences from ``first``: every word (BOS / EOS included) gets 1 .. max_ph phonemes, seeded"""
+    st = biaobei_struct()
+    out = []
+    for i, s in enumerate(st["sentences"][first:first + count]):
+        out.append(_rng(seed, f"ps.words.{first + i}").integers(1, max_ph + 1, size=len(s) + 2).tolist())
+    return out
+
+
+def ps_spread_mel2word(words, frames):
+    """teacher-forced mel2word giving utterance b exactly frames[b] frames spread as evenly as possible over its words (the first words
+    take the remainder; frames[b] < its word count leaves the last words without frames): [B, max(frames)] int64, 0 = padding"""
+    rows = []
+    for w, n_f in zip(words, frames):
+        n = len(w)
+        d = np.full(n, n_f // n)
+        d[:n_f % n] += 1
+        rows.append(np.repeat(np.arange(1, n + 1), d))
+    out = np.zeros((len(rows), max(len(r) for r in rows)), np.int64)
+    for b, r in enumerate(rows):
+        out[b, :len(r)] = r
+    return out

@@ -230,6 +230,17 @@ DTTS_API int dtts_load_weight(dtts_handle h, const char* name, const void* host_
  * another width than 64, a word-embedding width (embedding_size) other than the hidden size, rotary_value = 1, hidden_act != 0, a tensor
  * of another shape, and a tensor that a loaded layer lacks; DTTS_E_NOENT: no config / embeddings at all.  Built once per context. */
 #define DTTS_PART_GLOSS 1024
+/* The PortaSpeech baseline (DTTS_PS_ENCODE below; modules/portaspeech/model.py::PortaSpeech with dur_level: word, use_post_glow: false, no
+ * speakers): "ps.<state-dict key>" for ph_encoder.* (emb, pre.*, encoder.* with emb_rel_k / emb_rel_v [1][2 w + 1][hidden / heads]),
+ * word_encoder.* (FFTBlocks, FFN kernel 1), enc_pos_proj.*, dec_query_proj.*, dec_res_proj.*, attn.in_proj_weight, attn.out_proj.weight,
+ * dur_predictor.* and fvae.* (weight norm folded here as for DTTS_PART_ACOUSTIC), and two tensors that are no state-dict keys:
+ *   "ps.config" [2]: window_size (1 .. 8), word_enc_layers (1 .. 64);
+ *   "ps.word_encoder.pos_table" [n_pos][hidden]: SinusoidalPositionalEmbedding.weights of the word encoder (row 0 = padding); an encode
+ *   needs n_pos > T_w.
+ * The encoder depth, widths and kernels come from these fields of dtts_config: enc_layers, hidden_size, num_heads, enc_ffn_kernel_size,
+ * n_phone, dur_* and the FVAE fields.  DTTS_E_NOENT names the first missing tensor, DTTS_E_INVAL a tensor of another shape.  A context holds EITHER the Dict-TTS
+ * acoustic part or this one: finalising the second is refused with DTTS_E_STATE.  Built once per context. */
+#define DTTS_PART_PORTASPEECH 2048
 /* Fold, repack into MFMA fragment order and upload.  Fails with DTTS_E_NOENT naming the first missing tensor. */
 DTTS_API int dtts_finalize_weights(dtts_handle h, int parts);
 
@@ -1057,6 +1068,59 @@ typedef struct dtts_gloss_args {
     float* out_dev;               /* [sum_L][hidden] */
     int64_t* status_dev;          /* [2] */
 } dtts_gloss_args;
+
+/*
+ * The PortaSpeech baseline's encode — dtts_text2mel_fetch(h, DTTS_PS_ENCODE, (dtts_ps_args*), stream), args->size = sizeof(*args): replaces
+ * PortaSpeech.run_text_encoder (modules/portaspeech/model.py:239-288) with the part of dtts_finalize_weights(DTTS_PART_PORTASPEECH):
+ *   phoneme TextEncoder (embedding * sqrt(hidden), ConvReluNorm prenet, post-LN relative-position Transformer) -> ph_encoder_out;
+ *   phoneme -> word mean pooling, the word encoder (FFTBlocks), the duration predictor on ph_encoder_out and the per-word duration sums;
+ *   length regulation (or the teacher-forced mel2word), padded to frames_multiple by repeating the last column;
+ *   the single-head attention of every mel frame over the phonemes of its own word -> decoder_inp [B][T_mel][hidden].
+ * It leaves the context encoded exactly as dtts_text2mel_encode does, with decoder_inp as the FVAE's condition: dtts_text2mel_decode,
+ * DTTS_OUT_DUR / _MEL2WORD / _X_MASK / _MEL_LENS / _WORD_ENCODER_OUT and the three copy items below work afterwards; the Dict-TTS-only items
+ * (DTTS_OUT_PRON_ATTN, _DICT_ATTN, _CONTEXT, _POSTERIOR) answer DTTS_E_STATE.  One stream synchronisation when mel2word_dev is NULL, none
+ * otherwise.
+ * Inputs: txt_tokens [B][T_ph] i64 (0 = padding, a suffix), ph2word [B][T_ph] i64 (1-based word of a phoneme: over the live prefix it
+ * starts at 0 or 1 and grows by 0 or 1 per phoneme, so a word is a span and no word in front of the last one is empty — stricter than the
+ * reference, which pools an empty word into a zero row: such a row inside an utterance would break the suffix padding the word encoder
+ * derives from all-zero rows; 0 past the live prefix), mel2word [B][T_m2w] i64 or NULL (non-decreasing over its non-zero prefix, 0 behind it).
+ * status_dev i64 [4], written by every call: {0, 0, 0, 0}, or {first offending utterance + 1, code, value, position} with code
+ *   DTTS_PS_BAD_TOKEN     a token outside [0, n_phone);
+ *   DTTS_PS_ZERO_TOKEN    a zero token inside the live prefix (the prefix mask and txt_tokens > 0 would differ);
+ *   DTTS_PS_BAD_PH2WORD   a ph2word that, inside the live prefix, decreases, skips a word (a step > 1, or a first value > 1) or exceeds
+ *                         T_w; that is negative; or that is non-zero past the prefix;
+ *   DTTS_PS_EMPTY_WORD    a live frame whose word has no phonemes (the reference's fp32 sum q.k - 1e9 makes that row a batch-dependent
+ *                         uniform average: refused by name, not imitated);
+ *   DTTS_PS_BAD_MEL2WORD  a mel2word outside [0, T_w] or not of the form above.
+ * The first three are checked at the call's synchronisation (DTTS_E_INVAL naming them); without one (mel2word given), and for the last
+ * two, the caller reads status_dev after the call.  Nothing is read or written out of range for any such input.
+ * Deviation: attn rows of frames with mel2word = 0 are written as zeros; the reference leaves meaningless softmax rows there, which never
+ * reach decoder_inp.
+ * DTTS_E_INVAL, checked before the handle: a wrong size, B / T_ph / T_w < 1, T_m2w < 0 or mel2word without T_m2w, a NULL txt_tokens /
+ * ph2word / status_dev / T_mel_host, a misaligned pointer.  DTTS_E_STATE before dtts_finalize_weights(DTTS_PART_PORTASPEECH).
+ * The copy items (dst = a device buffer, after a DTTS_PS_ENCODE): DTTS_PS_PH_ENCODER_OUT f32 [B][T_ph][hidden], DTTS_PS_ATTN f32
+ * [B][T_mel][T_ph] (needs want_attn), DTTS_PS_DECODER_INP f32 [B][T_mel][hidden].
+ */
+#define DTTS_PS_ENCODE 65
+#define DTTS_PS_PH_ENCODER_OUT 66
+#define DTTS_PS_ATTN 67
+#define DTTS_PS_DECODER_INP 68
+#define DTTS_PS_BAD_TOKEN 1
+#define DTTS_PS_ZERO_TOKEN 2
+#define DTTS_PS_BAD_PH2WORD 3
+#define DTTS_PS_EMPTY_WORD 4
+#define DTTS_PS_BAD_MEL2WORD 5
+typedef struct dtts_ps_args {
+    int32_t size;                 /* sizeof(dtts_ps_args) */
+    int32_t B, T_ph, T_w;
+    int32_t T_m2w;                /* columns of mel2word_dev, or 0 */
+    int32_t want_attn;            /* != 0: keep the attention weights for DTTS_PS_ATTN */
+    const int64_t* txt_tokens_dev;
+    const int64_t* ph2word_dev;
+    const int64_t* mel2word_dev;  /* or NULL: predicted durations */
+    int64_t* status_dev;          /* [4] */
+    int32_t* T_mel_host;          /* out: frames per utterance, padded to frames_multiple */
+} dtts_ps_args;
 
 /*
  * Output side — replaces the sample conversion of save_wav (utils/audio.py:11-16; called from after_infer,
