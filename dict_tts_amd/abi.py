@@ -79,10 +79,13 @@ PS_STATUS_NAMES = {PS_BAD_TOKEN: "DTTS_PS_BAD_TOKEN: a token outside [0, n_phone
                    PS_BAD_PH2WORD: "DTTS_PS_BAD_PH2WORD: ph2word must start at 0 or 1, grow by 0 or 1 per live phoneme up to T_w, and be 0 past the live prefix",
                    PS_EMPTY_WORD: "DTTS_PS_EMPTY_WORD: a live frame whose word has no phonemes",
                    PS_BAD_MEL2WORD: "DTTS_PS_BAD_MEL2WORD: mel2word must lie in [0, T_w], be non-decreasing over its non-zero prefix and 0 behind it"}
+DICT_EDIT, DICT_ENTRY = 69, 70   # DTTS_DICT_EDIT / DTTS_DICT_ENTRY: replace / append entries of the resident table, read one back (not OUT_ items)
+MAX_SENSES = 15                  # DTTS_MAX_SENSES
 SPECTRAL_FORWARD, SPECTRAL_INVERSE = 1, 2  # dtts_spectral_args.mode bits; both = the reference's denoise
 SPK_EMBED, SPK_ID = 1, 2   # dtts_text2mel_speakers kinds: fp32 [B,256] (use_spk_embed) / int64 [B] (use_spk_id)
 TIMER_VOC_CONV, TIMER_S2PA = 1, 2
 TIMER_STAGE_ENCODER, TIMER_STAGE_DICT_ENCODER, TIMER_STAGE_FVAE, TIMER_STAGE_HIFIGAN = 3, 4, 5, 6   # the reference's profile_infer names
+TIMER_DICT_SEG_COPY = 7   # DTTS_TIMER_DICT_SEG_COPY: the K array's segment-copy launch of every DICT_EDIT
 
 OUT_NAMES = {v: "DTTS_" + k for k, v in list(globals().items()) if k.startswith("OUT_")}   # code -> "DTTS_OUT_X", as the library's messages spell it
 
@@ -288,6 +291,30 @@ def ps_args(B, T_ph, T_w, txt_tokens, ph2word, status, T_mel, mel2word=None, T_m
                   mel2word or None, status or None, C.pointer(T_mel) if T_mel is not None else None)
 
 
+class DictEditArgs(C.Structure):
+    """dtts_dict_edit_args (include/dicttts_hip.h): the argument block of dtts_text2mel_fetch(DTTS_DICT_EDIT)"""
+    _fields_ = [("size", C.c_int32), ("n_edit", C.c_int32), ("rows_on_device", C.c_int32), ("reserved", C.c_int32),
+                ("entry_id_host", C.c_void_p), ("tok_off_host", C.c_void_p), ("pin_off_host", C.c_void_p), ("key_map_host", C.c_void_p),
+                ("pinyin_host", C.c_void_p), ("pinyin_map_host", C.c_void_p), ("keys", C.c_void_p), ("values", C.c_void_p)]
+
+
+def dict_edit_args(n_edit, entry_id, tok_off, pin_off, key_map, pinyin, pinyin_map, keys, values=None, rows_on_device=False):
+    """a filled DictEditArgs block (pointers as integers, 0 / None = NULL; keys / values are device pointers iff rows_on_device)"""
+    return DictEditArgs(C.sizeof(DictEditArgs), int(n_edit), int(bool(rows_on_device)), 0, entry_id or None, tok_off or None, pin_off or None,
+                        key_map or None, pinyin or None, pinyin_map or None, keys or None, values or None)
+
+
+class DictEntryArgs(C.Structure):
+    """dtts_dict_entry_args (include/dicttts_hip.h): the argument block of dtts_text2mel_fetch(DTTS_DICT_ENTRY); n_entries, L_e, P_e are written"""
+    _fields_ = [("size", C.c_int32), ("entry", C.c_int32), ("n_entries", C.c_int32), ("L_e", C.c_int32), ("P_e", C.c_int32), ("reserved", C.c_int32),
+                ("k_dev", C.c_void_p), ("v_dev", C.c_void_p), ("key_map_dev", C.c_void_p), ("pinyin_dev", C.c_void_p), ("pinyin_map_dev", C.c_void_p)]
+
+
+def dict_entry_args(entry, k=None, v=None, key_map=None, pinyin=None, pinyin_map=None):
+    """a filled DictEntryArgs block (device pointers as integers, 0 / None = NULL)"""
+    return DictEntryArgs(C.sizeof(DictEntryArgs), int(entry), 0, 0, 0, 0, k or None, v or None, key_map or None, pinyin or None, pinyin_map or None)
+
+
 class DttsConfig(C.Structure):
     """struct dtts_config (include/dicttts_hip.h); field <- reference hparams key.
     resblock_dilation_sizes: one row per kernel size; three dilations >= 1 = ResBlock1, a row whose third entry is 0 = a two-dilation
@@ -451,6 +478,33 @@ class Context:
         p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
         self._chk(self.lib.dtts_dict_table_upload(self.h, len(tok_off) - 1, p(tok_off), p(keys), p(values), p(key_map),
                                                   p(pin_off), p(pinyin), p(pinyin_map)), "dtts_dict_table_upload")
+
+    def dict_table_edit(self, entry_id, tok_off, pin_off, key_map, pinyin, pinyin_map, keys, values, stream, rows_on_device=False):
+        """replace / append entries of the resident table (dtts_text2mel_fetch(DTTS_DICT_EDIT); an administrative call: synchronous, one device
+        synchronisation).  numpy arrays (host) for the edited entries only, laid out as dict_table_upload's: entry_id int32 [n] strictly
+        ascending (< n_entries replaces, n_entries .. appends), tok_off / pin_off int32 [n + 1], key_map f32 [sum_L], pinyin / pinyin_map int64
+        [sum_P].  keys / values: f32 [sum_L, gloss_dim] numpy arrays, or with rows_on_device DEVICE pointers (ints, 16-byte aligned) whose
+        producer was enqueued on ``stream``; values may be None = keys"""
+        c = lambda a, dt: np.ascontiguousarray(a, dtype=dt)
+        entry_id, tok_off, pin_off = c(entry_id, np.int32).reshape(-1), c(tok_off, np.int32).reshape(-1), c(pin_off, np.int32).reshape(-1)
+        n = entry_id.shape[0]
+        if tok_off.shape[0] != n + 1 or pin_off.shape[0] != n + 1:
+            raise DttsError(f"dict_table_edit: {n} entries need n + 1 offsets, got {tok_off.shape[0]} / {pin_off.shape[0]}")
+        key_map, pinyin, pinyin_map = c(key_map, np.float32), c(pinyin, np.int64), c(pinyin_map, np.int64)
+        if not rows_on_device:
+            keys = c(keys, np.float32)
+            values = None if values is None else c(values, np.float32)
+        p = lambda a: None if a is None else (a.ctypes.data if isinstance(a, np.ndarray) else int(a))
+        a = dict_edit_args(n, p(entry_id), p(tok_off), p(pin_off), p(key_map), p(pinyin), p(pinyin_map), p(keys), p(values), rows_on_device)
+        self._chk(self.lib.dtts_text2mel_fetch(self.h, DICT_EDIT, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_DICT_EDIT)")
+
+    def dict_table_entry(self, entry, stream, **dst):
+        """what the resident table holds for an entry (dtts_text2mel_fetch(DTTS_DICT_ENTRY)) -> (n_entries, L_e, P_e), read from the context's
+        host copy of the offsets; keywords: those of ``dict_entry_args`` — device destinations k / v f32 [L_e, hidden], key_map f32 [L_e],
+        pinyin / pinyin_map i64 [P_e], filled by copies enqueued on ``stream``.  entry = -1: only the count"""
+        a = dict_entry_args(entry, **dst)
+        self._chk(self.lib.dtts_text2mel_fetch(self.h, DICT_ENTRY, C.byref(a), stream), "dtts_text2mel_fetch(DTTS_DICT_ENTRY)")
+        return a.n_entries, a.L_e, a.P_e
 
     def text2mel_encode_ids(self, word_tokens, entry_ids, pron_modified, mel2word, B, T_w, L_k, P, stream):
         t_mel = C.c_int32(0)

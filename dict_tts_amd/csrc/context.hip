@@ -66,6 +66,8 @@ static const Unit UNITS[] = {
      DTTS_GLOSS_ENCODE, as_block<dtts_gloss_args, gloss_forward>, true},   // (an item outside the DTTS_OUT_* numbering: it is no output of an encode)
     {PART(PORTASPEECH), "ps.", build_ps, true, [](const dtts_ctx* h) { return h->ps_ready; },
      DTTS_PS_ENCODE, as_block<dtts_ps_args, ps_forward>, true},             // (the same: it is the baseline's encode itself)
+    {NO_PART, DTTS_DICT_EDIT, as_block<dtts_dict_edit_args, dict_edit_forward>, true},      // (the same: they change / read the id path's INPUT,
+    {NO_PART, DTTS_DICT_ENTRY, as_block<dtts_dict_entry_args, dict_entry_forward>, true},   //  the resident table; dict_edit.hip)
 };
 #undef PART
 #undef NO_PART

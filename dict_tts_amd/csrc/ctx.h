@@ -39,6 +39,7 @@
 #include "meldisc.h"
 #include "gloss.h"
 #include "portaspeech.h"
+#include "dict_edit.h"
 
 // dtts_config.tune_flags: the bits the library honours are listed at TUNE_RELEASE_MASK (context.hip)
 #define DTTS_TUNE(h, bit) (((h)->tune & (bit)) != 0)
@@ -223,6 +224,9 @@ struct dtts_ctx {
     int *t_off = nullptr, *t_poff = nullptr, *t_pmmax = nullptr;
     float *t_keys = nullptr, *t_values = nullptr, *t_key_map = nullptr;
     int64_t *t_pinyin = nullptr, *t_pinyin_map = nullptr;
+    // host mirrors of t_off / t_poff [t_entries + 1] and t_pmmax [t_entries], filled by the upload and by every edit (dict_edit.hip): an edit
+    // computes the new offsets on the host, DTTS_DICT_ENTRY answers L_e / P_e from them at once
+    std::vector<int> m_off, m_poff, m_pmmax;
     // ---- speaker conditioning (dtts_text2mel_speakers; modules/portaspeech/model.py:159-163, modules/dict_tts/model.py:44-45,94-96)
     int spk_kind = 0;                        // 0 = no spk_embed_proj loaded, DTTS_SPK_EMBED (Linear 256 -> hidden), DTTS_SPK_ID (Embedding)
     int spk_n = 0;                           // DTTS_SPK_ID: rows of the table (num_spk)
@@ -499,6 +503,8 @@ int build_fft_stack(dtts_ctx* h, Need& need, FftStack& S, const std::string& p, 
 int run_fft_stack(dtts_ctx* h, const FftStack& S, const float* x_in, const int* lens_in, const float* pos_table, int n_pos, int B, int T, int C,
                   int heads, float* y, const FftBufs& w, hipStream_t s);
 int gloss_forward(dtts_ctx* h, const dtts_gloss_args* a, hipStream_t stream);         // gloss.hip (the same)
+int dict_edit_forward(dtts_ctx* h, const dtts_dict_edit_args* a, hipStream_t stream);    // dict_edit.hip (the same)
+int dict_entry_forward(dtts_ctx* h, const dtts_dict_entry_args* a, hipStream_t stream);  // dict_edit.hip (the same; writes the block's out fields)
 
 // ---- a row of the one table of parts and block items (UNITS, context.hip): dtts_finalize_weights walks its parts in row order,
 // dtts_text2mel_fetch finds the item's forward in it, Block::finalized the part's ready predicate.  A row may be a part without an item

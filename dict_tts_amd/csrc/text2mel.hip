@@ -600,6 +600,9 @@ int dtts_dict_table_upload(dtts_handle h, int n_entries, const int32_t* tok_off,
     h->t_pinyin = n_pinyin;
     h->t_pinyin_map = n_pinyin_map;
     h->t_entries = n_entries;
+    h->m_off.assign(tok_off, tok_off + n_entries + 1);   // the host mirrors an edit starts from (dict_edit.hip)
+    h->m_poff.assign(pin_off, pin_off + n_entries + 1);
+    h->m_pmmax = std::move(pmmax);
     return DTTS_OK;
 }
 

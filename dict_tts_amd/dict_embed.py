@@ -31,35 +31,56 @@ def _np(t, dtype):
     return np.ascontiguousarray(t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t), dtype=dtype)
 
 
+def pack_items(items, pinyin_encoder=None, rows=True):
+    """the ragged packing of ``dict_embed`` items that ``table_from_items`` (a whole dictionary) and ``PortaSpeech_dict.edit_dict_table`` (the
+    edited entries) share.  pinyin_encoder: the list of pinyin strings the items' ``pinyin`` tokens are looked up in, or None when ``pinyin``
+    already holds ids.  An item may lack ``value`` (= its key).  rows=False leaves ``key`` / ``value`` where they are (device tensors): only
+    their shapes are read, and ``keys`` / ``values`` come back as None.
+    -> dict(tok_off i32 [n+1], pin_off i32 [n+1], key_map f32 [sum_L], pinyin i64 [sum_P], pinyin_map i64 [sum_P], D = the rows' width (None
+            without items), keys / values: lists of f32 arrays [L_i, D], same: every value equals its key)"""
+    index = None if pinyin_encoder is None else {tok: i for i, tok in reversed(list(enumerate(pinyin_encoder)))}   # list.index(): the first occurrence
+    n = len(items)
+    tok_off, pin_off = np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int32)
+    keys, values, key_map, pinyin, pinyin_map = [], [], [], [], []
+    same, D = True, None
+    for i, it in enumerate(items):
+        key = it["key"]
+        value = it["value"] if it.get("value") is not None else key
+        k, v = (_np(key, np.float32), _np(value, np.float32)) if rows else (key, value)
+        km = np.asarray(it["key_map"], np.float32)
+        pm = np.asarray(it["pinyin_map"], np.int64)
+        if index is None:
+            py = np.asarray(it["pinyin"], np.int64)
+        else:
+            py = np.array([index[t] for t in it["pinyin"]], np.int64)   # KeyError = a token the pinyin encoder does not hold
+        ks, vs = tuple(k.shape), tuple(v.shape)
+        if len(ks) != 2 or ks != vs or km.shape != (ks[0],) or pm.shape != py.shape or py.ndim != 1 or (D is not None and ks[1] != D):
+            raise ValueError(f"dict_embed item {i}: inconsistent shapes key {ks} value {vs} key_map {km.shape} "
+                             f"pinyin {py.shape} pinyin_map {pm.shape}")
+        D = ks[1]
+        if rows:
+            same = same and (key is value or np.array_equal(k, v))
+            keys.append(k)
+            values.append(v)
+        tok_off[i + 1] = tok_off[i] + ks[0]
+        pin_off[i + 1] = pin_off[i] + py.shape[0]
+        key_map.append(km)
+        pinyin.append(py)
+        pinyin_map.append(pm)
+    cat = lambda parts, dt: np.concatenate(parts) if parts else np.zeros(0, dt)
+    return {"tok_off": tok_off, "pin_off": pin_off, "key_map": cat(key_map, np.float32), "pinyin": cat(pinyin, np.int64),
+            "pinyin_map": cat(pinyin_map, np.int64), "D": D, "keys": keys if rows else None, "values": values if rows else None, "same": same}
+
+
 def table_from_items(items, pinyin_encoder):
     """items: the ``dict_embed`` items in word-id order; pinyin_encoder: list of pinyin strings (``pinyin_encoder.pkl``).
     -> dict(tok_off i32 [n+1], keys f32 [sum_L,D], values f32 [sum_L,D] or None when every value equals its key,
             key_map f32 [sum_L], pin_off i32 [n+1], pinyin i64 [sum_P], pinyin_map i64 [sum_P], L, P, ids)"""
-    index = {tok: i for i, tok in reversed(list(enumerate(pinyin_encoder)))}   # list.index(): the first occurrence
-    n = len(items)
-    tok_off, pin_off = np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int32)
-    keys, values, key_map, pinyin, pinyin_map = [], [], [], [], []
-    same = True
-    for i, it in enumerate(items):
-        k, v = _np(it["key"], np.float32), _np(it["value"], np.float32)
-        km = np.asarray(it["key_map"], np.float32)
-        pm = np.asarray(it["pinyin_map"], np.int64)
-        py = np.array([index[t] for t in it["pinyin"]], np.int64)   # KeyError = a token the pinyin encoder does not hold
-        if k.ndim != 2 or k.shape != v.shape or km.shape != (k.shape[0],) or pm.shape != py.shape:
-            raise ValueError(f"dict_embed item {i}: inconsistent shapes key {k.shape} value {v.shape} key_map {km.shape} "
-                             f"pinyin {py.shape} pinyin_map {pm.shape}")
-        same = same and (it["key"] is it["value"] or np.array_equal(k, v))
-        tok_off[i + 1] = tok_off[i] + k.shape[0]
-        pin_off[i + 1] = pin_off[i] + py.shape[0]
-        keys.append(k)
-        values.append(v)
-        key_map.append(km)
-        pinyin.append(py)
-        pinyin_map.append(pm)
-    return {"ids": {i: i for i in range(n)}, "tok_off": tok_off, "pin_off": pin_off, "keys": np.concatenate(keys),
-            "values": None if same else np.concatenate(values), "key_map": np.concatenate(key_map),
-            "pinyin": np.concatenate(pinyin), "pinyin_map": np.concatenate(pinyin_map),
-            "L": np.diff(tok_off), "P": np.diff(pin_off)}
+    p = pack_items(items, pinyin_encoder)
+    return {"ids": {i: i for i in range(len(items))}, "tok_off": p["tok_off"], "pin_off": p["pin_off"], "keys": np.concatenate(p["keys"]),
+            "values": None if p["same"] else np.concatenate(p["values"]), "key_map": p["key_map"],
+            "pinyin": p["pinyin"], "pinyin_map": p["pinyin_map"],
+            "L": np.diff(p["tok_off"]), "P": np.diff(p["pin_off"])}
 
 
 def table_from_dict_embed(path, pinyin_encoder):
@@ -71,7 +92,9 @@ def table_from_dict_embed(path, pinyin_encoder):
 
 
 def entry_ids_for_words(words, token_to_id, n_entries):
-    """the reference's per-character lookup (dataset_utils.py:313-318): unknown words use entry 2 ('<UNK>')"""
+    """the reference's per-character lookup (dataset_utils.py:313-318): unknown words use entry 2 ('<UNK>').  n_entries is the resident
+    table's CURRENT count: after ``PortaSpeech_dict.edit_dict_table(append=...)`` pass the new one (``dict_entries()``), and give the
+    appended words the ids it returned in ``token_to_id``"""
     out = []
     for w in words:
         i = token_to_id.get(w, 2)

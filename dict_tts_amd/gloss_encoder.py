@@ -164,12 +164,13 @@ class GlossEncoder(DeviceUnit):
 
     __call__ = encode
 
-    def build_items(self, entries, n_words):
+    def build_items(self, entries, n_words, device=False):
         """entries: {word id: [((initial, final_tone3), ids), ...]} — per word the glosses of its pronunciations in dictionary order, each
         with its pinyin pair and its token ids.  -> the ``n_words`` items of the binariser's ``dict_embed`` in word-id order (CPU tensors):
         key = value = the glosses' features concatenated, key_map ``[0] + [g + 1] * (L_g - 2) + [0]`` per gloss, pinyin the pairs
         concatenated, pinyin_map ``[g + 1] * 2``; a word without an entry gets the binariser's ``<UNK>`` item.  ``tokens_gloss`` holds the
-        token ids (the caller has the tokenizer that names them)"""
+        token ids (the caller has the tokenizer that names them).  device=True keeps ``key`` / ``value`` on the device (the '<UNK>' items'
+        zero rows too): gloss ids -> embeddings -> ``PortaSpeech_dict.edit_dict_table`` then never touches the host"""
         order = [w for w in range(int(n_words)) if w in entries and len(entries[w])]
         for w in entries:
             if not 0 <= int(w) < int(n_words):
@@ -178,12 +179,12 @@ class GlossEncoder(DeviceUnit):
         items = []
         for w in range(int(n_words)):
             if w not in entries or not len(entries[w]):
-                z = torch.zeros(3, self.hidden)
+                z = torch.zeros(3, self.hidden, device=self.device if device else None)
                 items.append({"tokens_gloss": ["O"], "key": z, "key_map": [0, 1, 0], "value": z.clone(), "pinyin": [UNK_PINYIN], "pinyin_map": [1]})
                 continue
             key, key_map, pinyin, pinyin_map, tokens = [], [], [], [], []
             for g, (pair, ids) in enumerate(entries[w]):
-                f = next(feats).cpu()
+                f = next(feats) if device else next(feats).cpu()
                 key.append(f)
                 key_map += [0] + [g + 1] * (f.shape[0] - 2) + [0]
                 pinyin += list(pair)

@@ -147,6 +147,60 @@ class PortaSpeech_dict(torch.nn.Module):
         self.ctx.dict_table_upload(table["tok_off"], table["keys"], table.get("values"), table["key_map"], table["pin_off"],
                                    table["pinyin"], table["pinyin_map"])
 
+    def edit_dict_table(self, replace=None, append=None, pinyin_encoder=None):
+        """change the resident dictionary in place (dtts_text2mel_fetch(DTTS_DICT_EDIT)): ``replace`` {entry id: item}, ``append`` [item, ...]
+        -> the ids of the appended entries.  Afterwards the table is, bit for bit, what ``upload_dict_table`` of the edited dictionary would
+        hold; other entries keep their ids (to delete a word, replace it with the '<UNK>' item).  An item is the binariser's ``dict_embed``
+        item: ``key`` [L, gloss_dim], optional ``value`` (= key), ``key_map`` [L], ``pinyin`` [P] (ids, or tokens of ``pinyin_encoder`` as
+        ``dict_embed.table_from_items`` takes them), ``pinyin_map`` [P]; ``key`` / ``value`` may be numpy arrays, CPU tensors or CUDA
+        tensors.  When every row of the call is a CUDA tensor the rows are concatenated on the device and never touch the host
+        (``GlossEncoder.build_items(device=True)``); otherwise they go through the host.  An administrative call: synchronous, with one
+        device synchronisation; not for every batch."""
+        from . import dict_embed
+        replace, append = dict(replace or {}), list(append or [])
+        n_old = self.dict_entries()
+        ids = sorted(int(e) for e in replace)
+        for e in ids:
+            if not 0 <= e < n_old:
+                raise ValueError(f"edit_dict_table: replace names entry {e}, the table holds {n_old} entries")
+        new_ids = list(range(n_old, n_old + len(append)))
+        items = [replace[e] for e in ids] + append
+        rows = [r for it in items for r in (it["key"], it.get("value")) if r is not None]
+        on_device = bool(rows) and all(isinstance(r, torch.Tensor) and r.is_cuda for r in rows)
+        p = dict_embed.pack_items(items, pinyin_encoder, rows=not on_device)
+        if p["D"] is not None and p["D"] != self.cfg.gloss_dim:
+            raise ValueError(f"edit_dict_table: the items' rows are {p['D']} wide, gloss_dim = {self.cfg.gloss_dim}")
+        stream = torch.cuda.current_stream().cuda_stream
+        if on_device:
+            f32 = lambda t: t.to(device=self.device, dtype=torch.float32)
+            keys = torch.cat([f32(it["key"]) for it in items]).contiguous()
+            separate = any(it.get("value") is not None and it["value"] is not it["key"] for it in items)
+            values = torch.cat([f32(it["value"] if it.get("value") is not None else it["key"]) for it in items]).contiguous() if separate else None
+            kp, vp = keys.data_ptr(), None if values is None else values.data_ptr()   # (alive until the call, which synchronises, returns)
+        else:
+            kp = np.concatenate(p["keys"]) if items else np.zeros((0, self.cfg.gloss_dim), np.float32)
+            vp = None if p["same"] else np.concatenate(p["values"])
+        self.ctx.dict_table_edit(ids + new_ids, p["tok_off"], p["pin_off"], p["key_map"], p["pinyin"], p["pinyin_map"], kp, vp, stream,
+                                 rows_on_device=on_device)
+        return new_ids
+
+    def dict_entries(self):
+        """entries of the resident table (0 before ``upload_dict_table``)"""
+        return self.ctx.dict_table_entry(-1, torch.cuda.current_stream().cuda_stream)[0]
+
+    def dict_entry(self, e):
+        """what the resident table holds for entry ``e`` (dtts_text2mel_fetch(DTTS_DICT_ENTRY)): device tensors ``K`` / ``V`` [L, hidden] (the
+        PROJECTED rows), ``key_map`` [L], ``pinyin`` / ``pinyin_map`` [P], and the ints ``L``, ``P``"""
+        stream = torch.cuda.current_stream().cuda_stream
+        _, L, P = self.ctx.dict_table_entry(int(e), stream)
+        out = lambda shape, dt=torch.float32: torch.empty(*shape, dtype=dt, device=self.device)
+        r = {"K": out((L, self.cfg.hidden_size)), "V": out((L, self.cfg.hidden_size)), "key_map": out((L,)),
+             "pinyin": out((P,), torch.int64), "pinyin_map": out((P,), torch.int64)}
+        self.ctx.dict_table_entry(int(e), stream, k=r["K"].data_ptr(), v=r["V"].data_ptr(), key_map=r["key_map"].data_ptr(),
+                                  pinyin=r["pinyin"].data_ptr(), pinyin_map=r["pinyin_map"].data_ptr())
+        r.update(L=L, P=P)
+        return r
+
     def _arm_speakers(self, spk_embed, B, stream):
         """project the batch's speakers and arm the next encode (modules/dict_tts/model.py:44-45; tasks/tts/dict_tts.py:182 passes
         sample['spk_ids'] with use_spk_id, sample['spk_embed'] otherwise); returns the device tensor the projection reads"""

@@ -1123,6 +1123,68 @@ typedef struct dtts_ps_args {
 } dtts_ps_args;
 
 /*
+ * Editing the resident dictionary — dtts_text2mel_fetch(h, DTTS_DICT_EDIT, (dtts_dict_edit_args*), stream), args->size = sizeof(*args): not a
+ * copy and not one of the DTTS_OUT_* outputs (it changes an INPUT of the id path: the table of dtts_dict_table_upload); it goes through the
+ * dispatcher of the block items so that the library keeps its entry points.  Replaces and appends entries of the resident table WITHOUT
+ * uploading the dictionary again: afterwards the table is, bit for bit, what dtts_dict_table_upload would have built from the edited
+ * dictionary (CSR offsets, K, V, key_map, pinyin, pinyin_map, the per-entry largest sense).  Entry order is kept; a replaced entry holds its new
+ * rows, appended entries come at the end; ids of other entries do not change.  There is no deletion: replace with the '<UNK>' item.
+ *   entry_id_host [n_edit] i32, strictly ascending: a value < n_entries replaces that entry; the values n_entries, n_entries + 1, ...
+ *     (contiguous, after the replacements) append.  tok_off_host / pin_off_host [n_edit + 1]: the ragged offsets (from 0) of the edited
+ *     entries' gloss rows and pinyin slots; an entry may have 0 rows or 0 slots.  key_map_host f32 [sum L], pinyin_host / pinyin_map_host
+ *     i64 [sum P]: HOST arrays, as in the upload.
+ *   keys / values f32 [sum L][gloss_dim]; values may be NULL = keys, as in the upload.  rows_on_device = 0: HOST pointers (staged on the
+ *     device by the call); 1: DEVICE pointers, 16-byte aligned, written by work enqueued earlier on `stream` (for example the gloss
+ *     encoder's output): the new rows never touch the host.
+ * Only the sum L new rows are projected (k_transform / v_transform, the upload's kernels: a row's bits do not depend on its position or
+ * on the row count); one segment-copy launch per array moves the unchanged runs of the old table and the projected rows into the new
+ * arrays, which are built BESIDE the old ones (transient memory: twice the table), then swapped in.  The work runs on `stream`, behind
+ * what the caller enqueued there; like the upload the call is synchronous for the host, and it synchronises the DEVICE once before it
+ * releases the previous arrays (nothing may still be using them).  It is therefore an ADMINISTRATIVE call, made when the dictionary
+ * changes, never per batch.  Encodes enqueued before the call read the old table, encodes after it the new one.
+ * A refused or failed edit leaves the previous table in use and intact.  n_edit = 0 succeeds and does nothing.
+ * DTTS_E_INVAL (naming the value), checked before the handle: a wrong size, n_edit < 0, a NULL array, ids that are negative or not strictly
+ * ascending, offsets that do not start at 0 or decrease, more than INT_MAX / 2 rows, a sense index above DTTS_MAX_SENSES in key_map or
+ * pinyin_map (the upload's wording), misaligned device rows; after it: appended ids that leave a gap behind n_entries, a table that would
+ * exceed INT_MAX / 2 rows.  DTTS_E_STATE: acoustic weights not finalised, no table resident, another current HIP device than the
+ * context's.  DTTS_E_NOMEM: the new arrays do not fit beside the old ones.
+ *
+ * Reading an entry back — dtts_text2mel_fetch(h, DTTS_DICT_ENTRY, (dtts_dict_entry_args*), stream): "what does the table hold for this
+ * word".  n_entries, L_e and P_e are filled at once from the context's host copy of the offsets; each device destination that is not NULL
+ * receives, by a copy enqueued on `stream`, the entry's projected rows K / V f32 [L_e][hidden], key_map f32 [L_e], pinyin / pinyin_map i64
+ * [P_e].  entry = -1 only reports n_entries (0 without a table).  Call once with NULL destinations for the sizes, then with buffers.
+ * DTTS_E_INVAL: a wrong size, a misaligned destination (both before the handle), an entry outside [-1, n_entries).  DTTS_E_STATE: no table
+ * resident (entry >= 0).
+ */
+#define DTTS_DICT_EDIT 69
+#define DTTS_DICT_ENTRY 70
+typedef struct dtts_dict_edit_args {
+    int32_t size;                    /* sizeof(dtts_dict_edit_args) */
+    int32_t n_edit;
+    int32_t rows_on_device;          /* 0: keys / values are host pointers; 1: device pointers, 16-byte aligned */
+    int32_t reserved;
+    const int32_t* entry_id_host;    /* [n_edit] */
+    const int32_t* tok_off_host;     /* [n_edit + 1] */
+    const int32_t* pin_off_host;     /* [n_edit + 1] */
+    const float* key_map_host;       /* [sum L] */
+    const int64_t* pinyin_host;      /* [sum P] */
+    const int64_t* pinyin_map_host;  /* [sum P] */
+    const float* keys;               /* [sum L][gloss_dim] */
+    const float* values;             /* the same shape, or NULL = keys */
+} dtts_dict_edit_args;
+typedef struct dtts_dict_entry_args {
+    int32_t size;                    /* sizeof(dtts_dict_entry_args) */
+    int32_t entry;                   /* 0 .. n_entries - 1, or -1: only n_entries */
+    int32_t n_entries, L_e, P_e;     /* out (host) */
+    int32_t reserved;
+    float* k_dev;                    /* [L_e][hidden] or NULL */
+    float* v_dev;                    /* [L_e][hidden] or NULL */
+    float* key_map_dev;              /* [L_e] or NULL */
+    int64_t* pinyin_dev;             /* [P_e] or NULL */
+    int64_t* pinyin_map_dev;         /* [P_e] or NULL */
+} dtts_dict_entry_args;
+
+/*
  * Output side — replaces the sample conversion of save_wav (utils/audio.py:11-16; called from after_infer,
  * tasks/tts/dict_tts.py:282-283) for a batch, on the device, so that the device->host copy is int16:
  * wav [B, T*hop] f32 as dtts_hifigan_forward wrote it, lens [B] i32 valid frames (NULL = T for all);
@@ -1183,7 +1245,8 @@ DTTS_API int dtts_debug_poke(dtts_handle h, dtts_stream stream);
 #define DTTS_TIMER_STAGE_DICT_ENCODER 4 /* 'dict_encoder' modules/dict_tts/model.py:86  = embedding, both encoders, S2PA                                   */
 #define DTTS_TIMER_STAGE_FVAE 5         /* 'fvae'         modules/dict_tts/model.py:57  = dtts_text2mel_decode (gather-expand + prior flow + decoder)       */
 #define DTTS_TIMER_STAGE_HIFIGAN 6      /* 'hifigan'      vocoders/hifigan.py:59        = dtts_hifigan_forward                                              */
-#define DTTS_TIMER_COUNT 7
+#define DTTS_TIMER_DICT_SEG_COPY 7      /* DTTS_DICT_EDIT: the segment-copy launch that moves the K array (one per edit; tools/dict_edit_bench.py)                 */
+#define DTTS_TIMER_COUNT 8
 DTTS_API int dtts_timer_enable(dtts_handle h, int which);
 DTTS_API int dtts_timer_read(dtts_handle h, int which, double* ms_total, int64_t* launches); /* synchronises */
 DTTS_API int dtts_timer_reset(dtts_handle h);
